@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the hot path (BASELINE.json metric): candidate views scored per second
 (+ Fisher scores per second) at 256x256 over 500k Gaussians.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path over one batch of synthetic input: the fused scorer (fr_fisher_views) ranks
 `--views` (64) candidate poses per GPU against a resident 500k-Gaussian map and a resident H_inv = 1/(H_train+0.1):
@@ -13,8 +13,14 @@ N = 1 : BASELINE.json configs[1] (500k Gaussians, 64 candidate 256x256 views, se
 N > 1 : configs[2]'s shape.  Default = weak scaling: every rank scores its own 64-view slice of a 64*N-view candidate
         set (seed 3); `--total-views T` = strong scaling: T views (configs[2]: 512) split over the ranks.  Either way the
         per-view scores are exchanged with ONE all-gather per step (RCCL over xGMI).
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects, plus the
-reported side numbers: serial_loop, compute_hessian_v1_ms, config4, columns_11, occupancy / frontier.
+Rank 0 prints ONE JSON line: the headline figure (metric, value, unit, higher_is_better, dtype) and `ms_per_step` of the K timed steps, and
+the `roofline` numbers the timed steps themselves give (kernel time from events around the scoring kernel).  A plain run does
+nothing else.  `--full` adds what takes runs of its own: the `cpu_baseline` and CPU occupancy / frontier legs, the parity of
+the oracle's scores, the calibrated VALU ceiling, the cached hardware counters, the measured copy rate, and the side numbers
+serial_loop, compute_hessian_v1_ms, api_pose_eval, config4, columns_11, gpu_occupancy_frontier.
+`--dump-outputs DIR` writes what the last timed step computed -- what a caller of the scorer receives: DIR/scores.npy (float32,
+the gathered per-view scores), DIR/vis_count.npy and DIR/num_rendered.npy (float64, per view) -- on inputs fixed by the
+arguments: H_inv is then the seeded weights of --synthetic-hinv.
 """
 import argparse
 import ctypes
@@ -370,8 +376,14 @@ def main():
     ap.add_argument("--total-views", type=int, default=0, help="strong scaling: this many views split over the ranks (configs[2]: 512)")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--columns", type=int, default=4)
-    ap.add_argument("--cpu-views", type=int, default=8, help="views of the 1-core CPU-baseline sample (0 = skip every side measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (CPU baselines, parity with the oracle, VALU ceiling, counters, copy rate, "
+                         "columns_11, serial loop, API latencies, config4, occupancy / frontier); a plain run only times the steps")
+    ap.add_argument("--cpu-views", type=int, default=8, help="with --full: views of the 1-core CPU-baseline sample (0 = skip every side measurement)")
     ap.add_argument("--dump-scores", type=str, default="", help="rank 0 writes the gathered scores of the last step to this .npy (tests)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (scores float32; vis_count, num_rendered float64); "
+                         "implies --synthetic-hinv, so that the inputs depend on the arguments alone")
     ap.add_argument("--seed", type=int, default=0, help="scene / pose seed (default: 2 on one GPU = configs[1], 3 on several = configs[2])")
     ap.add_argument("--tile-capacity", type=int, default=-1, help="A/B: keys per fixed (view, tile) segment (FisherScorer's default when negative; 0 = packed lists)")
     ap.add_argument("--spatial-order", action="store_true", help="A/B: lay the Gaussians out along a Z-curve (fr_spatial_order; FisherScorer's option, off by default)")
@@ -379,6 +391,11 @@ def main():
                     help="tests: H_inv = seeded uniform weights instead of 1/(H_train+0.1) (H_train is accumulated with float atomics, "
                          "so its last bits differ from run to run; with fixed weights the scores of two runs can be compared bit for bit)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # H_train is accumulated with float atomics (its last bits differ from run to run and from build to build): dumped outputs are
+    # computed on the seeded weights instead, so that two runs -- or two builds -- see the same inputs
+    synthetic_hinv = a.synthetic_hinv or bool(a.dump_outputs)
 
     if a.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: this process has made no GPU call; it starts the N ranks as a fresh child
@@ -396,7 +413,7 @@ def main():
     cpu_legs = None
     if rank == 0:
         entry.build()                                   # (imports the package; touches no device)
-        if world == 1 and a.cpu_views > 0:
+        if a.full and world == 1 and a.cpu_views > 0:
             # host-core baselines first: worker processes are forked before this process has any GPU state
             from oracle import occupancy_frontier
             cpu_legs = dict(cpu_baseline=cpu_baseline(P, W, H, seed, a.cpu_views, C, a.total_views if a.total_views > 0 else a.views),
@@ -453,7 +470,7 @@ def main():
     H_train = torch.zeros((P, C), dtype=torch.float32, device=dev)
     D.sharded_h_train(lambda w, Hacc: scorer.run(w, out_H=Hacc), kf, H_train)
     H_inv = torch.reciprocal(H_train + 0.1)
-    if a.synthetic_hinv:
+    if synthetic_hinv:
         H_inv = (torch.rand((P, C), generator=torch.Generator().manual_seed(seed + 7)) * 3.0 + 0.05).to(dev)
     first = scorer.run(w2c, H_inv=H_inv)      # sizes the tile-instance buffer (may re-run on overflow)
     num_rendered = first["num_rendered"].cpu().numpy().astype(np.int64)
@@ -499,6 +516,19 @@ def main():
     dt = float(t_max.item())
     if rank == 0 and a.dump_scores:
         np.save(a.dump_scores, host_scores.numpy().copy())
+    if a.dump_outputs:
+        # what FisherScorer.run hands its caller for the last timed step, all views in order: the scores (gathered over the ranks
+        # by the step itself) and the per-view counts (gathered here, outside the timed region; exact in float64)
+        counts = {k: last[k].cpu().numpy().astype(np.float64) for k in ("vis_count", "num_rendered")}
+        if dist_on:
+            parts = [None] * world
+            dist.all_gather_object(parts, counts)
+            counts = {k: np.concatenate([p[k] for p in parts]) for k in counts}
+        if rank == 0:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, "scores.npy"), host_scores.numpy().astype(np.float32))
+            for k, v in counts.items():
+                np.save(os.path.join(a.dump_outputs, f"{k}.npy"), v)
 
     if rank == 0:
         views_per_s = V_total * a.steps / dt
@@ -514,12 +544,13 @@ def main():
         # whole-path algorithmic bytes per view, SURVEY.md 8(d)
         B_view = (12 * P + 44 * vis_count.mean() + 24 * num_rendered.mean() + 40 * num_rendered.mean() +
                   40 * num_rendered.mean() + 24 * W * H + 8 * W * H + 4 * C * P)
-        pm, pmc_meta = pmc_record(P, V, W, C)
+        # the cached counters and the VALU ceiling (a microbenchmark run of its own): --full only
+        pm, pmc_meta = pmc_record(P, V, W, C) if a.full else (None, None)
         if pm and pm.get("dispatches_per_step") != launches_per_step:
             pm, pmc_meta = None, dict(pmc_meta, fresh=False, why="counters were taken with another number of view groups per step")
         # per LAUNCH like `achieved`: the record sums the step's dispatches
         traffic = pm["hbm_bytes_per_step"] / launches_per_step if pm and pm.get("hbm_bytes_per_step") else None
-        ceil = valu_ceiling() if world == 1 else None
+        ceil = valu_ceiling() if (a.full and world == 1) else None
         valu = None
         if pm and pm.get("SQ_INSTS_VALU") and kern_ms == kern_ms:
             step_ms = kern_ms * launches_per_step                    # the step's dispatches, summed
@@ -539,7 +570,8 @@ def main():
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{P} Gaussians (room_shell seed {seed}), {V_total} candidate {W}x{H} views per step"
-                                   f" ({V} on this GPU), Fisher columns {C}, H_inv from 16 keyframes; BASELINE.json configs[{1 if world == 1 else 2}]",
+                                   f" ({V} on this GPU), Fisher columns {C}, "
+                                   f"{'H_inv = seeded weights' if synthetic_hinv else 'H_inv from 16 keyframes'}; BASELINE.json configs[{1 if world == 1 else 2}]",
                        "gaussians": P, "views_per_gpu": V, "views_total": V_total, "image": [H, W], "columns": C,
                        "tile_instances_per_view": float(num_rendered.mean()), "listed_tile_instances_per_view": R / max(V, 1),
                        "visible_per_view": float(vis_count.mean()),
@@ -560,9 +592,9 @@ def main():
             "path": {"bytes_per_view": float(B_view), "achieved_GBps": float(B_view * views_per_s / world / 1e9),
                      "frac_of_hbm_peak": float(B_view * views_per_s / world / 1e9 / HBM_PEAK_GBS)},
         }
-        if world == 1:
+        if a.full and world == 1:
             out["roofline"]["measured_copy_GBps"] = measured_copy_bandwidth(dev)
-        if world == 1 and a.cpu_views > 0:
+        if a.full and world == 1 and a.cpu_views > 0:
             if C == 4:
                 # the same workload with the 11 Fisher columns of GaussianObjectSLAM, reported next to the headline
                 sc11 = FisherScorer(cam, *(act[k].to(dev) for k in ("means3D", "rgb_colors", "rotations", "opacities", "scales")),

@@ -20,10 +20,20 @@ COMMON = ["--steps", "2", "--warmup", "1", "--cpu-views", "0", "--gaussians", "3
 def _run(cmd, env_extra, out_npy):
     env = dict(os.environ, **env_extra)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    r = subprocess.run(cmd + ["--dump-scores", out_npy], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    # --dump-outputs (the last step's scores and per-view counts) beside the .npy: <name>_out/ (COMMON already fixes H_inv)
+    r = subprocess.run(cmd + ["--dump-scores", out_npy, "--dump-outputs", out_npy[:-len(".npy")] + "_out"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     return json.loads(line), np.load(out_npy)
+
+
+def _same_outputs(tmp_path, first, *others):
+    """every array `--dump-outputs` wrote for the runs `others` equals the run `first`'s, bit for bit, views in order"""
+    for k in ("scores", "vis_count", "num_rendered"):
+        want = np.load(tmp_path / f"{first}_out" / f"{k}.npy")
+        assert want.shape == (16,)
+        for o in others:
+            assert np.array_equal(np.load(tmp_path / f"{o}_out" / f"{k}.npy"), want), (o, k)
 
 
 def _two_ranks(args, out_npy, port):
@@ -44,6 +54,7 @@ def test_two_rank_bench_equals_one_rank(gpu, tmp_path):
         assert j["metric"] == one["metric"] == "candidate-views/sec" and j["value"] > 0 and j["cpu_baseline"] is None
         assert j["roofline"]["kernel"] == "k_fisher_tile_v4" and j["roofline"]["kernel_ms"] > 0
     assert one["n_gpus"] == 1 and one["build"]["build_id"].startswith("FRSRC:")
+    _same_outputs(tmp_path, "one", "weak", "strong")
 
 
 def test_plain_command_starts_its_own_ranks(gpu, tmp_path):
@@ -62,6 +73,7 @@ def test_plain_command_starts_its_own_ranks(gpu, tmp_path):
     assert np.array_equal(s1, s2)
     weak, sw = _run([sys.executable, "bench.py", "--gpus", "2", "--views", "8"] + COMMON, env, str(tmp_path / "weak.npy"))
     assert weak["scaling"] == "weak" and weak["config"]["views_total"] == 16 and np.array_equal(sw, s1)
+    _same_outputs(tmp_path, "one", "two", "weak")
 
 
 def test_one_rank_process_group_runs_the_collectives_through_rccl(gpu, tmp_path):
@@ -76,3 +88,4 @@ def test_one_rank_process_group_runs_the_collectives_through_rccl(gpu, tmp_path)
     assert coll["collectives"]["backend"] == "nccl" and coll["collectives"]["world_size"] == 1
     assert "collectives" not in plain
     assert np.array_equal(s0, s1)
+    _same_outputs(tmp_path, "plain", "rccl")

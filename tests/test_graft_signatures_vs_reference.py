@@ -1,17 +1,17 @@
-"""CPU, build container only: every method `install()` grafts onto the reference's classes must be callable the way the reference's
-own method of that name is -- same positional parameter names in the same order, a default wherever the reference has one, and
-nothing but defaulted parameters added behind.  The reference sources are PARSED (ast; nothing is imported, executed, copied or
-shipped); the test skips where /root/reference does not exist (the GPU box)."""
+"""CPU: every method `install()` grafts onto the reference's classes must be callable the way the reference's own method of that
+name is -- same positional parameter names in the same order, a default wherever the reference has one, and nothing but
+defaulted parameters added behind.  The reference side is tests/golden/reference_signatures.json: the parameter lists and the
+tester's call sites, read out of the reference sources by PARSING them (ast; nothing is imported, executed, copied or shipped;
+tests/golden/make_reference_signatures.py regenerates it from a reference checkout)."""
 import ast
+import json
 import os
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fisher-nerf-customized_amd")
-REF = "/root/reference"
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_signatures.json")
 
 # (reference file, reference class, product file, product mixin class(es) that hold the grafted methods)
 TARGETS = [
@@ -19,6 +19,9 @@ TARGETS = [
     ("models/SLAM/gaussian_object.py", "GaussianObjectSLAM", "models/SLAM/gaussian_object.py", ("ObjectFisherOps",)),
     ("planning/astar.py", "AstarPlanner", "planning/astar.py", ("OccupancyOps",)),
 ]
+# the reference's caller of the grafted Fisher methods, and the methods whose calls there are checked
+TESTER = "tester_gaussians_navigation.py"
+CALLED = ("compute_Hessian", "compute_H_train", "pose_eval", "pose_eval_popgs", "compute_H_train_popgs")
 # what the product adds that the reference class does not have (helpers and new operators): allowed, but named here so that a
 # typo in a grafted name cannot hide as "new"
 NEW_IN_PRODUCT = {
@@ -28,6 +31,7 @@ NEW_IN_PRODUCT = {
     "OccupancyOps": {"_fbe_point", "_ring_candidates", "generate_candidate_in_freespace", "_next_seed", "_eroded_free", "filter_candidates_in_freespace", "cells_of", "_occ_cfg",
                      "_occ_workspace", "_stream"},
 }
+STALE = "(a graft changed: regenerate tests/golden/reference_signatures.json with tests/golden/make_reference_signatures.py)"
 
 
 def _classes(path):
@@ -57,11 +61,16 @@ def _grafted_names(install_fn):
     return names
 
 
+def _reference():
+    with open(FIXTURE) as f:
+        return json.load(f)
+
+
 @pytest.mark.parametrize("ref_file,ref_cls,our_file,mixins", TARGETS)
 def test_grafted_methods_accept_the_reference_call_forms(ref_file, ref_cls, our_file, mixins):
-    ref_classes = _classes(os.path.join(REF, ref_file))
-    assert ref_cls in ref_classes, f"{ref_cls} not found in {ref_file}"
-    ref_methods = _methods(ref_classes[ref_cls])
+    ref_classes = _reference()["classes"]
+    assert ref_cls in ref_classes and ref_classes[ref_cls]["file"] == ref_file, f"{ref_cls} of {ref_file} not in the fixture"
+    ref_methods = ref_classes[ref_cls]["methods"]
     ours = _classes(os.path.join(PKG, our_file))
     checked = 0
     for mixin in mixins:
@@ -71,10 +80,11 @@ def test_grafted_methods_accept_the_reference_call_forms(ref_file, ref_cls, our_
         assert grafted, f"{mixin}.install grafts nothing?"
         for name in grafted:
             if name not in ref_methods:
-                assert name in NEW_IN_PRODUCT[mixin], f"{mixin}.install grafts `{name}`, which {ref_cls} does not define and the test does not list as new"
+                assert name in NEW_IN_PRODUCT[mixin], f"{mixin}.install grafts `{name}`, which {ref_cls} does not define and the test does not list as new {STALE}"
                 continue
             assert name in ours_methods, f"{mixin} has no method `{name}` to graft"
-            r_pos, r_ndef, r_kwonly, r_var, r_kw = _signature(ref_methods[name])
+            r = ref_methods[name]
+            r_pos, r_ndef, r_kwonly, r_var = r["pos"], r["ndefaults"], r["kwonly"], r["vararg"]
             o_pos, o_ndef, o_kwonly, o_var, o_kw = _signature(ours_methods[name])
             # positional call forms: the reference's parameters, by name and order, lead ours
             assert o_pos[:len(r_pos)] == r_pos, f"{ref_cls}.{name}: reference parameters {r_pos}, graft {o_pos}"
@@ -95,26 +105,22 @@ def test_the_reference_call_sites_pass_only_arguments_the_grafts_take():
     """The call sites the grafts serve (tester_gaussians_navigation.py:1423-2204): every keyword a call of compute_Hessian /
     compute_H_train / pose_eval* passes there is a parameter of the grafted method, and no call passes more positional arguments
     than it takes."""
-    src = open(os.path.join(REF, "tester_gaussians_navigation.py")).read()
-    tree = ast.parse(src)
+    sites = _reference()["call_sites"]
+    assert sites["file"] == TESTER
     ours = {}
     ours.update(_methods(_classes(os.path.join(PKG, "models/SLAM/gaussian.py"))["FisherOps"]))
     obj = _methods(_classes(os.path.join(PKG, "models/SLAM/gaussian_object.py"))["ObjectFisherOps"])
-    used = {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute)}
-    assert {"compute_Hessian", "compute_H_train", "pose_eval"} <= used
+    assert {"compute_Hessian", "compute_H_train", "pose_eval"} <= set(sites["attributes_used"])
     n_calls = 0
-    for node in ast.walk(tree):
-        if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)):
-            continue
-        name = node.func.attr
-        if name not in ("compute_Hessian", "compute_H_train", "pose_eval", "pose_eval_popgs", "compute_H_train_popgs"):
-            continue
+    for call in sites["calls"]:
+        name, line = call["name"], call["line"]
+        assert name in CALLED
         for table in (ours, obj):
             if name not in table:
                 continue
             pos, _, kwonly, var, kw = _signature(table[name])
-            assert var or len(node.args) <= len(pos), f"line {node.lineno}: {name} called with {len(node.args)} positional arguments, graft takes {pos}"
-            for k in node.keywords:
-                assert k.arg is None or kw or k.arg in pos or k.arg in kwonly, f"line {node.lineno}: {name}({k.arg}=...) is not a parameter of the graft {pos}"
+            assert var or call["n_args"] <= len(pos), f"line {line}: {name} called with {call['n_args']} positional arguments, graft takes {pos}"
+            for k in call["keywords"]:
+                assert k is None or kw or k in pos or k in kwonly, f"line {line}: {name}({k}=...) is not a parameter of the graft {pos}"
             n_calls += 1
     assert n_calls >= 8
