@@ -644,11 +644,12 @@ __device__ __forceinline__ void fr_fisher_record_one(const FrParams& p, const fl
                                                      const float* __restrict__ packed, float4* __restrict__ recq, int v, uint32_t id,
                                                      const float* vm, const float* pm, const float* wm, bool has_w2c,
                                                      float4* out6 = nullptr, const float4* ab_src = nullptr);
-// float4 per compact record of a front-end mode: AF 0 = score form, 1 = A-form of k_fisher_tile_v3h, 2 = general out_H form
+// float4 per compact record of a front-end mode: AF 0 = score form, 1 = A-form of k_fisher_tile_v3h, 2 = general out_H form,
+// 3 = pose form of k_fisher_pose_tile (the general 4-column form with the camera-frame mean in the place of the colour)
 // (score form with fixed key segments: 5 -- the 80 bytes the walk parks, k3 in the place of the footprint extents, which the tile
 // kernel then no longer needs: its keys say which strips a splat reaches and the footprint rows come from the conic itself)
-template <int C, int AF, bool DK = false> struct FrRecStride { static constexpr int value = AF == 2 ? (C >= 11 ? 13 : 7) : ((AF == 0 && DK) ? 5 : 6); };
-template <int C>
+template <int C, int AF, bool DK = false> struct FrRecStride { static constexpr int value = AF >= 2 ? (C >= 11 ? 13 : 7) : ((AF == 0 && DK) ? 5 : 6); };
+template <int C, bool POSE = false>
 __device__ __forceinline__ void fr_fisher_record_general(const FrParams& p, const float* __restrict__ packed, int v, uint32_t id,
                                                          const float* vm, const float* pm, const float* wm, bool has_w2c,
                                                          float4* out, const float4* ab_src);
@@ -934,7 +935,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 template <int C, int AF, bool DK>
 __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, FrRecordArgs ra)
 {
-	static_assert((C == 4 || C == 11) && AF >= 0 && AF <= 2 && !(AF == 1 && C != 4), "records modes: score form, A-form (4 columns), general out_H form");
+	static_assert((C == 4 || C == 11) && AF >= 0 && AF <= 3 && !((AF == 1 || AF == 3) && C != 4), "records modes: score form, A-form (4 columns), general out_H form, pose form (4 columns)");
 	constexpr int RS = FrRecStride<C, AF, DK>::value; // float4 per compact record
 	extern __shared__ uint32_t fr_dyn_lds[];     // hist[VC][T] | pairs[FR_THREADS * (VC + 1)] | wm[VC][12] | park[13][FR_THREADS] | DK: cursor[VC][T]
 	const int VC = p.VC;
@@ -1255,7 +1256,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 				for (int k = 0; k < 12; k++) wm[k] = has_w2c ? s_wm[12 * cvv + k] : 0.f;
 				float4* rec_out = ra.comp + ((size_t)v * PV + slot) * RS;
 				FR_ABL(if (p.ablate == 37) rec_out = ra.comp + (size_t)tid * RS;)     // 37: the records' arithmetic without their HBM traffic
-				if constexpr (AF == 2) fr_fisher_record_general<C>(p, ra.packed, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
+				if constexpr (AF >= 2) fr_fisher_record_general<C, (AF == 3)>(p, ra.packed, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
 				else fr_fisher_record_one<C, false, (AF == 1), (AF == 0 && DK)>(p, ra.H_inv, ra.hinv_stride, ra.packed, ra.recq, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
 				if constexpr (DK)
 				{
@@ -1272,7 +1273,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 					en.xy0 = park[10 * FR_THREADS + r]; en.xy1 = park[11 * FR_THREADS + r];
 					*(uint4*)(p.vis_list + ((size_t)v * nblk + blockIdx.x) * cap + (rk & 0xffffu)) = *(const uint4*)&en;
 				}
-				if constexpr (AF != 0) ra.slot_idx[(size_t)v * PV + slot] = p.order ? p.order[idx] : idx;    // (the out_H kernels go back to the caller's index)
+				if constexpr (AF == 1 || AF == 2) ra.slot_idx[(size_t)v * PV + slot] = p.order ? p.order[idx] : idx;    // (the out_H kernels go back to the caller's index)
 			}
 		}
 		// what is left over moves to the front of the list
@@ -3239,7 +3240,9 @@ __device__ __forceinline__ void fr_fisher_record_one(const FrParams& p, const fl
 //   q[0..14] the three mean rows over gamma(u) (fr_mean_rows_g)   q[15] 1 / opacity^2   q[16..18] r, g, b   q[19] 0
 //   C = 11:  q[20..40] the seven scale / rotation rows over (ux^2, ux uy, uy^2)   q[41..43] 0
 // = 7 float4 at C = 4, 13 at C = 11 (odd strides: sixteen consecutive parked records cover all LDS banks).
-template <int C>
+// POSE (C = 4, k_fisher_pose_tile): q[16..18] = the camera-frame mean m = rel_w2c x (the lever arm of the rotation columns); the walk
+// needs the colours only as their sum, which recB.w already holds.
+template <int C, bool POSE>
 __device__ __forceinline__ void fr_fisher_record_general(const FrParams& p, const float* __restrict__ packed, int v, uint32_t id,
                                                          const float* vm, const float* pm, const float* wm, bool has_w2c,
                                                          float4* out, const float4* ab_src)
@@ -3263,7 +3266,7 @@ __device__ __forceinline__ void fr_fisher_record_general(const FrParams& p, cons
 	out[3] = make_float4(Rg[0][4], Rg[1][0], Rg[1][1], Rg[1][2]);
 	out[4] = make_float4(Rg[1][3], Rg[1][4], Rg[2][0], Rg[2][1]);
 	out[5] = make_float4(Rg[2][2], Rg[2][3], Rg[2][4], inv_o * inv_o);
-	out[6] = make_float4(gsv[9], gsv[10], gsv[11], 0.f);
+	out[6] = POSE ? make_float4(po.x, po.y, po.z, 0.f) : make_float4(gsv[9], gsv[10], gsv[11], 0.f);
 	if constexpr (SR)
 	{
 		const fr_f3 sc = { gsv[12], gsv[13], gsv[14] };
@@ -4812,6 +4815,132 @@ __global__ __launch_bounds__(FR_THREADS) void k_fisher_tile_v3g(FrParams p, FrFi
 		__builtin_amdgcn_wave_barrier();
 	};
 	fr_strip_pass<16, 4, NQ, decltype(pass2), EF4>(gk, n, rec, sA, rq, sQ, wq, ent, lane, strip_lo, tile_x0, f.key_shift, wave, done, pass2);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Camera-pose Fisher information of a candidate view (fr_fisher_pose_views).  The view is rendered as fr_fisher_views renders it:
+// camera-frame means m_i = rel_w2c x_i through a camera with viewmatrix = I; rotations, scales, opacities and colours do not move
+// with the pose.  A left perturbation m_i(xi) = exp(xi^) m_i, xi = (rho, phi) translation first, has dm_i / dxi = [I | -[m_i]x].
+// With g_{p,i} pixel p's share of dL/dm_i (upstream gradient dL on every channel; the mean2D path and the cov2D-through-J(t) path of
+// backward.cu:335-475 with the limx / limy clamp -- cur_dL_dmeans of the reference's fused backward)
+//     j_p = sum_i [ g_{p,i} ; m_i x g_{p,i} ]            pose_H = sum_p j_p j_p^T        (6 x 6, symmetric PSD)
+// -- the point Fisher's backward_power = 2 convention: channels summed, then squared per pixel.  Contributor sets, cut-offs,
+// alpha <= 0.99 and the T < 1e-4 end are the forward's; decisions are held fixed, as in every backward here.
+// The pose gradient of a pixel is a signed SUM over its contributors, not a sum of per-pair squares, so the unknown back-to-front
+// colour X enters it linearly: with w_i = opacity G_i (p_i - X b_i) (notation of k_fisher_records) and r_i = R_i^T gamma(u) from the
+// record's three mean rows, g_{p,i} = dL w_i r_i, and a lane keeps two 6-vectors over e_i = opacity G_i [r_i ; m_i x r_i]:
+//     sP = sum (p_i - Xt b_i) e_i ,   sB = sum b_i e_i ,    j_p = dL (sP - (X - Xt) sB)
+// about the centre Xt = the first contributor's colour (as the scorer's sums: no cancellation on low-contrast pixels).  ONE front-to-back
+// walk, the strip / wave skeleton of k_fisher_tile_v3g.  The pixel's 21 upper-triangle products are summed over the wave by a butterfly
+// and over the four waves in LDS, in double and in a fixed order, and the workgroup writes its plain partial [V][T][21] (no atomics);
+// k_pose_reduce sums the tiles in order.  So the result is deterministic, and a view's value does not depend on the other views of the batch.
+__global__ __launch_bounds__(FR_THREADS) void k_fisher_pose_tile(FrParams p, FrFisherArgs f, double* __restrict__ part)
+{
+	constexpr int NQ = 5, EF4 = 2 + NQ;            // the pose record: {recA, recB} + mean rows and 1/o^2 + camera-frame mean
+	__shared__ uint32_t s_q[4][FR_QCAP];
+	__shared__ float4 s_ent[4][64][EF4];
+	__shared__ double s_red[4][21];
+	if (p.status[1]) return;
+	const int tid = threadIdx.x, lane = tid & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	uint32_t tile; int v;
+	fr_tile_of_block(p, tile, v);
+	const uint32_t tx = tile % p.gx, ty = tile / p.gx;
+	const uint32_t bx0 = tx * FR_BLOCK_X, by0 = ty * FR_BLOCK_Y + (uint32_t)wave * 4u;
+	const uint32_t pxx = bx0 + (uint32_t)(lane & 15), pxy = by0 + (uint32_t)(lane >> 4);
+	const bool inside = pxx < (uint32_t)p.W && pxy < (uint32_t)p.H;
+	const float pfx = (float)pxx, pfy = (float)pxy;
+	const size_t vt = (size_t)v * p.T + tile;
+	const uint32_t n = p.tile_cnt[vt];
+	const uint64_t* gk = p.keys + p.tile_off[vt];
+	const float4* rec = f.recA + (size_t)v * f.ab_view;
+	const float4* rq = f.recQ + (size_t)v * f.q_view;
+	const size_t sA = (size_t)f.ab_stride, sQ = (size_t)f.q_stride;
+	uint32_t* wq = s_q[wave];
+	float4 (*ent)[EF4] = s_ent[wave];
+	const float strip_lo = (float)by0, tile_x0 = (float)bx0;
+
+	float T = 1.0f, Xt = 0.f;
+	double Cg = 0.0;
+	bool done = !inside;
+	float sP[6], sB[6];
+#pragma unroll
+	for (int k = 0; k < 6; k++) { sP[k] = 0.f; sB[k] = 0.f; }
+	auto walk = [&](uint32_t, uint32_t, unsigned long long emask) {
+		unsigned long long mask = fr_wave_transpose64(emask, lane);
+		if (done) mask = 0ull;
+		while (mask != 0ull)
+		{
+			const int j = __ffsll((long long)mask) - 1;
+			mask &= mask - 1ull;
+			const float4 a4 = ent[j][0], b44 = ent[j][1];
+			const fr_v4f a = { a4.x, a4.y, a4.z, a4.w }, b4 = { b44.x, b44.y, b44.z, b44.w };
+			const FrPairAlpha g = fr_pair_alpha(a, b4, pfx, pfy);
+			const float cg = b44.w;
+			const float T_i = T;
+			bool con;
+			const bool kill = fr_prefix_update(g, cg, T, Cg, con);
+			if (con)
+			{
+				Xt = T_i == 1.0f ? cg : Xt;                                       // centre: the first contributor's colour
+				const float bi = 1.0f / g.om1;
+				const float pc = (float)(Cg - (double)Xt) * bi + T_i * cg;      // p_i - Xt b_i
+				const float dx = g.dx, dy = g.dy;
+				const float u0 = b4.x * dx + (b4.x * dx + b4.y * dy);            // u = -conic d
+				const float u1 = 2.0f * (b4.z * dy) + b4.y * dx;
+				const float u2 = u0 * u0, u3 = u0 * u1, u4 = u1 * u1;
+				const float4 q0 = ent[j][2], q1 = ent[j][3], q2 = ent[j][4], q3 = ent[j][5], m = ent[j][6];
+				float e[6];
+				e[0] = g.a_un * (q0.x * u0 + q0.y * u1 + q0.z * u2 + q0.w * u3 + q1.x * u4);
+				e[1] = g.a_un * (q1.y * u0 + q1.z * u1 + q1.w * u2 + q2.x * u3 + q2.y * u4);
+				e[2] = g.a_un * (q2.z * u0 + q2.w * u1 + q3.x * u2 + q3.y * u3 + q3.z * u4);
+				e[3] = m.y * e[2] - m.z * e[1];                                   // m x r
+				e[4] = m.z * e[0] - m.x * e[2];
+				e[5] = m.x * e[1] - m.y * e[0];
+#pragma unroll
+				for (int k = 0; k < 6; k++) { sP[k] += pc * e[k]; sB[k] += bi * e[k]; }
+			}
+			if (kill) { mask = 0ull; done = true; }
+		}
+	};
+	fr_strip_pass<16, 4, NQ, decltype(walk), EF4>(gk, n, rec, sA, rq, sQ, wq, ent, lane, strip_lo, tile_x0, f.key_shift, wave, done, walk);
+
+	// j_p, its 21 products, their sums over the wave (butterfly) and over the four waves (LDS, in wave order)
+	const double X = Cg + (double)(T * (p.bg[0] + p.bg[1] + p.bg[2]));
+	const float dlt = (float)(X - (double)Xt);
+	float jp[6];
+#pragma unroll
+	for (int k = 0; k < 6; k++) jp[k] = inside ? f.dL * (sP[k] - dlt * sB[k]) : 0.f;
+#pragma unroll
+	for (int a = 0, e = 0; a < 6; a++)
+#pragma unroll
+		for (int b = a; b < 6; b++, e++)
+		{
+			double h = (double)(jp[a] * jp[b]);
+#pragma unroll
+			for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o, 64);
+			if (lane == 0) s_red[wave][e] = h;
+		}
+	__syncthreads();
+	if (tid < 21) part[vt * 21 + (size_t)tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+}
+
+// [V][T][21] partials -> [V][6][6] (both triangles), the tiles summed in order in double; the caller's status word as k_reduce_scores
+// writes it.  On overflow nothing is written.
+__global__ __launch_bounds__(64) void k_pose_reduce(const double* __restrict__ part, int T, const int* __restrict__ status,
+                                                    float* __restrict__ out, int* __restrict__ status_out)
+{
+	if (blockIdx.x == 0 && threadIdx.x == 0) { status_out[0] = status[0]; status_out[1] = status[1]; status_out[2] = status[2]; status_out[3] = status[3]; }
+	if (status[1]) return;
+	const int v = blockIdx.x, e = threadIdx.x;
+	if (e >= 21) return;
+	int a = 0, b = e, w = 6;
+	while (b >= w) { b -= w; a++; w--; }
+	b += a;                                          // (a, b): the e-th entry of the upper triangle, row by row
+	double s = 0.0;
+	for (int t = 0; t < T; t++) s += part[((size_t)v * T + t) * 21 + e];
+	out[(size_t)v * 36 + a * 6 + b] = (float)s;
+	out[(size_t)v * 36 + b * 6 + a] = (float)s;
 }
 
 // fr_fisher_cfg.poses_are_c2w: the caller hands camera-to-world poses (what pose_eval receives, gaussian.py:1354-1362) and the
@@ -6754,7 +6883,7 @@ struct FrJoinGuard {
 
 // Score-only mode: the front end also produces the scorer's per-(view, Gaussian) records (k_pack_static, then phase C of
 // k_preprocess_views; with the single-view front end, k_fisher_records after k_scatter_keys, beside the sorts, on the second side stream).
-struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; };   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
+struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; bool pose = false; };   // pose: the records of k_fisher_pose_tile (fr_fisher_pose_views)   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
 template <int C> __global__ void k_pack_static(FrParams p, const float* __restrict__ H_inv, float* __restrict__ packed, float4* __restrict__ mt, float4* __restrict__ grp);
 template <int C, bool LIST, bool FORM_A> __global__ void k_fisher_records(FrParams p, FrRecordArgs ra);
 
@@ -6811,7 +6940,9 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 		// against 2.53 ms: the records' waves slow the latency-bound scatter and the one-workgroup-per-CU sort tier down.)
 		const bool dk = p.tile_cap != 0;
 		const size_t lds_c = lds_c_of(p.VC);
-		if (once && plan->general && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 2, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		if (once && plan->pose && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 3, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->pose) hipLaunchKernelGGL((k_preprocess_views_c<4, 3, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->general && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 2, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->general && plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views_c<4, 2, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->general && dk) hipLaunchKernelGGL((k_preprocess_views_c<11, 2, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->general) hipLaunchKernelGGL((k_preprocess_views_c<11, 2, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
@@ -7750,6 +7881,146 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	                   fc->out_scores, status);
 	if ((rc = fr_check_launch("k_reduce_scores"))) return rc;
 	return FR_OK;                                                    // (tile_join: the caller's stream now waits for the tile stream)
+}
+
+// ---- camera-pose Fisher information (k_fisher_pose_tile) ----
+// The workspace of fr_fisher_views with 4 columns (the pose records are the 112-byte general form) and behind it the per-(view, tile)
+// partials of the 21 upper-triangle entries, f64 [V][T][21].
+static size_t fr_pose_part_offset(int64_t P, int64_t W, int64_t H, int64_t V, int64_t max_rendered)
+{
+	return fr_fisher_layout(P, W, H, V, max_rendered, 4).total;
+}
+static size_t fr_pose_total(int64_t P, int64_t W, int64_t H, int64_t V, int64_t max_rendered)
+{
+	const int64_t T = ((W + 15) / 16) * ((H + 15) / 16);
+	return fr_align(fr_pose_part_offset(P, W, H, V, max_rendered) + (size_t)(V * T) * 21 * 8);
+}
+
+extern "C" size_t fr_fisher_pose_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered)
+{
+	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0) return 0;
+	return fr_pose_total(P, W, H, n_views, max_rendered);
+}
+
+extern "C" int fr_fisher_pose_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, size_t o[9])
+{
+	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0 || !o)
+		return fr_fail(FR_EINVAL, "fr_fisher_pose_workspace_layout: bad argument");
+	const FrFisherLayout L = fr_fisher_layout(P, W, H, n_views, max_rendered, 4);
+	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+	o[8] = fr_pose_part_offset(P, W, H, n_views, max_rendered);
+	return FR_OK;
+}
+
+extern "C" int fr_fisher_pose_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* fc, float* out_pose_H,
+                                    void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream)
+{
+	// every argument check comes before any device work
+	int rc = fr_validate(cfg, g, "fr_fisher_pose_views");
+	if (rc) return rc;
+	if (!fc || fc->n_views <= 0 || !fc->w2c || !status || !out_pose_H) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: bad fisher cfg or null output");
+	if (fc->H_inv || fc->out_scores) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: H_inv / out_scores are for fr_fisher_views");
+	if (fc->out_H) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: out_H is for fr_fisher_views");
+	if (fc->dL_dpix_image) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: no per-pixel upstream-gradient images (constant dL_dpix only)");
+	if (fc->reuse_static) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: reuse_static is not supported");
+	if (!g->colors_precomp) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: needs colors_precomp");
+	if (!(g->scales && g->rotations)) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: needs scales and rotations");
+	if (fc->tile_capacity < 0) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: negative tile_capacity");
+	const int P = cfg->P, W = cfg->image_width, H = cfg->image_height, V = fc->n_views;
+	const long long Tt = (long long)((W + 15) / 16) * ((H + 15) / 16);
+	if (Tt > FR_MAX_LDS_TILES) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: images beyond 4096 tiles are not supported");
+	if (fc->tile_capacity > 0)
+	{
+		const long long need = (long long)V * Tt * (long long)fc->tile_capacity;
+		if (need > max_rendered || need >= (1ll << 32)) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: n_views * tiles * tile_capacity exceeds max_rendered (or 2^32)");
+	}
+	hipStream_t s = (hipStream_t)stream;
+	if (P == 0)
+	{
+		(void)hipMemsetAsync(out_pose_H, 0, (size_t)V * 36 * 4, s);
+		if (fc->out_vis_count) (void)hipMemsetAsync(fc->out_vis_count, 0, (size_t)V * 4, s);
+		if (fc->out_num_rendered) (void)hipMemsetAsync(fc->out_num_rendered, 0, (size_t)V * 4, s);
+		(void)hipMemsetAsync(status, 0, 16, s);
+		return fr_check_launch("fr_fisher_pose_views (no Gaussians)");
+	}
+	const FrFisherLayout L = fr_fisher_layout(P, W, H, V, max_rendered, 4);
+	if (!workspace || workspace_bytes < fr_pose_total(P, W, H, V, max_rendered))
+		return fr_fail(FR_ENOSPACE, "fr_fisher_pose_views: workspace smaller than fr_fisher_pose_workspace_bytes()");
+	char* ws = (char*)workspace;
+	FrParams p;
+	fr_fill_params(p, cfg, g, V);
+	p.prefiltered = 0;
+	p.w2c = fc->w2c;
+	if (fc->poses_are_c2w)
+	{
+		float* inv = (float*)(ws + L.w2c_inv);
+		hipLaunchKernelGGL(k_invert_poses, dim3((V + 63) / 64), dim3(64), 0, s, V, fc->w2c, inv);
+		if ((rc = fr_check_launch("k_invert_poses"))) return rc;
+		p.w2c = inv;
+	}
+	p.radii = (int*)(ws + L.radii);
+	p.vis_list = (FrVisEntry*)(ws + L.radii);
+	p.vis_n = (uint32_t*)(ws + L.vis_n);
+	p.splat = (FrSplat*)(ws + L.splat);
+	p.cov3D_out = (float*)(ws + L.cov3D);
+	p.tile_cnt = (uint32_t*)(ws + L.tile_cnt);
+	p.tile_off = (uint32_t*)(ws + L.tile_off);
+	p.tile_fill = (uint32_t*)(ws + L.tile_fill);
+	p.status = (int*)(ws + L.status);
+	p.big_list = (uint32_t*)(ws + L.big_list);
+	const bool deal = (V & 7) == 0 && V <= 1024;
+	p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
+	p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;
+	p.blk_base = (uint32_t*)(ws + L.blk_base);
+	p.keys = (uint64_t*)(ws + L.keys);
+	p.key_capacity = max_rendered;
+	if (fc->tile_capacity > 0)
+	{
+		// fixed key segments where the compact-record front end can address them (as fr_fisher_views decides it)
+		const long long nblk_c = (P + FR_THREADS * fr_pick_G_views(P) - 1) / (FR_THREADS * fr_pick_G_views(P));
+		const bool slots_fit = nblk_c * FR_THREADS * fr_pick_G_views(P) < (1ll << 28);
+		if (p.gx <= 255u && p.gy <= 63u && slots_fit) p.tile_cap = (uint32_t)fc->tile_capacity;
+	}
+	(void)fr_plan_views_c(p.T, fr_pick_VC(p.T), p.tile_cap);
+	p.vis_count = fc->out_vis_count;
+	p.num_rendered = fc->out_num_rendered;
+	p.order = fc->order;
+	constexpr int rstride = FrRecStride<4, 3>::value;
+	FrScorerPlan plan;
+	plan.columns = 4;
+	plan.form_a = false;
+	plan.pose = true;
+	plan.ra.H_inv = nullptr; plan.ra.hinv_stride = 0;
+	plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
+	plan.ra.comp = (float4*)(ws + L.recq);
+	plan.ra.stride = rstride;
+	plan.ra.slot_idx = nullptr;
+	plan.ra.mt = (const float4*)(ws + L.mt);
+	plan.ra.grp = (const float4*)(ws + L.grp);
+	plan.ra.early = 1;
+	FrFisherArgs f;
+	memset(&f, 0, sizeof(f));
+	f.dL = fc->dL_dpix;
+	f.recA = plan.ra.comp; f.ab_view = (long long)L.PV * rstride; f.ab_stride = rstride;
+	f.recQ = plan.ra.comp + 2; f.q_view = (long long)L.PV * rstride; f.q_stride = rstride;
+	if ((rc = fr_bin_pipeline(p, g, s, &plan))) return rc;
+	f.key_shift = p.tile_cap ? 4 : 0;                   // (fixed segments: keys = depth | slot << 4 | strips)
+	double* part = (double*)(ws + fr_pose_part_offset(P, W, H, V, max_rendered));
+	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	if (g_prof_on)
+	{
+		(void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
+		(void)hipEventRecord(ev0, s);
+	}
+	hipLaunchKernelGGL(k_fisher_pose_tile, dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, part);
+	if (g_prof_on)
+	{
+		(void)hipEventRecord(ev1, s);
+		g_prof_events.push_back(std::make_pair(ev0, ev1));
+	}
+	if ((rc = fr_check_launch("k_fisher_pose_tile"))) return rc;
+	hipLaunchKernelGGL(k_pose_reduce, dim3(V), dim3(64), 0, s, (const double*)part, p.T, (const int*)p.status, out_pose_H, status);
+	return fr_check_launch("k_pose_reduce");
 }
 
 // =========================================================================================================

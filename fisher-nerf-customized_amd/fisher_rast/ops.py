@@ -472,6 +472,72 @@ class FisherScorer:
         res["scores"] = torch.cat([o["scores"] for o in outs]) if H_inv is not None else None
         return res
 
+    # -- camera-pose Fisher information (fr_fisher_pose_views) ---------------------------------------------
+    def pose_launch(self, w2c, poses_are_c2w=False, out=None):
+        """Enqueue one batch of pose Fisher matrices (no sync).  Returns a dict of device tensors: pose_H [V,6,6] (`out` when given:
+        a contiguous fp32 device tensor of 36 V elements), vis_count [V], num_rendered [V], status [4].  Its own workspace: the packed
+        static records of `launch` stay where they are."""
+        d = self.dev
+        w2c = _prep(w2c.reshape(-1, 4, 4), d)
+        V = int(w2c.shape[0])
+        if out is not None and (out.numel() != 36 * V or out.dtype != torch.float32 or not out.is_contiguous() or out.device != d):
+            raise ValueError("out must be a contiguous fp32 device tensor of V*36 elements")
+        # every element is written (or the status word says overflow, and none is)
+        pose_H = out.view(V, 6, 6) if out is not None else torch.empty((V, 6, 6), dtype=torch.float32, device=d)
+        vis = torch.empty((V,), dtype=torch.int32, device=d)
+        nr = torch.empty((V,), dtype=torch.int32, device=d)
+        status = torch.empty((4,), dtype=torch.int32, device=d)
+        max_rendered = V * self._keys_per_view()
+        nbytes = int(self.lib.fr_fisher_pose_workspace_bytes(self.P, self.W, self.H, V, max_rendered))
+        if nbytes == 0:
+            raise FisherRastError("fr_fisher_pose_workspace_bytes: bad argument")
+        ws = self._ws.get("pose")
+        if ws is None or ws.numel() < nbytes:
+            self._ws["pose"] = None
+            ws = self._ws["pose"] = torch.empty((nbytes,), dtype=torch.uint8, device=d)
+        fc = FisherCfg()
+        fc.n_views, fc.columns, fc.dL_dpix = V, self.columns, self.dL
+        fc.poses_are_c2w = 1 if poses_are_c2w else 0
+        fc.tile_capacity = self.tile_capacity if V * self.tiles * self.tile_capacity < (1 << 32) else 0
+        fc.w2c = ctypes.c_void_p(w2c.data_ptr())
+        fc.out_vis_count = vis.data_ptr()
+        fc.out_num_rendered = nr.data_ptr()
+        fc.order = self.order.data_ptr() if self.order is not None else None
+        with torch.cuda.device(d):
+            _lib.check(self.lib.fr_fisher_pose_views(ctypes.byref(self.cfg), ctypes.byref(self.g), ctypes.byref(fc),
+                                                     ctypes.c_void_p(pose_H.data_ptr()), ws.data_ptr(), ws.numel(), max_rendered,
+                                                     status.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)),
+                       "fr_fisher_pose_views")
+        return dict(pose_H=pose_H, vis_count=vis, num_rendered=nr, status=status, n_views=V, _keep=(w2c,))
+
+    def pose_fisher(self, w2c, poses_are_c2w=False):
+        """Camera-pose Fisher information of every view: [V,6,6] float32 on the device, xi = (translation, rotation), left
+        perturbation of the camera-frame means (include/fisher_rast.h, fr_fisher_pose_views).  Views beyond
+        `max_views_per_launch()` go in several calls; an overflow of the key buffer is redone with a larger one, as in `run`.
+        Synchronises once per call (the status word).  The same for 4- and 11-column scorers."""
+        w2c = w2c.reshape(-1, 4, 4)
+        V = int(w2c.shape[0])
+        chunk = self.max_views_per_launch()
+        outs = []
+        v0 = 0
+        while v0 < V:
+            v1 = min(V, v0 + chunk)
+            while True:
+                r = self.pose_launch(w2c[v0:v1], poses_are_c2w)
+                st = r["status"].cpu()
+                if int(st[1]) == 0:
+                    break
+                # overflow: nothing was written -- grow the key buffer (or the fixed segments) and redo this chunk
+                if int(st[3]):
+                    want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
+                    self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0
+                self.per_view_capacity = max(self.per_view_capacity, int(int(st[0]) * 1.25 / (v1 - v0)) + 4096)
+                chunk = min(chunk, self.max_views_per_launch())
+                v1 = min(v1, v0 + chunk)
+            outs.append(r["pose_H"])
+            v0 = v1
+        return torch.cat(outs) if outs else torch.zeros((0, 6, 6), dtype=torch.float32, device=self.dev)
+
 
 def spatial_order_of(means3D: torch.Tensor) -> torch.Tensor:
     """fr_spatial_order: int32 [P], entry k = index of the k-th Gaussian along the Z-curve of the means (stable for equal codes)."""

@@ -258,7 +258,29 @@ class FisherOps:
         return target_cls
 
 
-class GaussianSLAM(FisherOps):
+class PoseFisherOps:
+    """Mixin with the camera-pose Fisher information of candidate views (fr_fisher_pose_views, include/fisher_rast.h): the 6 x 6
+    matrix the reference's path objective takes the log-determinant of (tester_gaussians_navigation.py:1689-1701), which its
+    compute_Hessian(return_pose=True) returns as eye(6).  That method keeps doing so; these are new names.  xi = (translation,
+    rotation), left perturbation of the camera-frame means.  Needs FisherOps' `_scorer` / `_as_w2c` (install FisherOps first)."""
+
+    def compute_pose_Hessian(self, rel_w2c):
+        """[6, 6] pose Fisher information of one world->camera pose."""
+        return self.pose_Hessians(self._as_w2c(rel_w2c).reshape(1, 4, 4))[0]
+
+    def pose_Hessians(self, w2cs):
+        """[V, 6, 6] for V world->camera poses, batched through the scorer of the current map."""
+        return self._scorer().pose_fisher(self._as_w2c(w2cs).reshape(-1, 4, 4))
+
+    @classmethod
+    def install(cls, target_cls):
+        """Graft the two methods onto the reference's class (after FisherOps.install / ObjectFisherOps.install)."""
+        for name in ("compute_pose_Hessian", "pose_Hessians"):
+            setattr(target_cls, name, getattr(cls, name))
+        return target_cls
+
+
+class GaussianSLAM(FisherOps, PoseFisherOps):
     """Standalone carrier of the operator surface: a Gaussian map (param dict), a camera and keyframes."""
 
     def __init__(self, config=None, params=None, intrinsics=None, width=None, height=None, device="cuda"):

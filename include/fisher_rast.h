@@ -26,6 +26,8 @@
  *                           models/SLAM/gaussian.py:1338-1375, 1503-1570 and
  *                           models/SLAM/gaussian_object.py:1541-1551, 1591-1617, 1940-2045
  *                           (V x [forward + backward(power=2) + cat + sum]) as one batched call
+ *   fr_fisher_pose_views <- the pose_H of compute_Hessian(return_pose=True) that the path objective uses
+ *                           (tester_gaussians_navigation.py:1689-1701; a placeholder eye(6) in the reference)
  *   fr_densify_stats / fr_densify_masks / fr_prune_mask <- the statistics of get_loss / densify / prune_gaussians
  *                           models/SLAM/gaussian.py:289-291, models/SLAM/utils/slam_external.py:196-200, 345-465
  *   fr_knn_dist2         <- simple_knn._C.distCUDA2 (thirdparty/simple-knn, un-vendored submodule)
@@ -254,6 +256,27 @@ int fr_fisher_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views,
 int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* cfg_f,
                     void* workspace, size_t workspace_bytes, int64_t max_rendered,
                     int32_t* status, fr_stream_t stream);
+
+/* ---- camera-pose Fisher information of candidate views ---------------------------------------------
+ * The reference's path objective adds path_pose_weight * log det(pose_H) per step (tester_gaussians_navigation.py:1689-1701,
+ * 1925-1946); its compute_Hessian(return_pose=True) returns eye(6) there, a placeholder.  This is the quantity that name promises:
+ * each view is rendered as fr_fisher_views renders it (camera-frame means m_i = rel_w2c x_i, viewmatrix = I; rotations, scales,
+ * opacities and colours do not move with the pose), the pose is perturbed on the left, m_i(xi) = exp(xi^) m_i with xi = (rho, phi),
+ * translation first, so dm_i/dxi = [I | -[m_i]x], and with g_{p,i} pixel p's share of dL/dm_i for the constant upstream gradient
+ * dL_dpix on every channel (the mean2D and the cov2D-through-J(t) paths of the reference's backward, limx / limy clamp included)
+ *     j_p = sum_i [ g_{p,i} ; m_i x g_{p,i} ]        pose_H = sum_p j_p j_p^T     (6 x 6, symmetric positive semi-definite)
+ * Contributor sets and cut-offs are the forward's.  One front-to-back walk per (view, tile) writes plain per-tile partials, which are
+ * summed in a fixed order in double: the same call gives bit-identical results, and a view's result does not depend on the batch.
+ * fr_fisher_cfg fields used: n_views, dL_dpix, w2c, poses_are_c2w, out_vis_count, out_num_rendered, tile_capacity, order (columns is
+ * ignored: the pose Fisher does not depend on it).  H_inv / out_scores, out_H, dL_dpix_image and reuse_static are rejected (FR_EINVAL),
+ * and so are images beyond 4096 tiles; every check is made before any device work.
+ * out_pose_H: device float [n_views, 6, 6], both triangles written.  status as fr_fisher_views; on overflow nothing is written. */
+size_t fr_fisher_pose_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered);
+/* offsets [0..7] as fr_fisher_workspace_layout(.., columns = 4) (the records are the 112-byte pose form: the 4-column general out_H
+ * record with the camera-frame mean in the place of the colour), [8] the per-tile partials f64 [n_views, tiles, 21] */
+int fr_fisher_pose_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, size_t offsets[9]);
+int fr_fisher_pose_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* cfg_f, float* out_pose_H,
+                         void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream);
 
 /* ---- densification / pruning statistics of the training step ---------------------------
  * One pass over the Gaussians each, in place of the torch-op chains of models/SLAM/gaussian.py:289-291 and
