@@ -57,7 +57,8 @@ def replicate_map(params: Optional[dict], H_inv: Optional[torch.Tensor] = None, 
     `slam.params` or the activated render variables) and optionally H_inv; every other rank may pass None (or stale tensors of
     any content).  One small object broadcast carries names / shapes / dtypes, then ONE `dist.broadcast` per tensor
     (28 MB + 8 MB at 500k Gaussians).  Returns `(params, H_inv)` on every rank: on `src` the caller's own tensors, elsewhere
-    tensors on `device` (reused when the caller passed tensors of the right shape / dtype / device)."""
+    tensors on `device` (reused when the caller passed tensors of the right shape / dtype / device; their version counters are
+    bumped, as an in-place tensor op would)."""
     rank, world = _world(group)
     if not _collective(world):
         return params, H_inv
@@ -77,15 +78,23 @@ def replicate_map(params: Optional[dict], H_inv: Optional[torch.Tensor] = None, 
             return old.detach()
         return torch.empty(shape, dtype=dtype, device=device)
 
+    def _refilled(t):
+        # a collective writes behind autograd's version counter: bump it, so that whatever follows these tensors by version
+        # (FisherScorer's static records, GaussianSLAM's scorer cache) sees the refill
+        if rank != src:
+            torch.autograd.graph.increment_version(t)
+
     out = {} if rank != src else dict(params)
     for name, shape, dtype in meta[0]:
         t = _slot(params.get(name) if params else None, shape, dtype)
         _broadcast(t, src, group)
+        _refilled(t)
         if rank != src:
             out[name] = t
     if meta[1] is not None:
         h = _slot(H_inv, *meta[1])
         _broadcast(h, src, group)
+        _refilled(h)
         H_inv = H_inv if rank == src else h
     return out, H_inv
 

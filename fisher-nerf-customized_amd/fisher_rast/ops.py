@@ -326,7 +326,30 @@ class FisherScorer:
         # tile kernel gains 3.7 % and the projection kernel 2.8 %, the gathering k_pack_static loses as much (51 against 22 us) -- and two
         # DISTINCT splats of bit-equal depth in one tile (about one pair per view) then composite in Z-curve order, not in the reference's
         # index order (scores move by ~1e-5; exact duplicates keep their order).
-        self.order = spatial_order_of(self.means3D) if (spatial_order and self.P > 0) else None
+        # The order follows the means: `launch` / `pose_launch` take it again when the means' (address, version) has moved on.
+        self.spatial_order = bool(spatial_order) and self.P > 0
+        self.order, self._order_src = None, None
+        self._sync_order()
+
+    def _map_key(self):
+        """(address, version) of every tensor the static records are built from: an in-place write through a tensor op bumps the
+        version; a write that bypasses autograd's version counter (`.data`, collectives, DLPack, raw pointers) must be followed by
+        `map_changed()`."""
+        return tuple((t.data_ptr(), t._version) for t in (self.means3D, self.colors, self.rotations, self.opacities, self.scales, self.order)
+                     if t is not None)
+
+    def _sync_order(self, force=False):
+        if not self.spatial_order:
+            return
+        src = (self.means3D.data_ptr(), self.means3D._version)
+        if force or self.order is None or src != self._order_src:
+            self.order, self._order_src = spatial_order_of(self.means3D), src
+
+    def map_changed(self):
+        """Tell the scorer that the tensors it holds were written behind autograd's version counter (`.data`, a collective, DLPack,
+        a raw pointer): the next call packs its static records again, and the spatial order is taken again."""
+        self._static_key, self._static_hinv = None, None
+        self._sync_order(force=True)
 
     # -- helpers -------------------------------------------------------------------------------------
     def max_views_per_launch(self):
@@ -390,6 +413,7 @@ class FisherScorer:
         # against 2.08 ms per step -- and a group that had not overflowed would have been added to out_H twice by the redo.)
         max_rendered = V * self._keys_per_view()
         ws = self._workspace(V, max_rendered)
+        self._sync_order()
         fc = FisherCfg()
         fc.n_views, fc.columns, fc.dL_dpix = V, C, self.dL
         fc.poses_are_c2w = 1 if poses_are_c2w else 0
@@ -409,11 +433,11 @@ class FisherScorer:
         fc.out_num_rendered = nr.data_ptr()
         fc.order = self.order.data_ptr() if self.order is not None else None
         # the per-Gaussian static records (means, cov3D, colours, shared H_inv rows) are packed into the workspace by every call; a call
-        # that finds there what it would write -- same workspace and layout, same shared H_inv tensor in the same version (this scorer's
-        # Gaussians never change) -- skips that kernel (fr_fisher_cfg.reuse_static)
+        # that finds there what it would write -- same workspace and layout, same shared H_inv tensor in the same version, the map's
+        # tensors (and the order) at the same addresses in the same versions -- skips that kernel (fr_fisher_cfg.reuse_static)
         # (the H_inv TENSOR is held on to: a fresh tensor of a later call can then not land on its address and pass for it)
         shared = None if (H_inv is None or H_inv_per_view) else H_inv
-        skey = (ws.data_ptr(), ws.numel(), V, max_rendered, fc.tile_capacity, None if shared is None else shared._version)
+        skey = (ws.data_ptr(), ws.numel(), V, max_rendered, fc.tile_capacity, None if shared is None else shared._version, self._map_key())
         if H_inv is not None and out_H is not None:
             # scores AND diagonals in one call run the two-pass fall-back kernel, which packs its own static records and leaves the
             # front end's {mean, trace} array unwritten: nothing of this call may be reused by the next one
@@ -495,6 +519,7 @@ class FisherScorer:
         if ws is None or ws.numel() < nbytes:
             self._ws["pose"] = None
             ws = self._ws["pose"] = torch.empty((nbytes,), dtype=torch.uint8, device=d)
+        self._sync_order()
         fc = FisherCfg()
         fc.n_views, fc.columns, fc.dL_dpix = V, self.columns, self.dL
         fc.poses_are_c2w = 1 if poses_are_c2w else 0

@@ -115,6 +115,9 @@ def _replicate_worker(rank, world, port, out_dir):
             params = {k: torch.zeros_like(v) for k, v in full.items()}   # a stale replica: zeros of the right shape are reused in place
             H_inv = torch.zeros((P, 4))
         stale_ptr = None if params is None or rank == 0 else params["means3D"].data_ptr()
+        # the tensors a rank hands in (rank 2 gets them refilled in place, rank 0 sends them): their versions before the broadcast
+        held = [] if params is None else list(params.items()) + [("H_inv", H_inv)]
+        v0 = {k: t._version for k, t in held}
         # the replicas differ before the broadcast: the fingerprint check must say so on every rank
         mine = [v for v in (params or {"x": torch.zeros(3)}).values()]
         differs = False
@@ -126,7 +129,14 @@ def _replicate_worker(rank, world, port, out_dir):
         D.assert_replicated([got[k] for k in sorted(got)] + [H_got])
         ok = all(torch.equal(got[k], full[k]) for k in full) and torch.equal(H_got, H_full) and set(got) == set(full)
         reused = stale_ptr is None or got["means3D"].data_ptr() == stale_ptr
-        torch.save(dict(ok=ok, differs=differs, reused=reused), os.path.join(out_dir, f"rep{rank}.pt"))
+        # a broadcast writes behind autograd's version counter: replicate_map bumps the version of every tensor it refilled in place
+        # (so that a scorer or a scorer cache that follows versions sees the new map) and leaves the source's tensors alone
+        if rank == 0:
+            versions = all(t._version == v0[k] for k, t in held)
+        else:
+            versions = all(t._version > v0[k] for k, t in held)
+        torch.save(dict(ok=ok, differs=differs, reused=reused, versions=versions, checked=len(held)),
+                   os.path.join(out_dir, f"rep{rank}.pt"))
     finally:
         dist.destroy_process_group()
 
@@ -139,6 +149,7 @@ def test_replicate_map_world3(tmp_path):
     for r in range(3):
         d = torch.load(tmp_path / f"rep{r}.pt")
         assert d["ok"] and d["differs"] and d["reused"], (r, d)
+        assert d["versions"] and d["checked"] == (0 if r == 1 else 6), (r, d)
 
 
 def test_replicate_map_is_identity_without_a_process_group():

@@ -214,14 +214,26 @@ def test_pose_eval_keeps_h_train_until_map_or_keyframes_change(config1, gpu):
     slam.keyframe_list[0]['est_w2c'][0, 3] += 0.25                                # a keyframe pose refined in place
     s4, _ = slam.pose_eval(poses)
     assert slam._h_inv_cache[2] is not held and not torch.equal(s4, s3)
+
+    def fresh_scores():
+        # a SLAM object that has seen nothing before: clones of the current map and keyframe poses
+        f = mgs.GaussianSLAM(params={k: v.clone() for k, v in slam.params.items()}, intrinsics=c["K"], width=c["W"], height=c["H"], device=gpu)
+        for kf in slam.keyframe_list:
+            f.add_keyframe(kf['est_w2c'].clone())
+        return f.pose_eval(poses)[0]
+    assert torch.allclose(s4, fresh_scores(), rtol=1e-5)
     held = slam._h_inv_cache[2]
     slam.params["logit_opacities"].mul_(0.9)                                      # an optimiser step on the map
     s5, _ = slam.pose_eval(poses)
     assert slam._h_inv_cache[2] is not held and not torch.equal(s5, s4)
+    assert torch.allclose(s5, fresh_scores(), rtol=1e-5)
     # and against the two-step route of the reference's structure
     Ht = slam.compute_H_train()
     want = slam._scorer().run(torch.stack(poses), H_inv=torch.reciprocal(Ht + slam.H_TRAIN_REG), poses_are_c2w=True)["scores"].cpu()
     assert torch.allclose(s5, want, rtol=1e-5)
+    slam.params["means3D"][::2] += torch.tensor([0.05, -0.02, 0.04], device=gpu)  # ... and on the means, which the static records hold
+    s6, _ = slam.pose_eval(poses)
+    assert not torch.allclose(s6, s5, rtol=1e-3) and torch.allclose(s6, fresh_scores(), rtol=1e-5)
 
 
 def test_per_view_weights_path_eval(config1, gpu):
