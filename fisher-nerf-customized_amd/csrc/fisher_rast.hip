@@ -639,7 +639,7 @@ struct FrRecordArgs {
 };
 // floats per Gaussian of the packed static record (k_pack_static): {mean 3, cov3D 6, rgb 3, (scale 3, rot 4), H_inv C}
 template <int C> struct FrPackSize { static constexpr int value = (C >= 11) ? 32 : 16; };
-template <int C, bool REWRITE, bool FORM_A = false, bool FIVE = false>
+template <int C, bool REWRITE, bool FORM_A = false, bool FIVE = false, bool IDV = false>
 __device__ __forceinline__ void fr_fisher_record_one(const FrParams& p, const float* __restrict__ H_inv, long long hinv_stride,
                                                      const float* __restrict__ packed, float4* __restrict__ recq, int v, uint32_t id,
                                                      const float* vm, const float* pm, const float* wm, bool has_w2c,
@@ -932,10 +932,16 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 // underneath the projection arithmetic of the other workgroups on the CU -- k_scatter_vis (latency-bound, 0.15 ms of the
 // 64-view step on its own) and the blk_base array disappear, k_scan_tiles only builds the lists of long tiles.  The order of the
 // keys inside a segment is arbitrary either way; the sort makes it the reference's.
-template <int C, int AF, bool DK>
+// IDV (fr_fisher_cfg.view_is_identity; the 4-column score form with fixed key segments only): the camera's view matrix is the
+// identity -- the scorer's camera has it (gaussian.py:343), every candidate pose arrives through w2c.  Phase A's near-plane
+// transform, phase B's view products (fr_preprocess_one<true>) and phase C's (fr_mean_rows_unit<true, true>) drop out, and with
+// them the 16 registers of the matrix; phases A and B stay bit-identical to the general instantiation.  The hint is checked: a
+// workgroup that finds another matrix in p.view raises the overflow flag (nothing is scored) and status[3] bit 1 (FisherScorer throws).
+template <int C, int AF, bool DK, bool IDV = false>
 __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, FrRecordArgs ra)
 {
 	static_assert((C == 4 || C == 11) && AF >= 0 && AF <= 3 && !((AF == 1 || AF == 3) && C != 4), "records modes: score form, A-form (4 columns), general out_H form, pose form (4 columns)");
+	static_assert(!IDV || (C == 4 && AF == 0 && DK), "the identity-view front end is the 4-column score form's with fixed key segments");
 	constexpr int RS = FrRecStride<C, AF, DK>::value; // float4 per compact record
 	extern __shared__ uint32_t fr_dyn_lds[];     // hist[VC][T] | pairs[FR_THREADS * (VC + 1)] | wm[VC][12] | park[13][FR_THREADS] | DK: cursor[VC][T]
 	const int VC = p.VC;
@@ -965,7 +971,14 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 	if (tid < FR_VC_MAX) { s_n[tid] = 0; s_ref[tid] = 0; }
 	float vm[16], pm[16];
 #pragma unroll
-	for (int k = 0; k < 16; k++) { vm[k] = p.view[k]; pm[k] = p.proj[k]; }
+	for (int k = 0; k < 16; k++) { vm[k] = IDV ? (k % 5 == 0 ? 1.f : 0.f) : p.view[k]; pm[k] = p.proj[k]; }
+	if constexpr (IDV)
+	{
+		bool id = true;
+#pragma unroll
+		for (int k = 0; k < 16; k++) id = id && p.view[k] == vm[k];
+		if (!id && tid == 0) { atomicOr(&p.status[1], 1); atomicOr(&p.status[3], 2); }
+	}
 	const size_t PV = (size_t)nblk * cap;
 	const unsigned long long lt = (1ull << lane) - 1ull;
 	__syncthreads();
@@ -1066,7 +1079,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 			{
 				if ((skipv >> vv) & 1u) { if (lane == 0) s_ca[vv * 4 + wave] = 0u; continue; }       // (uniform: the whole round is out of this view)
 				const fr_f3 po = has_w2c ? fr_world_to_cam(pw, s_wm + 12 * vv) : pw;
-				const fr_f3 p_view = fr_xform4x3(po, vm);        // (the near-plane decision: the reference's arithmetic, unfused)
+				const fr_f3 p_view = IDV ? po : fr_xform4x3(po, vm);    // (the near-plane decision: the reference's arithmetic, unfused)
 				bool keep = live && !(p_view.z <= 0.001f);
 				if (early)
 				{
@@ -1144,7 +1157,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 					for (int k = 0; k < 12; k++) wm[k] = s_wm[12 * vv + k];
 				}
 				const fr_f3 po = has_w2c ? fr_world_to_cam(pw, wm) : pw;
-				sp = fr_preprocess_one(po, c3, vm, pm, p.W, p.H, p.tanfovx, p.tanfovy, p.focal_x, p.focal_y, p.gx, p.gy);
+				sp = fr_preprocess_one<IDV>(po, c3, vm, pm, p.W, p.H, p.tanfovx, p.tanfovy, p.focal_x, p.focal_y, p.gx, p.gy);
 				if (sp.radius > 0) { o = o_pre; ext = fr_alpha_extent(sp.conx, sp.cony, sp.conz, o); }
 			}
 			const bool vis = sp.radius > 0;
@@ -1257,7 +1270,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 				float4* rec_out = ra.comp + ((size_t)v * PV + slot) * RS;
 				FR_ABL(if (p.ablate == 37) rec_out = ra.comp + (size_t)tid * RS;)     // 37: the records' arithmetic without their HBM traffic
 				if constexpr (AF >= 2) fr_fisher_record_general<C, (AF == 3)>(p, ra.packed, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
-				else fr_fisher_record_one<C, false, (AF == 1), (AF == 0 && DK)>(p, ra.H_inv, ra.hinv_stride, ra.packed, ra.recq, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
+				else fr_fisher_record_one<C, false, (AF == 1), (AF == 0 && DK), IDV>(p, ra.H_inv, ra.hinv_stride, ra.packed, ra.recq, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
 				if constexpr (DK)
 				{
 					// 8-byte list entry {depth, x0 | y0 << 8 | width << 16 | height << 24}, y0 / height in strip rows (tile grids up to
@@ -3141,7 +3154,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 // ---------------------------------------------------------------------------------------------------------
 // REWRITE: the (view, Gaussian) record still holds the rasteriser's FrSplat and is turned into {recA, recB} here (stand-alone
 // k_fisher_records); otherwise the front end has already written {recA, recB} and only recQ is produced.
-template <int C, bool REWRITE, bool FORM_A, bool FIVE>
+template <int C, bool REWRITE, bool FORM_A, bool FIVE, bool IDV>
 __device__ __forceinline__ void fr_fisher_record_one(const FrParams& p, const float* __restrict__ H_inv, long long hinv_stride,
                                                      const float* __restrict__ packed, float4* __restrict__ recq, int v, uint32_t id,
                                                      const float* vm, const float* pm, const float* wm, bool has_w2c,
@@ -3167,7 +3180,10 @@ __device__ __forceinline__ void fr_fisher_record_one(const FrParams& p, const fl
 	// square of its conic's condition number).
 	float Rg[3][5];
 	float Bg[6][3];
-	fr_mean_rows_g<true>(po, &gsv[3], vm, pm, p.focal_x, p.focal_y, p.tanfovx, p.tanfovy, p.W, p.H, Rg, SR ? Bg : nullptr, nullptr, nullptr);
+	static_assert(!IDV || (FIVE && !SR), "the identity-view record chain is the 4-column score form's");
+	// the score form with fixed key segments (the benchmark's): the closed-form rows of the three unit inputs (IDV: view = identity)
+	if constexpr (FIVE && !SR) fr_mean_rows_unit<true, IDV>(po, &gsv[3], vm, pm, p.focal_x, p.focal_y, p.tanfovx, p.tanfovy, p.W, p.H, Rg);
+	else fr_mean_rows_g<true>(po, &gsv[3], vm, pm, p.focal_x, p.focal_y, p.tanfovx, p.tanfovy, p.W, p.H, Rg, SR ? Bg : nullptr, nullptr, nullptr);
 	float Cg[SR ? 7 : 1][3];
 	int go = 12;
 	if constexpr (SR)
@@ -6883,7 +6899,7 @@ struct FrJoinGuard {
 
 // Score-only mode: the front end also produces the scorer's per-(view, Gaussian) records (k_pack_static, then phase C of
 // k_preprocess_views; with the single-view front end, k_fisher_records after k_scatter_keys, beside the sorts, on the second side stream).
-struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; bool pose = false; };   // pose: the records of k_fisher_pose_tile (fr_fisher_pose_views)   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
+struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; bool pose = false; bool view_identity = false; };   // view_identity: fr_fisher_cfg.view_is_identity   // pose: the records of k_fisher_pose_tile (fr_fisher_pose_views)   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
 template <int C> __global__ void k_pack_static(FrParams p, const float* __restrict__ H_inv, float* __restrict__ packed, float4* __restrict__ mt, float4* __restrict__ grp);
 template <int C, bool LIST, bool FORM_A> __global__ void k_fisher_records(FrParams p, FrRecordArgs ra);
 
@@ -6948,6 +6964,7 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 		else if (once && plan->general) hipLaunchKernelGGL((k_preprocess_views_c<11, 2, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->form_a && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 1, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->form_a) hipLaunchKernelGGL((k_preprocess_views_c<4, 1, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->columns == 4 && dk && plan->view_identity) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, true, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && dk) hipLaunchKernelGGL((k_preprocess_views_c<11, 0, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
@@ -7763,6 +7780,7 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	plan.form_a = v3h;
 	plan.general = v3g;
 	plan.columns = fc->columns;
+	plan.view_identity = fc->view_is_identity != 0;
 	plan.ra.H_inv = fc->H_inv; plan.ra.hinv_stride = fc->H_inv_view_stride;
 	plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
 	// compact records with the multi-view front end (the same condition fr_bin_pipeline uses for it); FR_DEBUG_MODE=19: dense (A/B runs)

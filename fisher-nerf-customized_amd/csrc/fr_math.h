@@ -215,14 +215,51 @@ struct fr_cov2d {
 	c.cov00 = (A00 * c.T0[0] + A10 * c.T0[1]) + A20 * c.T0[2];\
 	c.cov01 = (A01 * c.T0[0] + A11 * c.T0[1]) + A21 * c.T0[2];\
 	c.cov11 = (A01 * c.T1[0] + A11 * c.T1[1]) + A21 * c.T1[2];
-template <bool FAST = false>
+// IDV: the view matrix is the identity, by contract (the scorer's camera: gaussian.py:343).  `view` is not read; t = mean, W = I,
+// T0 = (J00, 0, J02), T1 = (0, J11, J12), and the products with those zeros and ones are left out.  With -ffp-contract=off that is
+// exact for finite inputs (x * 1 = x, x + 0 = x): only the sign of a zero can differ, and cov00 / cov11 then get +0.3 anyway.
+#define FR_COV2D_SETUP_ID_BODY \
+	const float limx = 1.3f * tan_fovx;\
+	const float limy = 1.3f * tan_fovy;\
+	c.txtz = fr_divt<FAST>(mean.x, mean.z);\
+	c.tytz = fr_divt<FAST>(mean.y, mean.z);\
+	c.tx = fminf(limx, fmaxf(-limx, c.txtz)) * mean.z;\
+	c.ty = fminf(limy, fmaxf(-limy, c.tytz)) * mean.z;\
+	c.tz = mean.z;\
+	const float J00 = fr_divt<FAST>(focal_x, c.tz);\
+	const float J02 = fr_divt<FAST>(-(focal_x * c.tx), (c.tz * c.tz));\
+	const float J11 = fr_divt<FAST>(focal_y, c.tz);\
+	const float J12 = fr_divt<FAST>(-(focal_y * c.ty), (c.tz * c.tz));\
+	for (int cc = 0; cc < 3; cc++)\
+		for (int r = 0; r < 3; r++)\
+			c.Wc[cc][r] = cc == r ? 1.f : 0.f;\
+	c.T0[0] = J00; c.T0[1] = 0.f; c.T0[2] = J02;\
+	c.T1[0] = 0.f; c.T1[1] = J11; c.T1[2] = J12;\
+	for (int i = 0; i < 6; i++) c.c3[i] = cov3D[i];\
+	const float c0 = cov3D[0], c1 = cov3D[1], c2 = cov3D[2], c3 = cov3D[3], c4 = cov3D[4], c5 = cov3D[5];\
+	const float A00 = J00 * c0 + J02 * c2;\
+	const float A20 = J00 * c2 + J02 * c5;\
+	const float A01 = J11 * c1 + J12 * c2;\
+	const float A11 = J11 * c3 + J12 * c4;\
+	const float A21 = J11 * c4 + J12 * c5;\
+	c.cov00 = A00 * J00 + A20 * J02;\
+	c.cov01 = A01 * J00 + A21 * J02;\
+	c.cov11 = A11 * J11 + A21 * J12;
+template <bool FAST = false, bool IDV = false>
 FR_HD void fr_cov2d_setup(fr_f3 mean, float focal_x, float focal_y, float tan_fovx, float tan_fovy,
                           const float* cov3D, const float* view, fr_cov2d& c)
 {
-	if constexpr (FAST) { FR_CONTRACT FR_COV2D_SETUP_BODY }
+	if constexpr (IDV)
+	{
+		(void)view;
+		if constexpr (FAST) { FR_CONTRACT FR_COV2D_SETUP_ID_BODY }
+		else { FR_COV2D_SETUP_ID_BODY }
+	}
+	else if constexpr (FAST) { FR_CONTRACT FR_COV2D_SETUP_BODY }
 	else { FR_COV2D_SETUP_BODY }
 }
 #undef FR_COV2D_SETUP_BODY
+#undef FR_COV2D_SETUP_ID_BODY
 
 // ---- forward.cu:181-255: everything preprocessCUDA derives for one Gaussian -------------------------
 struct fr_splat {
@@ -234,7 +271,9 @@ struct fr_splat {
 	uint32_t tiles;
 };
 
-// p_orig is the point handed to the rasteriser (already in the candidate frame for the Fisher path).
+// p_orig is the point handed to the rasteriser (already in the candidate frame for the Fisher path).  IDV: `view` is the identity
+// (fr_cov2d_setup); every output is the general path's bit for bit.
+template <bool IDV = false>
 FR_HD fr_splat fr_preprocess_one(fr_f3 p_orig, const float* cov3D, const float* view, const float* proj,
                                  int W, int H, float tan_fovx, float tan_fovy, float focal_x, float focal_y,
                                  uint32_t gx, uint32_t gy)
@@ -243,7 +282,8 @@ FR_HD fr_splat fr_preprocess_one(fr_f3 p_orig, const float* cov3D, const float* 
 	s.radius = 0; s.tiles = 0; s.depth = 0.f; s.px = s.py = 0.f; s.conx = s.cony = s.conz = 0.f;
 	s.rect.x0 = s.rect.y0 = s.rect.x1 = s.rect.y1 = 0;
 
-	fr_f3 p_view = fr_xform4x3(p_orig, view);
+	fr_f3 p_view = p_orig;
+	if constexpr (!IDV) p_view = fr_xform4x3(p_orig, view);
 	if (p_view.z <= 0.001f)
 		return s;
 	fr_f4 p_hom = fr_xform4x4(p_orig, proj);
@@ -251,7 +291,7 @@ FR_HD fr_splat fr_preprocess_one(fr_f3 p_orig, const float* cov3D, const float* 
 	float projx = p_hom.x * p_w, projy = p_hom.y * p_w;
 
 	fr_cov2d c;
-	fr_cov2d_setup(p_orig, focal_x, focal_y, tan_fovx, tan_fovy, cov3D, view, c);
+	fr_cov2d_setup<false, IDV>(p_orig, focal_x, focal_y, tan_fovx, tan_fovy, cov3D, view, c);
 	const float covx = c.cov00 + 0.3f, covy = c.cov01, covz = c.cov11 + 0.3f;
 
 	float det = (covx * covz - covy * covy);
@@ -572,6 +612,102 @@ FR_HD void fr_mean_rows_g(fr_f3 mean, const float* cov3D, const float* view, con
 	else { FR_MEAN_ROWS_G_BODY }
 }
 #undef FR_MEAN_ROWS_G_BODY
+
+// fr_mean_rows_g without its dead work (no Bg, no cov2D / f outputs): the three calls of fr_cov2d_abc_backward take the unit inputs
+// (dL_da, dL_db, dL_dc) = (1,0,0), (0,1,0), (0,0,1), so for each of them exactly the terms that multiply a zero or add a zero are left
+// out (x * 1 = x, x + 0 = x; x * 0 cannot be folded by the compiler without fast-math), and what the three share -- t0v*, t1v*, 1/tz,
+// tz^2, tz^3, h tz^2, the fov clamp masks -- is evaluated once.  Unit input j gives dL_dT0 / dL_dT1:
+//   j = 0: (2 t0v, 0)     j = 1: (t1v, t0v)     j = 2: (0, 2 t1v)
+// and dL_dJ00 / dL_dJ02 vanish for j = 2, dL_dJ11 / dL_dJ12 for j = 0.  IDV: the view matrix is the identity (fr_cov2d_setup), so
+// dL_dJ = dL_dT's matching entries and dmean = (dL_dtx, dL_dty, dL_dtz).  FAST = false gives fr_mean_rows_g<false>'s rows bit for bit
+// on finite inputs, up to the sign of a zero (tests/test_mean_rows_unit_cpu.py); FAST = true contracts like fr_mean_rows_g<true>.
+#define FR_MEAN_ROWS_UNIT_BODY \
+	fr_cov2d c; \
+	fr_cov2d_setup<FAST, IDV>(mean, focal_x, focal_y, tan_fovx, tan_fovy, cov3D, view, c); \
+	const float a = c.cov00 + 0.3f, b = c.cov01, cc = c.cov11 + 0.3f; \
+	const float denom = a * cc - b * b; \
+	const float d2 = denom * denom; \
+	const float f = d2 < 3.0e38f ? fr_divt<FAST>(d2, d2 + 0.0000001f) : 0.f; \
+	float Mp[3][2]; \
+	fr_proj_jacobian<FAST>(mean, proj, Mp); \
+	const float hw = (float)(0.5 * W), hh = (float)(0.5 * H); \
+	for (int k = 0; k < 3; k++) { Rg[k][0] = Mp[k][0] * hw; Rg[k][1] = Mp[k][1] * hh; } \
+	const float limx = 1.3f * tan_fovx; \
+	const float limy = 1.3f * tan_fovy; \
+	const bool xm = !(c.txtz < -limx || c.txtz > limx); \
+	const bool ym = !(c.tytz < -limy || c.tytz > limy); \
+	const float* T0 = c.T0; const float* T1 = c.T1; \
+	const float c0 = c.c3[0], c1 = c.c3[1], c2 = c.c3[2], c3 = c.c3[3], c4 = c.c3[4], c5 = c.c3[5]; \
+	float t0v0, t0v1, t0v2, t1v0, t1v1, t1v2; \
+	if constexpr (IDV) \
+	{ \
+		t0v0 = T0[0] * c0 + T0[2] * c2; t0v1 = T0[0] * c1 + T0[2] * c4; t0v2 = T0[0] * c2 + T0[2] * c5; \
+		t1v0 = T1[1] * c1 + T1[2] * c2; t1v1 = T1[1] * c3 + T1[2] * c4; t1v2 = T1[1] * c4 + T1[2] * c5; \
+	} \
+	else \
+	{ \
+		t0v0 = T0[0] * c0 + T0[1] * c1 + T0[2] * c2; t0v1 = T0[0] * c1 + T0[1] * c3 + T0[2] * c4; t0v2 = T0[0] * c2 + T0[1] * c4 + T0[2] * c5; \
+		t1v0 = T1[0] * c0 + T1[1] * c1 + T1[2] * c2; t1v1 = T1[0] * c1 + T1[1] * c3 + T1[2] * c4; t1v2 = T1[0] * c2 + T1[1] * c4 + T1[2] * c5; \
+	} \
+	const float tz = fr_divt<FAST>(1.f, c.tz); \
+	const float tz2 = tz * tz; \
+	const float tz3 = tz2 * tz; \
+	const float ax = -h_x * tz2, ay = h_y * tz2, nay = -h_y * tz2; \
+	const float bx = (2 * h_x * c.tx) * tz3, by = (2 * h_y * c.ty) * tz3; \
+	/* dL_dJ00, dL_dJ02 (from dL_dT0 = u) and dL_dJ11, dL_dJ12 (from dL_dT1 = u) */ \
+	auto dj0 = [&](float u0, float u1, float u2, float& j00, float& j02) { \
+		if constexpr (IDV) { j00 = u0; j02 = u2; } \
+		else { j00 = c.Wc[0][0] * u0 + c.Wc[0][1] * u1 + c.Wc[0][2] * u2; j02 = c.Wc[2][0] * u0 + c.Wc[2][1] * u1 + c.Wc[2][2] * u2; } \
+	}; \
+	auto dj1 = [&](float u0, float u1, float u2, float& j11, float& j12) { \
+		if constexpr (IDV) { j11 = u1; j12 = u2; } \
+		else { j11 = c.Wc[1][0] * u0 + c.Wc[1][1] * u1 + c.Wc[1][2] * u2; j12 = c.Wc[2][0] * u0 + c.Wc[2][1] * u1 + c.Wc[2][2] * u2; } \
+	}; \
+	/* dmean = view[0..2 | 4..6 | 8..10] . (dL_dtx, dL_dty, dL_dtz), with the zero terms of unit input j left out */ \
+	auto put = [&](int j, float dtx, float dty, float dtz, float w) { \
+		float mx, my, mz; \
+		if constexpr (IDV) { mx = dtx; my = dty; mz = dtz; } \
+		else if (j == 0) { mx = view[0] * dtx + view[2] * dtz; my = view[4] * dtx + view[6] * dtz; mz = view[8] * dtx + view[10] * dtz; } \
+		else if (j == 2) { mx = view[1] * dty + view[2] * dtz; my = view[5] * dty + view[6] * dtz; mz = view[9] * dty + view[10] * dtz; } \
+		else { mx = view[0] * dtx + view[1] * dty + view[2] * dtz; my = view[4] * dtx + view[5] * dty + view[6] * dtz; mz = view[8] * dtx + view[9] * dty + view[10] * dtz; } \
+		Rg[0][2 + j] = mx * w; Rg[1][2 + j] = my * w; Rg[2][2 + j] = mz * w; \
+	}; \
+	{	/* j = 0: dL_dT0 = 2 t0v, dL_dT1 = 0 (dL_dty = 0) */ \
+		float j00, j02; \
+		dj0(2 * t0v0, 2 * t0v1, 2 * t0v2, j00, j02); \
+		const float dtx = xm ? ax * j02 : 0.f; \
+		const float dtz = ax * j00 + bx * j02; \
+		if constexpr (IDV) put(0, dtx, 0.f, dtz, 0.5f * f); \
+		else if (xm) put(0, dtx, 0.f, dtz, 0.5f * f); \
+		else { Rg[0][2] = (view[2] * dtz) * (0.5f * f); Rg[1][2] = (view[6] * dtz) * (0.5f * f); Rg[2][2] = (view[10] * dtz) * (0.5f * f); } \
+	} \
+	{	/* j = 1: dL_dT0 = t1v, dL_dT1 = t0v */ \
+		float j00, j02, j11, j12; \
+		dj0(t1v0, t1v1, t1v2, j00, j02); \
+		dj1(t0v0, t0v1, t0v2, j11, j12); \
+		const float dtx = xm ? ax * j02 : 0.f; \
+		const float dty = ym ? nay * j12 : 0.f; \
+		const float dtz = ax * j00 - ay * j11 + bx * j02 + by * j12; \
+		put(1, dtx, dty, dtz, f); \
+	} \
+	{	/* j = 2: dL_dT0 = 0 (dL_dtx = 0), dL_dT1 = 2 t1v */ \
+		float j11, j12; \
+		dj1(2 * t1v0, 2 * t1v1, 2 * t1v2, j11, j12); \
+		const float dty = ym ? nay * j12 : 0.f; \
+		const float dtz = -(ay * j11) + by * j12; \
+		if constexpr (IDV) put(2, 0.f, dty, dtz, 0.5f * f); \
+		else if (ym) put(2, 0.f, dty, dtz, 0.5f * f); \
+		else { Rg[0][4] = (view[2] * dtz) * (0.5f * f); Rg[1][4] = (view[6] * dtz) * (0.5f * f); Rg[2][4] = (view[10] * dtz) * (0.5f * f); } \
+	}
+template <bool FAST = false, bool IDV = false>
+FR_HD void fr_mean_rows_unit(fr_f3 mean, const float* cov3D, const float* view, const float* proj,
+                             float focal_x, float focal_y, float tan_fovx, float tan_fovy, int W, int H, float Rg[3][5])
+{
+	const float h_x = focal_x, h_y = focal_y;
+	if constexpr (FAST) { FR_CONTRACT FR_MEAN_ROWS_UNIT_BODY }
+	else { FR_MEAN_ROWS_UNIT_BODY }
+}
+#undef FR_MEAN_ROWS_UNIT_BODY
 
 // The 12 coefficients of F(u) = sum_c hv[c] (R_c . gamma(u))^2 as a bivariate polynomial in (ux, uy) (terms of degree 2, 3
 // and 4 only): Rg = the three mean rows, Cg = the seven scale / rotation rows over (ux^2, ux uy, uy^2) (C >= 11), hv = the

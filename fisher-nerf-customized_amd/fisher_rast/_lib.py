@@ -64,6 +64,7 @@ class FisherCfg(ctypes.Structure):
         ("poses_are_c2w", ctypes.c_int32),
         ("reuse_static", ctypes.c_int32),
         ("order", ctypes.c_void_p),
+        ("view_is_identity", ctypes.c_int32),
     ]
 
 

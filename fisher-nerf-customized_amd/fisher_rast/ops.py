@@ -300,6 +300,11 @@ class FisherScorer:
         self.view = _prep(raster_settings.viewmatrix, d)
         self.proj = _prep(raster_settings.projmatrix, d)
         self.campos = _prep(raster_settings.campos, d)
+        # The camera of the scorer's callers has the identity as its view matrix (every candidate pose arrives through w2c): the
+        # library then leaves the view products out of the projection front end (fr_fisher_cfg.view_is_identity).  One exact
+        # comparison here, none per call; the library checks the matrix again and a wrong hint raises in `run`.
+        self.view_is_identity = (self.view is not None and self.view.numel() == 16
+                                 and bool(torch.equal(self.view.reshape(4, 4).cpu(), torch.eye(4, dtype=self.view.dtype))))
         self._ws = {}
         self._static_key, self._static_hinv = None, None
         self.per_view_capacity = max(int(0.75 * self.P), 1 << 16)
@@ -432,6 +437,7 @@ class FisherScorer:
         fc.out_vis_count = vis.data_ptr()
         fc.out_num_rendered = nr.data_ptr()
         fc.order = self.order.data_ptr() if self.order is not None else None
+        fc.view_is_identity = 1 if self.view_is_identity else 0
         # the per-Gaussian static records (means, cov3D, colours, shared H_inv rows) are packed into the workspace by every call; a call
         # that finds there what it would write -- same workspace and layout, same shared H_inv tensor in the same version, the map's
         # tensors (and the order) at the same addresses in the same versions -- skips that kernel (fr_fisher_cfg.reuse_static)
@@ -475,9 +481,12 @@ class FisherScorer:
                 st = r["status"].cpu()
                 if int(st[1]) == 0:
                     break
+                if int(st[3]) & 2:
+                    raise FisherRastError("FisherScorer.view_is_identity is set, but the camera's view matrix is not the identity "
+                                          "(nothing was scored)")
                 # tile-instance buffer too small: NOTHING was scored or accumulated (every kernel behind the scan returns on the
                 # overflow flag, include/fisher_rast.h), so out_H is as it was: grow and redo this chunk
-                if int(st[3]):
+                if int(st[3]) & 1:
                     # a tile list longer than its fixed segment (st[2] = the longest): longer segments, or packed lists
                     want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
                     self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0

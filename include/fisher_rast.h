@@ -226,6 +226,10 @@ typedef struct fr_fisher_cfg {
 	                               (Splats of EQUAL depth in one tile are ordered by their place in `order`; fr_spatial_order is stable
 	                               -- equal means keep the caller's order -- so duplicated Gaussians composite as in the reference.)
 	                               Ignored by the fall-back kernels (H_inv and out_H in one launch, images beyond 4096 tiles). */
+	int32_t view_is_identity;   /* 1: the caller vouches that cfg->viewmatrix is the identity (the scorer's camera: gaussian.py:343), and
+	                               the score-only front end with fixed key segments leaves the view products out (bit-identical
+	                               projections).  The kernel checks the matrix: any other raises the overflow flag -- nothing is scored --
+	                               and bit 1 of status[3] (value 2).  0: the general path. */
 } fr_fisher_cfg;
 
 /* Morton (Z-curve, 10 bits per axis over the bounding box of the means) order of P points: order_out[k] = index of the k-th point
