@@ -13,7 +13,7 @@
 //                                           cub::InclusiveSum + the blocking cudaMemcpy of rasterizer_impl.cu:277-282), list of long tiles
 //   k_scatter_keys/_vis  (P/(256 G), V)     packed lists: emit (depth_bits<<32 | gaussian) into the tile's segment
 //                                           (duplicateWithKeys, rasterizer_impl.cu:70-111)
-//   k_sort_tiles, k_sort_part, k_sort_mid/_big   per-tile bitonic network on the 64-bit keys, in registers (DPP / permlane exchanges
+//   k_sort_tiles, k_sort_split, k_sort_parts, k_sort_mid/_big   per-tile bitonic network on the 64-bit keys, in registers (DPP / permlane exchanges
 //                                           between lanes, LDS only where waves' runs join); long lists of fixed segments are first
 //                                           partitioned at sampled pivots into wave-sized parts: replaces the global
 //                                           cub::DeviceRadixSort (rasterizer_impl.cu:304-309).  Keys are unique, so the
@@ -48,7 +48,7 @@
 #define FR_THREADS 256
 #define FR_G_MAX 32                  // upper bound of Gaussians per thread in the per-Gaussian kernels (FrParams::G)
 #define FR_MAX_LDS_TILES 4096        // tile histogram kept in LDS up to 1024x1024 images
-#define FR_PART_MIN_DEFAULT 2048     // fixed key segments: lists beyond this many keys are partitioned (k_sort_part) instead of sorted whole
+#define FR_PART_MIN_DEFAULT 2048     // fixed key segments: lists beyond this many keys are partitioned (k_sort_split) instead of sorted whole
 #define FR_SORT_SMALL_KEYS 2048      // per-tile segments up to this size: 16 KiB of LDS, many workgroups per CU
 #define FR_SORT_MID_KEYS 4096        // listed segments up to this size: 32 KiB of LDS, 256 threads
 #define FR_SORT_BIG_KEYS 16384       // up to this size: 128 KiB of LDS, one workgroup per CU; beyond: global memory
@@ -125,6 +125,8 @@ struct FrParams {
 	uint32_t* blk_base;          // [V][gridDim.x][T] or null: start of each preprocess workgroup's range inside a tile segment
 	uint32_t* big_list;          // [0] = number of tiles with more than FR_SORT_SMALL_KEYS splats, [1] = k_tile_lists' finished-block count, [16..] the tiles (view*T + tile)
 	uint32_t* view_work;         // [V] tile instances listed per view, or null  } the balanced deal of the views over the XCDs
+	uint32_t* part_list;         // fixed key segments of the multi-view scorer, or null: [0] = number of parts, [16..] {key offset, count} of every part of 2 .. 512 keys
+	                             // that k_sort_split cut out of a long list (k_sort_parts sorts them); FR_PART_MAXP entries per (view, tile) at most
 	uint32_t* view_perm;         // [V] (round * 8 + XCD) -> view, or null        } (fr_deal_views / fr_tile_of_block)
 	int* status;                 // [4]
 	int* vis_count;              // [V] or null
@@ -1469,9 +1471,10 @@ __global__ __launch_bounds__(FR_THREADS) void k_scatter_vis(FrParams p)
 // XCD-aware (tile, view) of a 1-D grid of T*V workgroups: workgroups b and b+8 share an XCD (and its L2), so every
 // XCD is given whole views -- the tiles of one view then gather that view's per-splat records through one L2.
 // Placement is a speed matter only; the map is a bijection whenever V % 8 == 0 and the plain one otherwise.
-__device__ __forceinline__ void fr_tile_of_block(const FrParams& p, uint32_t& tile, int& v)
+// (`first`: workgroups in front of the T*V of the map, k_sort_split's; a multiple of 8 keeps the XCD of every tile)
+__device__ __forceinline__ void fr_tile_of_block(const FrParams& p, uint32_t& tile, int& v, uint32_t first = 0u)
 {
-	const uint32_t L = blockIdx.x;
+	const uint32_t L = blockIdx.x - first;
 	if ((p.V & 7) == 0)
 	{
 		const uint32_t xcd = L & 7u, q = L >> 3;
@@ -1788,13 +1791,12 @@ __device__ __forceinline__ void fr_sort_wg_segment(uint64_t* sk, uint64_t* __res
 
 // Segments of up to FR_SORT_SMALL_KEYS keys: one workgroup per (tile, view).  Up to 512 keys the first wave sorts alone
 // (no barrier at all; the other three leave at once), beyond that the four waves hold 256 K keys, K = 4 or 8.
-__global__ __launch_bounds__(FR_THREADS) void k_sort_tiles(FrParams p)
+// `first`: the workgroups in front of the T*V of the tile map (k_sort_split).
+__device__ __forceinline__ void fr_sort_short_list(const FrParams& p, uint64_t* skeys, uint32_t first)
 {
-	if (p.status[1]) return;
-	__shared__ uint64_t skeys[FR_SORT_SMALL_KEYS];
 	const int tid = threadIdx.x;
 	uint32_t tile; int v;
-	fr_tile_of_block(p, tile, v);
+	fr_tile_of_block(p, tile, v, first);
 	const size_t vt = (size_t)v * p.T + tile;
 	const uint32_t n = p.tile_cnt[vt];
 	if (n < 2 || n > p.small_max) return;
@@ -1823,56 +1825,76 @@ __global__ __launch_bounds__(FR_THREADS) void k_sort_tiles(FrParams p)
 	else fr_sort_wg_segment<8, 4>(skeys, gk, n, tid);
 }
 
+__global__ __launch_bounds__(FR_THREADS) void k_sort_tiles(FrParams p)
+{
+	if (p.status[1]) return;
+	__shared__ uint64_t skeys[FR_SORT_SMALL_KEYS];
+	fr_sort_short_list(p, skeys, 0u);
+}
+
 // ---------------------------------------------------------------------------------------------------------
-// k_sort_part: the long lists of fixed key segments (FR_SORT_SMALL_KEYS < n <= part_max) are PARTITIONED before they are sorted.
+// The long lists of fixed key segments (small_max < n <= part_max) are PARTITIONED before they are sorted.
 // A bitonic network over n keys runs log2(n_pad) (log2(n_pad) + 1) / 2 stages on every key -- 78 for 4096, 91 for 8192 -- and the
-// two long-list tiers cost 3x / 10x the time per key of the short-list tier (16 keys per lane, 1024-thread workgroups).  Here a
-// workgroup
-//   1  sorts a SAMPLE of 512 of the list's keys (every n/512-th; one wave, in registers) and takes NP - 1 of them as pivots, NP = the
-//      power of two that makes a part ~256-320 keys.  Pivots are full 64-bit keys (depth | slot), so runs of equal depth split too, and
-//      a sample follows the depth clusters of the walls a tile looks at (equal-width buckets do not: profiles/r04_e_split_sort.txt);
-//   2  classifies every key (binary search over the pivots: the part index is monotone in the key), counts the parts, scans;
+// two long-list tiers cost 3x / 10x the time per key of the short-list tier (16 keys per lane, 1024-thread workgroups).  Here the
+// unit of sorting work is a PART of at most 512 keys, the size one wave sorts in registers (the cheapest form of the network: 45
+// stages, no LDS, no barrier), in two launches:
+//
+// k_sort_split -- the first `split_blocks` workgroups stride over big_list; a workgroup
+//   1  sorts a SAMPLE of 512 of the list's keys (every n/512-th; its four waves, two keys per lane, the runs joined through LDS --
+//      one wave with eight keys per lane left three waves waiting and cost the kernel 85 VGPRs, five waves per SIMD for the short
+//      lists beside it) and takes NP - 1 of them as pivots, NP = the power of two that makes a part ~256-320 keys.  Pivots are full
+//      64-bit keys (depth | slot), so runs of equal depth split too, and a sample follows the depth clusters of the walls a tile
+//      looks at (equal-width buckets do not: profiles/r04_e_split_sort.txt);
+//   2  classifies every key (binary search over the pivots: the part index is monotone in the key), counts the parts; wave 0 scans
+//      the counts and appends one descriptor {key offset, count} per part of 2 .. 512 keys to the PART LIST (one global atomic per
+//      list claims its entries);
 //   3  scatters the keys part by part into the UPPER half of the tile's segment (a fixed segment holds tile_capacity keys, the list
 //      uses n of them; the order inside a part is arbitrary);
-//   4  lets its four waves take the parts one after the other, each sorted by ONE wave in registers (up to 512 keys: the cheapest
-//      form of the network, 45 stages, no LDS, no barrier); a part that sampling left larger goes to the whole workgroup;
-//   5  moves the tile's offset to where the sorted list now stands.
+//   4  sorts a part that sampling left beyond 512 keys itself, as a workgroup (rare: profiles/NOTES.md round 6);
+//   5  moves the tile's offset to where the sorted list will stand.
+// The workgroups behind them are the short-list tier (k_sort_tiles' body), one per (tile, view): the splits run longest, so they
+// start first, and the short lists fill the machine around them.
+//
+// k_sort_parts -- any wave of the grid takes any part: wave i sorts parts i, i + waves, ... of the part list.
+//
 // Parts are ranges of the key order, so their concatenation is the sorted list: the same result as the bitonic tiers, which keep the
-// lists this kernel does not take (packed lists: no room; lists beyond part_max).
+// lists these kernels do not take (packed lists: no room; lists beyond part_max).
 #define FR_PART_SAMPLE 512
 #define FR_PART_MAXP 64
-__global__ __launch_bounds__(FR_THREADS) void k_sort_part(FrParams p, uint32_t part_max)
+__global__ __launch_bounds__(FR_THREADS) void k_sort_split(FrParams p, uint32_t part_max, uint32_t split_blocks)
 {
-	__shared__ uint64_t skeys[FR_SORT_SMALL_KEYS];          // the workgroup-level sort of an oversized part
+	__shared__ uint64_t skeys[FR_SORT_SMALL_KEYS];          // a short list's runs / the workgroup-level sort of an oversized part
 	__shared__ uint64_t s_piv[FR_PART_MAXP];
 	__shared__ uint32_t s_cnt[FR_PART_MAXP], s_off[FR_PART_MAXP], s_cur[FR_PART_MAXP];
-	__shared__ uint32_t s_next;
+	__shared__ uint32_t s_over;
 	if (p.status[1]) return;
+	if (blockIdx.x >= split_blocks) { fr_sort_short_list(p, skeys, split_blocks); return; }
 	const int tid = threadIdx.x, lane = tid & 63;
 	const uint32_t count = p.big_list[0];
-	for (uint32_t b = blockIdx.x; b < count; b += gridDim.x)
+	for (uint32_t b = blockIdx.x; b < count; b += split_blocks)
 	{
 		const size_t vt = p.big_list[16 + b];
 		const uint32_t n = p.tile_cnt[vt];
 		if (n > part_max) continue;                            // (uniform) a bitonic tier's list
-		uint64_t* gk = p.keys + p.tile_off[vt];
+		const uint32_t toff = p.tile_off[vt];
+		uint64_t* gk = p.keys + toff;
 		const uint32_t n_al = (n + 63u) & ~63u;
 		uint64_t* tmp = gk + n_al;
 		// parts of ~256-320 keys: NP = 4 (n <= 1280), 8 (<= 2560), 16 (<= 5120), 32 (<= 10240), 64
 		const uint32_t NP = n <= 1280u ? 4u : n <= 2560u ? 8u : n <= 5120u ? 16u : n <= 10240u ? 32u : 64u;
 		__syncthreads();                                       // the previous list's LDS is free
 		if (tid < FR_PART_MAXP) { s_cnt[tid] = 0u; s_cur[tid] = 0u; }
-		if (tid == 0) s_next = 0u;
-		// ---- 1: the sample, sorted by wave 0 (8 keys per lane)
-		if (tid < 64)
+		// ---- 1: the sample, sorted by the four waves (2 keys per lane, runs joined through LDS)
 		{
-			uint64_t key[8];
+			const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+			uint64_t key[2];
 #pragma unroll
-			for (int r = 0; r < 8; r++) key[r] = gk[(uint32_t)(((uint64_t)(uint32_t)(lane * 8 + r) * n) >> 9)];
-			fr_wave_stages<8, 9>(key, (uint32_t)FR_PART_SAMPLE, lane);
-			// pivot q (1 .. NP - 1) = sample element q * 512 / NP = register 0 of lane q * 64 / NP
-			const uint32_t step = 64u / NP;                      // 8, 4, 2 or 1 lanes
-			if (((uint32_t)lane % step) == 0u && lane > 0) s_piv[(uint32_t)lane / step] = key[0];
+			for (int r = 0; r < 2; r++) key[r] = gk[(uint32_t)(((uint64_t)(uint32_t)(w * 128 + lane * 2 + r) * n) >> 9)];
+			fr_wave_stages<2, 7>(key, (uint32_t)FR_PART_SAMPLE, lane);
+			fr_wg_stages<2, 4, 2>(key, skeys, (uint32_t)FR_PART_SAMPLE, w, lane);
+			// pivot q (1 .. NP - 1) = sample element q * 512 / NP (an even position: register 0 of its thread)
+			const uint32_t pos = (uint32_t)(w * 128 + lane * 2), step = (uint32_t)FR_PART_SAMPLE / NP;
+			if (pos % step == 0u && pos > 0u) s_piv[pos / step] = key[0];
 		}
 		__syncthreads();
 		auto part_of = [&](uint64_t k) -> uint32_t {
@@ -1896,10 +1918,26 @@ __global__ __launch_bounds__(FR_THREADS) void k_sort_part(FrParams p, uint32_t p
 			for (int r = 0; r < KB; r++) { const uint32_t i = i0 + r * FR_THREADS + tid; if (i < n) atomicAdd(&s_cnt[part_of(k[r])], 1u); }
 		}
 		__syncthreads();
-		if (tid == 0)
+		// ... scanned by wave 0 (lane q = part q), which also enters the parts of one wave's size in the part list
+		if (tid < 64)
 		{
-			uint32_t run = 0;
-			for (uint32_t q = 0; q < NP; q++) { s_off[q] = run; run += s_cnt[q]; }
+			const uint32_t c = (uint32_t)lane < NP ? s_cnt[lane] : 0u;
+			uint32_t run = c;
+#pragma unroll
+			for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(run, d, 64); if (lane >= d) run += t; }
+			s_off[lane] = run - c;
+			const bool item = c >= 2u && c <= 512u;
+			const unsigned long long items = __ballot(item);
+			const unsigned long long over = __ballot(c > 512u);
+			uint32_t base = 0u;
+			if (lane == 0)
+			{
+				if (items) base = atomicAdd(&p.part_list[0], (uint32_t)__popcll(items));
+				s_over = over != 0ull;
+			}
+			base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+			if (item)
+				((uint2*)(p.part_list + 16))[base + (uint32_t)__popcll(items & ((1ull << lane) - 1ull))] = make_uint2(toff + n_al + (run - c), c);
 		}
 		__syncthreads();
 		// ---- 3: scatter
@@ -1915,24 +1953,10 @@ __global__ __launch_bounds__(FR_THREADS) void k_sort_part(FrParams p, uint32_t p
 				if (i < n) { const uint32_t q = part_of(k[r]); tmp[s_off[q] + atomicAdd(&s_cur[q], 1u)] = k[r]; }
 			}
 		}
-		__syncthreads();                                       // (the workgroup's own global stores, read back by its waves below)
-		// ---- 4: the parts, one wave each
-		for (;;)
-		{
-			uint32_t q = 0;
-			if (lane == 0) q = atomicAdd(&s_next, 1u);
-			q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
-			if (q >= NP) break;
-			const uint32_t c = s_cnt[q];
-			uint64_t* pk = tmp + s_off[q];
-			if (c < 2u || c > 512u) continue;
-			if (c <= 64u) fr_sort_wave_segment<1>(pk, c, lane);
-			else if (c <= 128u) fr_sort_wave_segment<2>(pk, c, lane);
-			else if (c <= 256u) fr_sort_wave_segment<4>(pk, c, lane);
-			else fr_sort_wave_segment<8>(pk, c, lane);
-		}
-		__syncthreads();
-		// ... and what sampling left larger than a wave's 512 keys, by the whole workgroup (uniform: every thread reads the same counts)
+		if (tid == 0) p.tile_off[vt] = toff + n_al;            // ---- 5
+		if (!s_over) continue;                                 // (uniform)
+		__syncthreads();                                       // (the workgroup's own global stores, read back below)
+		// ---- 4: what sampling left larger than a wave's 512 keys, by the whole workgroup (uniform: every thread reads the same counts)
 		for (uint32_t q = 0; q < NP; q++)
 		{
 			const uint32_t c = s_cnt[q];
@@ -1943,7 +1967,25 @@ __global__ __launch_bounds__(FR_THREADS) void k_sort_part(FrParams p, uint32_t p
 			else fr_bitonic(pk, c, tid, FR_THREADS);
 			__syncthreads();
 		}
-		if (tid == 0) p.tile_off[vt] += n_al;                  // ---- 5
+	}
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_sort_parts(FrParams p)
+{
+	if (p.status[1]) return;
+	const int lane = threadIdx.x & 63;
+	const uint32_t count = p.part_list[0];
+	const uint2* __restrict__ parts = (const uint2*)(p.part_list + 16);
+	const uint32_t waves = gridDim.x * (uint32_t)(FR_THREADS / 64);
+	for (uint32_t i = blockIdx.x * (uint32_t)(FR_THREADS / 64) + (threadIdx.x >> 6); i < count; i += waves)
+	{
+		const uint2 d = parts[i];
+		uint64_t* pk = p.keys + (uint32_t)__builtin_amdgcn_readfirstlane((int)d.x);
+		const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.y);
+		if (c <= 64u) fr_sort_wave_segment<1>(pk, c, lane);
+		else if (c <= 128u) fr_sort_wave_segment<2>(pk, c, lane);
+		else if (c <= 256u) fr_sort_wave_segment<4>(pk, c, lane);
+		else fr_sort_wave_segment<8>(pk, c, lane);
 	}
 }
 
@@ -1961,7 +2003,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_sort_mid_tiles(FrParams p, uint3
 	{
 		const size_t vt = p.big_list[16 + b];
 		const uint32_t n = p.tile_cnt[vt];
-		if (n > (uint32_t)FR_SORT_MID_KEYS || n <= part_max) continue;        // (n <= part_max: k_sort_part's list)
+		if (n > (uint32_t)FR_SORT_MID_KEYS || n <= part_max) continue;        // (n <= part_max: k_sort_split's list)
 		uint64_t* gk = p.keys + p.tile_off[vt];
 		__syncthreads();
 #ifdef FR_AB
@@ -6876,6 +6918,21 @@ static FrSideStream& fr_side_stream(int which = 0)
 	return ss;
 }
 
+// compute units of the current device (sizes the grids that stride over device-side work lists)
+static int fr_cu_count()
+{
+	static thread_local int cus = 0, device = -1;
+	int dev = -1;
+	(void)hipGetDevice(&dev);
+	if (device != dev || cus <= 0)
+	{
+		if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+		device = dev;
+		(void)hipGetLastError();
+	}
+	return cus;
+}
+
 // Every fork onto a side stream is joined back into the caller's stream on EVERY way out of fr_bin_pipeline, the error returns
 // included: the caller may free or reuse the workspace as soon as its own stream has drained, and a side-stream kernel that is
 // still writing records or keys into it must therefore be ordered in front of whatever the caller enqueues next.
@@ -6910,6 +6967,7 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 	{
 		FrZeroer z;
 		z.add(p.tile_cnt, (size_t)p.V * p.T * 4); z.add(p.status, 16); z.add(p.big_list, 64);
+		if (p.part_list) z.add(p.part_list, 4);
 		if (p.view_work) z.add(p.view_work, (size_t)p.V * 4);
 		if (p.vis_count) z.add(p.vis_count, (size_t)p.V * 4);
 		if (p.num_rendered && p.vis_list != nullptr && p.T <= FR_MAX_LDS_TILES) z.add(p.num_rendered, (size_t)p.V * 4);   // counted by k_preprocess_views
@@ -6985,7 +7043,7 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 		hipLaunchKernelGGL(k_preprocess, gridP, dim3(FR_THREADS), hist_lds, s, p);
 		if ((rc = fr_check_launch("k_preprocess"))) return rc;
 	}
-	// fixed segments with room for k_sort_part: lists beyond `small_max` keys go to it (FR_PART_MIN, rig: A/B of the hand-over)
+	// fixed segments with room for k_sort_split: lists beyond `small_max` keys go to it (FR_PART_MIN, rig: A/B of the hand-over)
 	if (multi && p.tile_cap >= 2u * (uint32_t)FR_SORT_SMALL_KEYS + 128u && fr_debug_mode() != 32)
 	{
 		p.small_max = (uint32_t)FR_PART_MIN_DEFAULT;
@@ -7019,7 +7077,7 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 	// CU at most), so it goes to a side stream and runs underneath the two 256-thread tiers instead of after them.
 	FrSideStream& side = fr_side_stream();
 	// (a handful of views: the fork / join events cost more than the overlap gains -- one view 0.478 against 0.500 ms)
-	// (FR_DEBUG_MODE=7: every sort tier on the caller's stream -- timing ablation; fixed segments of 32768 keys and more: k_sort_part
+	// (FR_DEBUG_MODE=7: every sort tier on the caller's stream -- timing ablation; fixed segments of 32768 keys and more: k_sort_split
 	// takes every list a segment can hold twice, the 1024-thread tier is left with lists beyond 16320 keys and runs behind it)
 	const bool part_all = p.tile_cap >= 32768u && fr_debug_mode() != 32;
 	const bool want_fork = fr_debug_mode() != 7 && (!multi || p.V >= 8) && !part_all;
@@ -7027,10 +7085,11 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 	const int big_blocks = p.T * p.V < 256 ? p.T * p.V : 256;
 	if (forked) joins.forked(&side);
 	// Fixed key segments have room behind a list (tile_capacity keys per tile): lists of up to part_max keys are partitioned into
-	// wave-sized parts and sorted there (k_sort_part: after the short-list tier on the caller's stream); the two bitonic tiers keep what
-	// is longer, and everything long when the lists are packed.  FR_DEBUG_MODE=32 (rig): no partitioning.
+	// wave-sized parts (k_sort_split, in one grid with the short-list tier) and the parts sorted by whichever wave is free
+	// (k_sort_parts), both on the caller's stream; the two bitonic tiers keep what is longer, and everything long when the lists
+	// are packed.  FR_DEBUG_MODE=32 (rig): no partitioning.
 	uint32_t part_max = 0;
-	if (p.tile_cap >= 2u * (uint32_t)FR_SORT_SMALL_KEYS + 128u && fr_debug_mode() != 32)
+	if (p.part_list && p.tile_cap >= 2u * (uint32_t)FR_SORT_SMALL_KEYS + 128u && fr_debug_mode() != 32)
 	{
 		part_max = p.tile_cap / 2u - 64u;
 		if (part_max > 16320u) part_max = 16320u;
@@ -7039,14 +7098,31 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 	if ((rc = fr_check_launch("k_sort_big_tiles"))) return rc;
 	const int mid_blocks = p.T * p.V < 2048 ? p.T * p.V : 2048;
 	// (the middle tier on a side stream of its own as well, all three tiers at once: 2.04 ms per 64-view step against 1.95 --
-	// the 256-thread tiers take each other's LDS and wave slots; k_sort_part beside the short-list tier on a stream of its own:
-	// 1.504-1.520 against 1.508-1.519 behind it, profiles/r04_q_ab_sort_part.txt)
-	hipLaunchKernelGGL(k_sort_tiles, dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p);
-	if ((rc = fr_check_launch("k_sort_tiles"))) return rc;
+	// the 256-thread tiers take each other's LDS and wave slots; the round-4 partition kernel beside the short-list tier on a stream
+	// of its own: 1.504-1.520 against 1.508-1.519 behind it, profiles/r04_q_ab_sort_part.txt)
 	if (part_max)
 	{
-		hipLaunchKernelGGL(k_sort_part, dim3(mid_blocks), dim3(FR_THREADS), 0, s, p, part_max);
-		if ((rc = fr_check_launch("k_sort_part"))) return rc;
+		// the splitting workgroups first: a fixed count striding over big_list (its length lives on the device), a multiple of 8
+		// whenever the tile map deals views over the XCDs (then T * V is one too).  Four per CU: they hold their wave slots for the
+		// whole kernel, and the short lists want the rest (64 views, ms per step on one box: 512 workgroups 1.447-1.453, 768
+		// 1.438-1.440, 1024 1.426-1.439, 1536 1.440-1.443, 2048 1.432-1.435: flat from 768 up; 256 lost 0.05 ms with the
+		// one-wave sample sort -- profiles/NOTES.md round 6).  FR_SPLIT_BLOCKS, FR_PART_BLOCKS (rig): other counts.
+		uint32_t split_blocks = (4u * (uint32_t)fr_cu_count()) & ~7u;
+		if (split_blocks < 8u) split_blocks = 8u;
+		if (split_blocks > (uint32_t)(p.T * p.V)) split_blocks = (uint32_t)(p.T * p.V);
+		FR_AB_ONLY({ const int e = fr_env_int("FR_SPLIT_BLOCKS"); if (e >= 8 && e <= 8192) split_blocks = (uint32_t)e & ~7u; })
+		hipLaunchKernelGGL(k_sort_split, dim3(split_blocks + (uint32_t)(p.T * p.V)), dim3(FR_THREADS), 0, s, p, part_max, split_blocks);
+		if ((rc = fr_check_launch("k_sort_split"))) return rc;
+		// the part count lives on the device too: a grid that fills the machine once (8 workgroups of 4 waves per CU)
+		uint32_t part_blocks = 8u * (uint32_t)fr_cu_count();
+		FR_AB_ONLY({ const int e = fr_env_int("FR_PART_BLOCKS"); if (e >= 1 && e <= 65536) part_blocks = (uint32_t)e; })
+		hipLaunchKernelGGL(k_sort_parts, dim3(part_blocks), dim3(FR_THREADS), 0, s, p);
+		if ((rc = fr_check_launch("k_sort_parts"))) return rc;
+	}
+	else
+	{
+		hipLaunchKernelGGL(k_sort_tiles, dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p);
+		if ((rc = fr_check_launch("k_sort_tiles"))) return rc;
 	}
 	if (part_max < (uint32_t)FR_SORT_MID_KEYS)
 	{
@@ -7507,7 +7583,7 @@ static int fr_debug_mode()
 
 #define FR_MAX_GROUPS 4              // view groups of one fr_fisher_views call (fr_pick_groups)
 struct FrFisherLayout {
-	size_t radii, vis_n, splat, recq, slot_idx, packed, mt, grp, big_list, view_work, view_perm, blk_base, cov3D, tile_cnt, tile_off, tile_fill, tile_scores, w2c_inv, status, keys, fallback, seg_T, seg_C, seg_X, seg_list, total;
+	size_t radii, vis_n, splat, recq, slot_idx, packed, mt, grp, big_list, part_list, view_work, view_perm, blk_base, cov3D, tile_cnt, tile_off, tile_fill, tile_scores, w2c_inv, status, keys, fallback, seg_T, seg_C, seg_X, seg_list, total;
 	size_t PV;                   // slots per view of the compact records: projection workgroups * 256 G (>= P)
 };
 static FrFisherLayout fr_fisher_layout(int64_t P, int64_t W, int64_t H, int64_t V, int64_t max_rendered, int columns)
@@ -7550,6 +7626,9 @@ static FrFisherLayout fr_fisher_layout(int64_t P, int64_t W, int64_t H, int64_t 
 	L.seg_C = o; o = fr_align(o + FR_SEG_PER_TILE * seg_tiles * FR_THREADS * 8);
 	L.seg_X = o; o = fr_align(o + seg_tiles * FR_THREADS * 8);
 	L.seg_list = o; o = fr_align(o + (FR_SEG_PER_TILE * seg_tiles + 1) * 4);
+	// the part list of the long lists of fixed key segments: one {count, pad[15], parts} per view group, like big_list; a list
+	// has at most FR_PART_MAXP parts
+	L.part_list = o; o = fr_align(o + (size_t)(V * T) * FR_PART_MAXP * 8 + 64 * FR_MAX_GROUPS);
 	L.total = o;
 	return L;
 }
@@ -7560,6 +7639,14 @@ extern "C" int fr_fisher_workspace_layout(int32_t P, int32_t W, int32_t H, int32
 		return fr_fail(FR_EINVAL, "fr_fisher_workspace_layout: bad argument");
 	const FrFisherLayout L = fr_fisher_layout(P, W, H, n_views, max_rendered, columns);
 	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+	return FR_OK;
+}
+
+extern "C" int fr_fisher_part_list_offset(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns, size_t* offset)
+{
+	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0 || (columns != 4 && columns != 11) || !offset)
+		return fr_fail(FR_EINVAL, "fr_fisher_part_list_offset: bad argument");
+	*offset = fr_fisher_layout(P, W, H, n_views, max_rendered, columns).part_list;
 	return FR_OK;
 }
 
@@ -7736,6 +7823,7 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	p.tile_fill = (uint32_t*)(ws + L.tile_fill);
 	p.status = (int*)(ws + L.status);
 	p.big_list = (uint32_t*)(ws + L.big_list);
+	p.part_list = (uint32_t*)(ws + L.part_list);
 	// the views dealt over the XCDs by weight (FR_DEBUG_MODE=27: in index order, for A/B runs)
 	const bool deal = (V & 7) == 0 && V <= 1024 && fr_debug_mode() != 27;
 	p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
@@ -7848,6 +7936,7 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 		pg.tile_cnt = p.tile_cnt + (size_t)v0 * p.T; pg.tile_off = p.tile_off + (size_t)v0 * p.T; pg.tile_fill = p.tile_fill + (size_t)v0 * p.T;
 		pg.status = p.status + 4 * gi;
 		pg.big_list = p.big_list + (size_t)v0 * p.T + 16 * gi;
+		pg.part_list = p.part_list + (size_t)v0 * p.T * (2 * FR_PART_MAXP) + 16 * gi;
 		if (p.view_perm && (Vg & 7) == 0) { pg.view_work = p.view_work + v0; pg.view_perm = p.view_perm + v0; }
 		else { pg.view_work = nullptr; pg.view_perm = nullptr; }
 		pg.blk_base = p.blk_base + (size_t)v0 * (size_t)fr_preprocess_blocks(P, V) * (size_t)p.T;
@@ -7986,6 +8075,7 @@ extern "C" int fr_fisher_pose_views(const fr_raster_cfg* cfg, const fr_gaussians
 	p.tile_fill = (uint32_t*)(ws + L.tile_fill);
 	p.status = (int*)(ws + L.status);
 	p.big_list = (uint32_t*)(ws + L.big_list);
+	p.part_list = (uint32_t*)(ws + L.part_list);
 	const bool deal = (V & 7) == 0 && V <= 1024;
 	p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
 	p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;

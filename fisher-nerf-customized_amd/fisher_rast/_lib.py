@@ -84,7 +84,7 @@ class OccCfg(ctypes.Structure):
 
 # every symbol include/fisher_rast.h and include/fisher_occ.h declare
 EXPORTS = (
-    "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
+    "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
     "fr_forward", "fr_backward", "fr_backward_scratch_bytes", "fr_backward_ws", "fr_forward_pair", "fr_forward_features", "fr_backward_pair", "fr_backward_pair_scratch_bytes", "fr_backward_pair_ws", "fr_fisher_workspace_bytes", "fr_fisher_views",
     "fr_fisher_pose_workspace_bytes", "fr_fisher_pose_workspace_layout", "fr_fisher_pose_views",
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
@@ -129,8 +129,9 @@ def load():
     # libamdhip64 dependency is resolved, or the two would each hold their own (device-less) state.
     import torch  # noqa: F401
     lib = ctypes.CDLL(SO_PATH)
+    ab_build = "FISHER_RAST_SO" in os.environ          # an A/B partner may be an older build, without the newest entry points
     for name in EXPORTS:
-        if not hasattr(lib, name):
+        if not hasattr(lib, name) and not ab_build:
             raise FisherRastError(f"{SO_PATH} does not export {name}")
     lib.fr_version.restype = ctypes.c_int
     lib.fr_last_error.restype = ctypes.c_char_p
@@ -139,6 +140,9 @@ def load():
     lib.fr_fisher_workspace_layout.restype = ctypes.c_int
     lib.fr_fisher_workspace_layout.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+    if hasattr(lib, "fr_fisher_part_list_offset"):
+        lib.fr_fisher_part_list_offset.restype = ctypes.c_int
+        lib.fr_fisher_part_list_offset.argtypes = lib.fr_fisher_workspace_layout.argtypes
     # a stale or foreign binary must not pass for the sources beside it (FISHER_RAST_SO builds for A/B runs are exempt)
     want = source_hash()
     got = lib.fr_build_id().decode().split(":")[-1]

@@ -313,7 +313,7 @@ class FisherScorer:
         # list the in-LDS sort tiers take) x 8 B = 128 KiB per tile -- 32 MiB per 256 x 256 view of the 288 GB; a longer list
         # raises the overflow flag and `run` grows the segments, or goes back to packed lists where they would not fit.
         self.tiles = ((self.W + 15) // 16) * ((self.H + 15) // 16)
-        # (default: 32768 keys -- the library then partitions every list of up to 16320 keys behind itself, k_sort_part, and the
+        # (default: 32768 keys -- the library then partitions every list of up to 16320 keys behind itself, k_sort_split + k_sort_parts, and the
         # 1024-thread bitonic tier and its side stream only see longer lists -- or 16384 where that would pass the cap per view)
         if tile_capacity < 0:
             tile_capacity = 32768 if self.tiles * 32768 * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 16384

@@ -251,6 +251,11 @@ size_t fr_fisher_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n_view
  * [5] tile_scores f32[V,T], [6] status i32[4], [7] visible-list lengths u32[V, blocks] */
 int fr_fisher_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns,
                                size_t offsets[8]);
+/* Byte offset of the PART LIST in the same workspace (fixed key segments; appended behind every section above): u32 [0] = number
+ * of parts of the last call (of its first view group), [16 ..] pairs {key offset relative to section [2], count}: the ranges of
+ * 2 .. 512 keys that the long lists (2049 .. tile_capacity / 2 - 64 keys) were cut into, each sorted by one wave; up to 64 per
+ * (view, tile).  A view group after the first has its own {count, pad[15], pairs} at u32 index first_view * tiles * 128 + 16 * group. */
+int fr_fisher_part_list_offset(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns, size_t* offset);
 
 /* Scores n_views candidate poses in one batched launch sequence.  g->means3D are WORLD positions; each view's
  * camera-frame means are computed in-kernel from cfg_f->w2c and then rendered through cfg->viewmatrix/projmatrix
