@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("FISHER_RAST_SO", os.path.join(_HERE, "libfisher_rast.so"))
 
 FR_OK, FR_EINVAL, FR_ELAUNCH, FR_ENOSPACE = 0, 1, 2, 3
+FR_POPGS_TOPT, FR_POPGS_DOPT = 0, 1
 
 _f32p = ctypes.c_void_p  # device pointers travel as raw addresses
 
@@ -87,6 +88,7 @@ EXPORTS = (
     "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
     "fr_forward", "fr_backward", "fr_backward_scratch_bytes", "fr_backward_ws", "fr_forward_pair", "fr_forward_features", "fr_backward_pair", "fr_backward_pair_scratch_bytes", "fr_backward_pair_ws", "fr_fisher_workspace_bytes", "fr_fisher_views",
     "fr_fisher_pose_workspace_bytes", "fr_fisher_pose_workspace_layout", "fr_fisher_pose_views",
+    "fr_popgs_diag_criterion_workspace_bytes", "fr_popgs_diag_criterion",
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
@@ -96,7 +98,7 @@ _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -203,6 +205,13 @@ def load():
     lib.fr_fisher_pose_views.restype = ctypes.c_int
     lib.fr_fisher_pose_views.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.POINTER(FisherCfg), _f32p,
                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+    if hasattr(lib, "fr_popgs_diag_criterion"):
+        lib.fr_popgs_diag_criterion_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_popgs_diag_criterion_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64]
+        lib.fr_popgs_diag_criterion.restype = ctypes.c_int
+        lib.fr_popgs_diag_criterion.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _f32p, _f32p, ctypes.c_int64, _f32p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.fr_densify_stats.restype = ctypes.c_int
     lib.fr_densify_stats.argtypes = [ctypes.c_int32, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]
     lib.fr_densify_masks.restype = ctypes.c_int

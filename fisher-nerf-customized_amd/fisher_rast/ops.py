@@ -1,12 +1,14 @@
 """Torch-tensor front end of the C ABI: device memory, streams and nothing else.
 
-Three groups of entry points:
+Four groups of entry points:
   * `rasterize_forward` / `rasterize_backward` / `mark_visible` -- the argument lists of the reference's
     pybind module `_C` (thirdparty/diff-gaussian-rasterization-modified/ext.cpp:14-18,
     rasterize_points.h:18-66); `diff_gaussian_rasterization/_C.py` re-exports them under the reference names.
   * `FisherScorer` -- the batched multi-view scorer behind GaussianSLAM.compute_Hessian / compute_H_train /
     pose_eval (models/SLAM/gaussian.py:1338-1375, 1503-1570).
   * `knn_dist2` -- simple_knn._C.distCUDA2.
+  * `popgs_diag_criterion` -- the POp-GS T-opt / D-opt score of a batch of views from their probe rows, and the priors of the
+    path evaluation updated in the same pass (tester_gaussians_navigation.py:2147-2178).
 """
 import ctypes
 from typing import Optional
@@ -602,3 +604,69 @@ def knn_dist2(points: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(dev):
         _lib.check(lib.fr_knn_dist2(P, _ptr(pts), _ptr(out), ws.data_ptr(), ws.numel(), _stream(dev)), "fr_knn_dist2")
     return out
+
+
+def popgs_diag_criterion(rows: torch.Tensor, prior_in: torch.Tensor, lam: float = 1e-6, criterion: str = "topt", *,
+                         prior_out: Optional[torch.Tensor] = None, accumulate: Optional[torch.Tensor] = None,
+                         vis_count: Optional[torch.Tensor] = None, scores: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fr_popgs_diag_criterion: the POp-GS T-opt / D-opt score of V views from their probe rows, and optionally the views' updated
+    priors, in one pass (tester_gaussians_navigation.py:2147-2178).
+      rows [V, K, ...]   fp32 probe rows (`_pose_probe_rows`), E = the elements of one probe
+      prior_in           E elements (shared by all views) or V * E (one block per view), in the layout of the rows
+      prior_out          V * E elements or None; may be `prior_in` itself.  accumulate [V] (bool / uint8) says which views' blocks
+                         receive prior_in + J; the others are left as they are
+      vis_count [V]      int32 or None: a view that sees nothing scores exactly 0
+    Returns scores [V] float64 on the device (no host synchronisation).  Nothing is copied or converted: tensors that are not
+    contiguous fp32 (int32 / uint8 for the two small ones) on the device of `rows` are an error."""
+    _need_gpu(rows, "rows")
+    dev = rows.device
+    if rows.dim() < 3:
+        raise FisherRastError("rows must be [V, K, ...]")
+    V, K = int(rows.shape[0]), int(rows.shape[1])
+    E = rows.numel() // max(V * K, 1)
+    crit = {"topt": _lib.FR_POPGS_TOPT, "dopt": _lib.FR_POPGS_DOPT}.get(str(criterion).lower())
+    if crit is None:
+        raise ValueError("criterion must be 'topt' or 'dopt'")
+
+    def plain(t, name, dtype):
+        _need_gpu(t, name)
+        if t.device != dev or t.dtype != dtype or not t.is_contiguous():
+            raise FisherRastError(f"{name} must be a contiguous {dtype} tensor on {dev}")
+        return t
+
+    plain(rows, "rows", torch.float32)
+    plain(prior_in, "prior_in", torch.float32)
+    if prior_in.numel() not in (E, V * E):
+        raise FisherRastError(f"prior_in has {prior_in.numel()} elements, expected {E} (shared) or {V * E} (per view)")
+    stride = E if prior_in.numel() == V * E and V > 1 else 0
+    if prior_out is not None and plain(prior_out, "prior_out", torch.float32).numel() != V * E:
+        raise FisherRastError(f"prior_out has {prior_out.numel()} elements, expected {V * E}")
+    if accumulate is not None:
+        accumulate = torch.as_tensor(accumulate)
+        if accumulate.dtype == torch.bool:
+            accumulate = accumulate.to(torch.uint8)
+        if not accumulate.is_cuda:
+            accumulate = accumulate.to(dev)
+        if plain(accumulate, "accumulate", torch.uint8).numel() != V:
+            raise FisherRastError("accumulate must have one entry per view")
+        if prior_out is None:
+            raise FisherRastError("accumulate needs prior_out")
+    if vis_count is not None and plain(vis_count, "vis_count", torch.int32).numel() != V:
+        raise FisherRastError("vis_count must have one entry per view")
+    lib = _lib.load()
+    need = int(lib.fr_popgs_diag_criterion_workspace_bytes(V, E))
+    if workspace is None:
+        workspace = torch.empty((max(need, 8) // 8,), dtype=torch.float64, device=dev)
+    else:
+        plain(workspace, "workspace", workspace.dtype)
+    if scores is None:
+        scores = torch.empty((V,), dtype=torch.float64, device=dev)
+    elif plain(scores, "scores", torch.float64).numel() != V:
+        raise FisherRastError("scores must have one entry per view")
+    with torch.cuda.device(dev):
+        _lib.check(lib.fr_popgs_diag_criterion(V, K, E, _ptr(rows), _ptr(prior_in), stride, _ptr(prior_out), _ptr(accumulate),
+                                               _ptr(vis_count), float(lam), crit, _ptr(scores), _ptr(workspace),
+                                               workspace.numel() * workspace.element_size(), _stream(dev)),
+                   "fr_popgs_diag_criterion")
+    return scores

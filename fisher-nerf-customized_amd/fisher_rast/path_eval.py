@@ -10,6 +10,7 @@ weights (`H_inv_view_stride`) and per-view `out_H` blocks, then updates every pa
 Every step also adds `path_pose_weight * log(det(pose_H))`.  The reference's pose_H is eye(6), a placeholder, so that term is
 zero; `evaluate_paths(..., pose_fisher=True)` puts the camera-pose Fisher information there (`FisherScorer.pose_fisher`, all
 steps of all paths in one batched call).
+`evaluate_paths_popgs` (below) is the same round structure for the POp-GS variant of the loop (tester 2109-2204).
 """
 import numpy as np
 import torch
@@ -113,3 +114,105 @@ def evaluate_paths(scorer, start_c2w, path_actions, final_EIGs, H_train, *, forw
         else:
             out.append((totals[i] + float(final_EIGs[i])) / n)
     return out
+
+
+# ---- POp-GS path evaluation (tester_gaussians_navigation.py:2109-2204) ------------------------------------------------------
+# The reference calls `estimate_diag_JtJ_simple` at EVERY step of every path -- K probes through autograd each -- scores the step
+# with T-opt or D-opt against the path's prior, and uses the result only on every `acc_H_train_every`-th step, where it also
+# folds the estimate into the prior.  Here only the accumulation steps are computed, in rounds as `evaluate_paths` runs them:
+# round m = ONE probe launch for the m-th accumulation step of every path that has one (K views per path of one
+# fr_fisher_views call), then ONE fr_popgs_diag_criterion call that scores them and updates the paths' priors in place.
+
+def popgs_round_schedule(path_lengths, acc_H_train_every):
+    """The rounds of a batched evaluation.  Returns (order, rounds):
+      order   the path indices by descending number of accumulation steps (stable), so that the paths active in a round are a
+              prefix of it and a path's place in it is its row in the state tensor;
+      rounds  rounds[m] = [(path, step, last), ...] in that order: the m-th accumulation step of every path that has one.
+              `step` is 1-based, (step + 1) % acc_H_train_every == 0 (tester 2176); `last` marks a path's final accumulation
+              step, whose estimate no later step reads."""
+    acc = int(acc_H_train_every)
+    if acc < 1:
+        raise ValueError("acc_H_train_every must be >= 1")
+    steps = [[s for s in range(1, int(n) + 1) if (s + 1) % acc == 0] for n in path_lengths]
+    order = sorted(range(len(steps)), key=lambda i: -len(steps[i]))
+    rounds = []
+    for m in range(max((len(s) for s in steps), default=0)):
+        rounds.append([(i, steps[i][m], len(steps[i]) == m + 1) for i in order if len(steps[i]) > m])
+    return order, rounds
+
+
+def popgs_path_value(point_terms, n_actions, final_EIG, path_end_weight=0.0, object_path_end_weight=0.0):
+    """End of a path exactly as tester 2186-2191: the branch is chosen by `path_end_weight`, the final EIG is multiplied by
+    `object_path_end_weight`.  `point_terms` are the (weighted) terms of the accumulation steps, added in order; a path without
+    actions divides by 1 (the reference would divide by zero)."""
+    total = 0.0
+    for t in point_terms:
+        total += float(t)
+    n = max(int(n_actions), 1)
+    final = float(final_EIG.item() if hasattr(final_EIG, "item") else final_EIG)
+    if path_end_weight > 0:
+        return total / n + float(object_path_end_weight) * final
+    return (total + final) / n
+
+
+def popgs_rows_from_flat(H_diag, P):
+    """[means(3P) | opacity(P) | rot(4P) | scale(3P)] (gaussian_object.py:2100-2107, what compute_H_train_popgs returns)
+    -> the scorer's row layout [P, 11] = [mean | opacity | scale | rot]."""
+    h = H_diag.reshape(-1)
+    if h.numel() != 11 * P:
+        raise ValueError(f"H_train_diag has {h.numel()} entries, expected 11 * {P}")
+    return torch.cat([h[:3 * P].reshape(P, 3), h[3 * P:4 * P].reshape(P, 1), h[8 * P:11 * P].reshape(P, 3),
+                      h[4 * P:8 * P].reshape(P, 4)], dim=1).contiguous()
+
+
+def evaluate_paths_popgs(slam, start_c2w, path_actions, final_EIGs, H_train_diag, *, criterion="topt", lam=1e-6, K=4,
+                         forward_step_size=0.065, turn_angle=10., acc_H_train_every=5, path_point_weight=1.0,
+                         path_end_weight=0.0, object_path_end_weight=0.0, cam_height=None, probes=None, chunk_bytes=4 << 30):
+    """The list of total_path_EIG values of `path_evaluation_popgs` (tester 2121-2193), one per path.
+    `slam`: a GaussianObjectSLAM with the grafted `_pose_probe_rows`; `H_train_diag`: what `compute_H_train_popgs` returns.
+    `probes`: None draws the K upstream-gradient images of every accumulation step with torch.randn on the device; otherwise a
+    callable probes(path_index, acc_index) -> [K, 3, H, W] (acc_index counts the path's accumulation steps from 0).  The
+    reference's random stream (one draw per step, used or not) is not reproduced.
+    Memory: one round holds paths x K x P x 44 bytes of probe rows (1.85 GB at 21 paths, K = 4, P = 500k; rounds beyond
+    `chunk_bytes` are cut into several launches) beside the state, P x 44 bytes per path with two or more accumulation steps."""
+    from . import ops
+    crit = str(criterion).lower()
+    if crit not in ("topt", "dopt"):
+        raise ValueError("criterion must be 'topt' or 'dopt'")
+    K = int(K)
+    start = np.array(start_c2w, dtype=np.float64, copy=True)
+    if cam_height is not None:
+        start[1, 3] = cam_height
+    n_paths = len(path_actions)
+    order, rounds = popgs_round_schedule([len(a) for a in path_actions], acc_H_train_every)
+    place = {i: r for r, i in enumerate(order)}
+    poses = [rollout(start, a, forward_step_size, turn_angle) for a in path_actions]
+    point_terms = [[] for _ in range(n_paths)]
+    if rounds:
+        P = int(slam.params['means3D'].shape[0])
+        dev = slam.params['means3D'].device
+        prior0 = popgs_rows_from_flat(H_train_diag.detach().to(dev, torch.float32), P)
+        # rows of the state: the paths that ever fold an estimate into their prior (a prefix of `order`)
+        n_state = sum(1 for _, _, last in rounds[0] if not last)
+        state = torch.empty((n_state, P, 11), dtype=torch.float32, device=dev)
+        per = max(1, int(chunk_bytes // (K * P * 44)))
+    for m, rnd in enumerate(rounds):
+        cuts = sorted({0, len(rnd)} | set(range(per, len(rnd), per)) | ({n_state} if m == 0 and 0 < n_state < len(rnd) else set()))
+        for v0, v1 in zip(cuts[:-1], cuts[1:]):
+            part = rnd[v0:v1]
+            assert all(place[i] == v0 + k for k, (i, _, _) in enumerate(part))
+            c2w = np.stack([poses[i][s - 1] for i, s, _ in part])
+            w2c = torch.from_numpy(np.linalg.inv(c2w)).float().to(dev)
+            zs = None if probes is None else [z for i, _, _ in part for z in probes(i, m)]
+            rows, vis = slam._pose_probe_rows(w2c, K, zs)
+            writes = v1 <= n_state
+            scores = ops.popgs_diag_criterion(
+                rows, prior0 if m == 0 else state[v0:v1], lam, crit,
+                prior_out=state[v0:v1] if writes else None,
+                accumulate=torch.tensor([not last for _, _, last in part], dtype=torch.uint8) if writes else None,
+                vis_count=vis.to(torch.int32).contiguous())
+            del rows
+            for (i, _, _), s in zip(part, scores.cpu().tolist()):            # the round's one host read
+                point_terms[i].append(float(path_point_weight) * s)
+    return [popgs_path_value(point_terms[i], len(path_actions[i]), final_EIGs[i], path_end_weight, object_path_end_weight)
+            for i in range(n_paths)]

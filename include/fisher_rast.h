@@ -28,6 +28,8 @@
  *                           (V x [forward + backward(power=2) + cat + sum]) as one batched call
  *   fr_fisher_pose_views <- the pose_H of compute_Hessian(return_pose=True) that the path objective uses
  *                           (tester_gaussians_navigation.py:1689-1701; a placeholder eye(6) in the reference)
+ *   fr_popgs_diag_criterion <- the T-opt / D-opt criterion and prior update inside path_evaluation_popgs
+ *                           (tester_gaussians_navigation.py:2147-2178, models/SLAM/gaussian_object.py:1705-1719)
  *   fr_densify_stats / fr_densify_masks / fr_prune_mask <- the statistics of get_loss / densify / prune_gaussians
  *                           models/SLAM/gaussian.py:289-291, models/SLAM/utils/slam_external.py:196-200, 345-465
  *   fr_knn_dist2         <- simple_knn._C.distCUDA2 (thirdparty/simple-knn, un-vendored submodule)
@@ -286,6 +288,36 @@ size_t fr_fisher_pose_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n
 int fr_fisher_pose_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, size_t offsets[9]);
 int fr_fisher_pose_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* cfg_f, float* out_pose_H,
                          void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream);
+
+/* ---- POp-GS diagonal criteria over probe rows ("T-opt/D-opt variants") ---------------------
+ * The reference scores a pose from the diagonal estimator with a chain of torch ops over [11 P] vectors and, along a path, folds
+ * the estimate into the path's prior (models/SLAM/gaussian_object.py:1705-1719, tester_gaussians_navigation.py:2147-2178).
+ * One call does that for V views in one streaming pass.  Per entry e of view v
+ *     J      = (sum_k rows[v,k,e]^2) / K                                      fp32
+ *     prior  = prior_in[v,e] + lam ;  post = prior + J
+ *     T-opt:  scores[v] = - sum_e 1 / max(post, 1e-12)
+ *     D-opt:  scores[v] =   sum_e [ log max(post, 1e-12) - log max(prior, 1e-12) ]
+ * Every term is formed in fp32 without cancellation -- the D-opt term is log1p(J / prior) where nothing is clamped and exactly 0
+ * where J == 0, never the difference of two rounded logarithms -- and the terms are added in fp64: per thread, per wave, one partial per
+ * workgroup into `workspace`, then a view's partials in index order.  No atomics: the same call gives the same bits, and a view's
+ * score does not depend on the other views of the batch (the workgroups per view depend on E alone).
+ *   rows        [V, K, E] the probe rows as fr_fisher_views wrote them (out_H per view under dL_dpix_image), E = P * columns entries
+ *               per view.  The criteria are sums over all entries, so any layout will do that prior and rows share.
+ *   prior_in    [E] with prior_in_view_stride = 0 (every view against the same prior: the first round of a path evaluation), or
+ *               [V, E] with prior_in_view_stride = E
+ *   prior_out   [V, E] or null; accumulate [V] bytes or null (= no view accumulates).  Where accumulate[v] != 0,
+ *               prior_out[v,e] = prior_in[v,e] + J (fp32; the reference's H_train_path + cur_diag, lam not included); the other views'
+ *               blocks are not touched.  prior_out may BE prior_in (same pointer, stride E); any other overlap is rejected.
+ *   vis_count   [V] or null: a view with vis_count[v] == 0 scores exactly 0.0 (tester 2162-2163); its prior still accumulates
+ *   scores      [V] fp64
+ *   workspace   fr_popgs_diag_criterion_workspace_bytes(V, E) bytes (host-only query; 0 for a bad argument), 8-byte aligned
+ * 16-byte loads and stores when E % 4 == 0 and the pointers are 16-byte aligned, dword ones otherwise; the result is the same. */
+enum { FR_POPGS_TOPT = 0, FR_POPGS_DOPT = 1 };
+#define FR_POPGS_CLAMP 1e-12f
+size_t fr_popgs_diag_criterion_workspace_bytes(int32_t V, int64_t E);
+int fr_popgs_diag_criterion(int32_t V, int32_t K, int64_t E, const float* rows, const float* prior_in, int64_t prior_in_view_stride,
+                            float* prior_out, const uint8_t* accumulate, const int32_t* vis_count, float lam, int32_t criterion,
+                            double* scores, void* workspace, size_t workspace_bytes, fr_stream_t stream);
 
 /* ---- densification / pruning statistics of the training step ---------------------------
  * One pass over the Gaussians each, in place of the torch-op chains of models/SLAM/gaussian.py:289-291 and
