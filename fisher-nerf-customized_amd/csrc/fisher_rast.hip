@@ -30,6 +30,8 @@
 //                                           few views: <.., 1> pass 1 per tile + work list, <.., 2> pass 2 per list segment
 //   k_fisher_tile_v2<4|11>  T*V             transmittance pass + backward(power=2) fused, wave-private: H_inv AND out_H in one launch,
 //                                           11-column out_H beyond 4096 tiles
+//   k_render_views_tile<3|6>  T*V           fr_render_views: RGB, (z, 1, z z), median depth and final T of V views from 48-byte compact records,
+//                                           the pair arithmetic of k_render_forward_walk (bit-identical images)
 //   k_fisher_tile        T*V                first-generation scan kernel: fallback for tiles beyond the LDS index of the above
 //   k_knn_*, fr_spatial_order               simple-knn distCUDA2; the Z-curve order of the Gaussians
 //
@@ -647,10 +649,12 @@ __device__ __forceinline__ void fr_fisher_record_one(const FrParams& p, const fl
                                                      const float* vm, const float* pm, const float* wm, bool has_w2c,
                                                      float4* out6 = nullptr, const float4* ab_src = nullptr);
 // float4 per compact record of a front-end mode: AF 0 = score form, 1 = A-form of k_fisher_tile_v3h, 2 = general out_H form,
-// 3 = pose form of k_fisher_pose_tile (the general 4-column form with the camera-frame mean in the place of the colour)
+// 3 = pose form of k_fisher_pose_tile (the general 4-column form with the camera-frame mean in the place of the colour),
+// 4 = render form of k_render_views_tile: 48 bytes {x, y, ext, opacity} {conic.x, conic.y, conic.z, depth} {r, g, b, m.z} -- the single-view
+// rasteriser's values bit for bit (no fused multiply-add, v_rcp or v_log reaches it; `ext` only culls)
 // (score form with fixed key segments: 5 -- the 80 bytes the walk parks, k3 in the place of the footprint extents, which the tile
 // kernel then no longer needs: its keys say which strips a splat reaches and the footprint rows come from the conic itself)
-template <int C, int AF, bool DK = false> struct FrRecStride { static constexpr int value = AF >= 2 ? (C >= 11 ? 13 : 7) : ((AF == 0 && DK) ? 5 : 6); };
+template <int C, int AF, bool DK = false> struct FrRecStride { static constexpr int value = AF == 4 ? 3 : AF >= 2 ? (C >= 11 ? 13 : 7) : ((AF == 0 && DK) ? 5 : 6); };
 template <int C, bool POSE = false>
 __device__ __forceinline__ void fr_fisher_record_general(const FrParams& p, const float* __restrict__ packed, int v, uint32_t id,
                                                          const float* vm, const float* pm, const float* wm, bool has_w2c,
@@ -942,7 +946,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 template <int C, int AF, bool DK, bool IDV = false>
 __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, FrRecordArgs ra)
 {
-	static_assert((C == 4 || C == 11) && AF >= 0 && AF <= 3 && !((AF == 1 || AF == 3) && C != 4), "records modes: score form, A-form (4 columns), general out_H form, pose form (4 columns)");
+	static_assert((C == 4 || C == 11) && AF >= 0 && AF <= 4 && !((AF == 1 || AF >= 3) && C != 4), "records modes: score form, A-form (4 columns), general out_H form, pose form (4 columns), render form (4 columns)");
 	static_assert(!IDV || (C == 4 && AF == 0 && DK), "the identity-view front end is the 4-column score form's with fixed key segments");
 	constexpr int RS = FrRecStride<C, AF, DK>::value; // float4 per compact record
 	extern __shared__ uint32_t fr_dyn_lds[];     // hist[VC][T] | pairs[FR_THREADS * (VC + 1)] | wm[VC][12] | park[13][FR_THREADS] | DK: cursor[VC][T]
@@ -1161,6 +1165,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 				const fr_f3 po = has_w2c ? fr_world_to_cam(pw, wm) : pw;
 				sp = fr_preprocess_one<IDV>(po, c3, vm, pm, p.W, p.H, p.tanfovx, p.tanfovy, p.focal_x, p.focal_y, p.gx, p.gy);
 				if (sp.radius > 0) { o = o_pre; ext = fr_alpha_extent(sp.conx, sp.cony, sp.conz, o); }
+				if constexpr (AF == 4) cg = po.z;                    // render form: the camera-frame depth in the place of the colour sum
 			}
 			const bool vis = sp.radius > 0;
 			// ---- ordered ranks.  The pending list is a sequence of rounds, each sorted by (view, index), so the pairs of one view stand
@@ -1238,10 +1243,21 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 				park[0 * FR_THREADS + pos] = __float_as_uint(sp.px);
 				park[1 * FR_THREADS + pos] = __float_as_uint(sp.py);
 				park[2 * FR_THREADS + pos] = ext;
-				park[3 * FR_THREADS + pos] = __float_as_uint(__builtin_amdgcn_logf(o));
-				park[4 * FR_THREADS + pos] = __float_as_uint(-0.5f * sp.conx);
-				park[5 * FR_THREADS + pos] = __float_as_uint(-sp.cony);
-				park[6 * FR_THREADS + pos] = __float_as_uint(-0.5f * sp.conz);
+				if constexpr (AF == 4)
+				{
+					// render form: opacity and conic as the rasteriser composites them (the tile kernel derives the footprint's form itself)
+					park[3 * FR_THREADS + pos] = __float_as_uint(o);
+					park[4 * FR_THREADS + pos] = __float_as_uint(sp.conx);
+					park[5 * FR_THREADS + pos] = __float_as_uint(sp.cony);
+					park[6 * FR_THREADS + pos] = __float_as_uint(sp.conz);
+				}
+				else
+				{
+					park[3 * FR_THREADS + pos] = __float_as_uint(__builtin_amdgcn_logf(o));
+					park[4 * FR_THREADS + pos] = __float_as_uint(-0.5f * sp.conx);
+					park[5 * FR_THREADS + pos] = __float_as_uint(-sp.cony);
+					park[6 * FR_THREADS + pos] = __float_as_uint(-0.5f * sp.conz);
+				}
 				park[7 * FR_THREADS + pos] = __float_as_uint(cg);
 				park[8 * FR_THREADS + pos] = (uint32_t)i;
 				park[9 * FR_THREADS + pos] = fr_as_u32(sp.depth);
@@ -1271,7 +1287,14 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 				for (int k = 0; k < 12; k++) wm[k] = has_w2c ? s_wm[12 * cvv + k] : 0.f;
 				float4* rec_out = ra.comp + ((size_t)v * PV + slot) * RS;
 				FR_ABL(if (p.ablate == 37) rec_out = ra.comp + (size_t)tid * RS;)     // 37: the records' arithmetic without their HBM traffic
-				if constexpr (AF >= 2) fr_fisher_record_general<C, (AF == 3)>(p, ra.packed, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
+				if constexpr (AF == 4)
+				{
+					const float4 t2 = ((const float4*)(ra.packed + (size_t)idx * FrPackSize<C>::value))[2];      // {cov3D[5], r, g, b}
+					rec_out[0] = ab[0];
+					rec_out[1] = make_float4(ab[1].x, ab[1].y, ab[1].z, __uint_as_float(park[9 * FR_THREADS + r]));
+					rec_out[2] = make_float4(t2.y, t2.z, t2.w, ab[1].w);
+				}
+				else if constexpr (AF >= 2) fr_fisher_record_general<C, (AF == 3)>(p, ra.packed, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
 				else fr_fisher_record_one<C, false, (AF == 1), (AF == 0 && DK), IDV>(p, ra.H_inv, ra.hinv_stride, ra.packed, ra.recq, v, idx, vm, pm, wm, has_w2c, rec_out, ab);
 				if constexpr (DK)
 				{
@@ -4425,10 +4448,42 @@ __global__ __launch_bounds__(FR_THREADS) void k_render_forward_walk(FrParams p, 
 // The stream / chunk skeleton of k_fisher_tile_v3 for one pass of one wave; NQ = float4 of recq parked per candidate.
 // body(m, id, emask) runs once per chunk of m <= 64 candidates: lane l < m holds candidate l (its index `id`, its footprint
 // `emask` over the wave's pixels) and has parked its record at ent[l]; the body sets `done` for finished pixels.
-template <int BW, int BH, int NQ, class Body, int EF4 = FR_ENT_F4>
+// How a lane parks its candidate `id` at `e` (its EF4 float4 of LDS) and what footprint it has over the wave's strip.
+// The scorer's records: {recA, recB} are the footprint's own form, NQ float4 of recq follow.
+template <int BW, int BH, int NQ>
+struct FrParkScorer {
+	__device__ __forceinline__ unsigned long long operator()(const float4* __restrict__ rec, size_t sA, const float4* __restrict__ rq, size_t sQ,
+	                                                         uint32_t id, float4* e, float strip_lo, float tile_x0) const
+	{
+		const float4 a = rec[sA * id], b4 = rec[sA * id + 1];
+		e[0] = a; e[1] = b4;
+#pragma unroll
+		for (int k = 0; k < NQ; k++) e[2 + k] = rq[sQ * id + k];
+		return fr_footprint_mask<BW, BH>(a, b4, strip_lo, tile_x0);
+	}
+};
+// The 48-byte render records: parked as k_render_forward_walk parks a candidate -- {x, y, conic.x, conic.y} {conic.z, opacity, power
+// threshold, depth} {r, g, b, .} and, with FEAT, {m.z, 1, m.z m.z, .}; the footprint's {.., log2 opacity} {-conic.x / 2, -conic.y,
+// -conic.z / 2} form is derived here (it only culls).
+template <int BW, int BH, bool FEAT>
+struct FrParkRender {
+	__device__ __forceinline__ unsigned long long operator()(const float4* __restrict__ rec, size_t sA, const float4*, size_t,
+	                                                         uint32_t id, float4* e, float strip_lo, float tile_x0) const
+	{
+		const float4 q0 = rec[sA * id], q1 = rec[sA * id + 1], q2 = rec[sA * id + 2];
+		e[0] = make_float4(q0.x, q0.y, q1.x, q1.y);
+		e[1] = make_float4(q1.z, q0.w, fr_power_threshold(q0.w), q1.w);
+		e[2] = make_float4(q2.x, q2.y, q2.z, 0.f);
+		if constexpr (FEAT) e[3] = make_float4(q2.w, 1.0f, q2.w * q2.w, 0.f);
+		const float4 a = make_float4(q0.x, q0.y, q0.z, __builtin_amdgcn_logf(q0.w));
+		const float4 b4 = make_float4(-0.5f * q1.x, -q1.y, -0.5f * q1.z, 0.f);
+		return fr_footprint_mask<BW, BH>(a, b4, strip_lo, tile_x0);
+	}
+};
+template <int BW, int BH, int NQ, class Body, int EF4 = FR_ENT_F4, class Park = FrParkScorer<BW, BH, NQ>>
 __device__ __forceinline__ void fr_strip_pass(const uint64_t* __restrict__ gk, uint32_t n, const float4* __restrict__ rec, size_t sA,
                                               const float4* __restrict__ rq, size_t sQ, uint32_t* wq, float4 (*ent)[EF4],
-                                              int lane, float strip_lo, float tile_x0, int kshift, int wave, bool& done, Body body)
+                                              int lane, float strip_lo, float tile_x0, int kshift, int wave, bool& done, Body body, Park park = Park())
 {
 	// kshift = 4: keys = depth | slot << 4 | strips (fixed key segments) -- the wave keeps the keys with its bit, no gather per key
 	const float strip_hi = strip_lo + (float)(BH - 1), tile_x1 = tile_x0 + (float)(BW - 1);
@@ -4470,11 +4525,7 @@ __device__ __forceinline__ void fr_strip_pass(const uint64_t* __restrict__ gk, u
 		if ((uint32_t)lane < m)
 		{
 			my_id = wq[(qh + lane) & (FR_QCAP - 1)];
-			const float4 a = rec[sA * my_id], b4 = rec[sA * my_id + 1];
-			ent[lane][0] = a; ent[lane][1] = b4;
-#pragma unroll
-			for (int k = 0; k < NQ; k++) ent[lane][2 + k] = rq[sQ * my_id + k];
-			emask = fr_footprint_mask<BW, BH>(a, b4, strip_lo, tile_x0);
+			emask = park(rec, sA, rq, sQ, my_id, ent[lane], strip_lo, tile_x0);
 		}
 		qh = (qh + m) & (FR_QCAP - 1); qn -= m;
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -4999,6 +5050,95 @@ __global__ __launch_bounds__(64) void k_pose_reduce(const double* __restrict__ p
 	for (int t = 0; t < T; t++) s += part[((size_t)v * T + t) * 21 + e];
 	out[(size_t)v * 36 + a * 6 + b] = (float)s;
 	out[(size_t)v * 36 + b * 6 + a] = (float)s;
+}
+
+// fr_render_views: one workgroup per (tile, view) composites the view's RGB image, the (z, 1, z z) depth / silhouette image (NCH = 6),
+// the median depth and the final transmittance from the compact 48-byte render records of k_preprocess_views_c<4, 4, ..>.  The
+// fr_strip_pass skeleton: a wave owns a 16 x 4 strip, keeps the keys that carry its strip bit (fixed key segments; packed lists:
+// the extent test per key), parks 64 candidates at a time, and every pixel-lane walks the bits of its own footprint column front
+// to back.  The pair arithmetic is k_render_forward_walk's statement by statement (forward.cu:338-366), so a view's images are
+// the single-view rasteriser's bit for bit.  Every output pointer may be null.  On overflow nothing is written; the caller's
+// status word is copied either way.
+template <int NCH>
+__global__ __launch_bounds__(FR_THREADS) void k_render_views_tile(FrParams p, FrFisherArgs f, float* __restrict__ out_color,
+                                                                  float* __restrict__ out_feat, float* __restrict__ out_depth,
+                                                                  float* __restrict__ out_T, int* __restrict__ status_out)
+{
+	constexpr int EF4 = NCH == 6 ? 5 : 3;        // float4 per parked record (4 would repeat the LDS banks after four records)
+	__shared__ uint32_t s_q[4][FR_QCAP];
+	__shared__ float4 s_ent[4][64][EF4];
+	if (blockIdx.x == 0 && threadIdx.x < FR_STATUS_WORDS) status_out[threadIdx.x] = p.status[threadIdx.x];
+	if (p.status[1]) return;
+	const int tid = threadIdx.x, lane = tid & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	uint32_t tile; int v;
+	fr_tile_of_block(p, tile, v);
+	const uint32_t tx = tile % p.gx, ty = tile / p.gx;
+	const uint32_t bx0 = tx * FR_BLOCK_X, by0 = ty * FR_BLOCK_Y + (uint32_t)wave * 4u;
+	const uint32_t pxx = bx0 + (uint32_t)(lane & 15), pxy = by0 + (uint32_t)(lane >> 4);
+	const bool inside = pxx < (uint32_t)p.W && pxy < (uint32_t)p.H;
+	const float pfx = (float)pxx, pfy = (float)pxy;
+	const size_t vt = (size_t)v * p.T + tile;
+	const uint32_t n = p.tile_cnt[vt];
+	const uint64_t* gk = p.keys + p.tile_off[vt];
+	const float4* rec = f.recA + (size_t)v * f.ab_view;
+	uint32_t* wq = s_q[wave];
+	float4 (*ent)[EF4] = s_ent[wave];
+	const float strip_lo = (float)by0, tile_x0 = (float)bx0;
+
+	float T = 1.0f;
+	float C[NCH];
+#pragma unroll
+	for (int c = 0; c < NCH; c++) C[c] = 0.f;
+	float D = 15.0f;
+	bool done = !inside;
+	auto walk = [&](uint32_t, uint32_t, unsigned long long emask) {
+		unsigned long long mask = fr_wave_transpose64(emask, lane);
+		if (done) mask = 0ull;
+		while (mask != 0ull)
+		{
+			const int j = __ffsll((long long)mask) - 1;
+			mask &= mask - 1ull;
+			const float4 r0 = ent[j][0], r1 = ent[j][1], r2 = ent[j][2];
+			const float dx = r0.x - pfx, dy = r0.y - pfy;
+			const float power = -0.5f * (r0.z * dx * dx + r1.x * dy * dy) - r0.w * dx * dy;
+			// forward.cu:338-357; NaN falls through both tests as it does there
+			if (power > 0.0f || power < r1.z) continue;
+			const float G = fr_expf(power);
+			const float alpha = fminf(0.99f, r1.y * G);
+			if (alpha < 1.0f / 255.0f) continue;
+			const float test_T = T * (1 - alpha);
+			if (test_T < 0.0001f) { done = true; mask = 0ull; continue; }
+			C[0] = C[0] + r2.x * alpha * T; C[1] = C[1] + r2.y * alpha * T; C[2] = C[2] + r2.z * alpha * T;
+			if constexpr (NCH == 6)
+			{
+				const float4 r3 = ent[j][3];
+				C[3] = C[3] + r3.x * alpha * T; C[4] = C[4] + r3.y * alpha * T; C[5] = C[5] + r3.z * alpha * T;
+			}
+			D = (T > 0.5f && test_T < 0.5f) ? r1.w : D;
+			T = test_T;
+		}
+	};
+	fr_strip_pass<16, 4, 0, decltype(walk), EF4, FrParkRender<16, 4, (NCH == 6)>>(gk, n, rec, (size_t)f.ab_stride, nullptr, 0, wq, ent, lane, strip_lo, tile_x0, f.key_shift, wave, done, walk);
+	if (inside)
+	{
+		const size_t HW = (size_t)p.H * p.W;
+		const size_t pix = (size_t)p.W * pxy + pxx;
+		if (out_T) out_T[(size_t)v * HW + pix] = T;
+		if (out_color)
+		{
+			out_color[((size_t)v * 3 + 0) * HW + pix] = C[0] + T * p.bg[0];
+			out_color[((size_t)v * 3 + 1) * HW + pix] = C[1] + T * p.bg[1];
+			out_color[((size_t)v * 3 + 2) * HW + pix] = C[2] + T * p.bg[2];
+		}
+		if constexpr (NCH == 6)
+		{
+			out_feat[((size_t)v * 3 + 0) * HW + pix] = C[3] + T * p.bg[0];
+			out_feat[((size_t)v * 3 + 1) * HW + pix] = C[4] + T * p.bg[1];
+			out_feat[((size_t)v * 3 + 2) * HW + pix] = C[5] + T * p.bg[2];
+		}
+		if (out_depth) out_depth[(size_t)v * HW + pix] = D;
+	}
 }
 
 // fr_fisher_cfg.poses_are_c2w: the caller hands camera-to-world poses (what pose_eval receives, gaussian.py:1354-1362) and the
@@ -6956,7 +7096,7 @@ struct FrJoinGuard {
 
 // Score-only mode: the front end also produces the scorer's per-(view, Gaussian) records (k_pack_static, then phase C of
 // k_preprocess_views; with the single-view front end, k_fisher_records after k_scatter_keys, beside the sorts, on the second side stream).
-struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; bool pose = false; bool view_identity = false; };   // view_identity: fr_fisher_cfg.view_is_identity   // pose: the records of k_fisher_pose_tile (fr_fisher_pose_views)   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
+struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; bool pose = false; bool view_identity = false; bool render = false; };   // render: the 48-byte records of k_render_views_tile (fr_render_views)   // view_identity: fr_fisher_cfg.view_is_identity   // pose: the records of k_fisher_pose_tile (fr_fisher_pose_views)   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
 template <int C> __global__ void k_pack_static(FrParams p, const float* __restrict__ H_inv, float* __restrict__ packed, float4* __restrict__ mt, float4* __restrict__ grp);
 template <int C, bool LIST, bool FORM_A> __global__ void k_fisher_records(FrParams p, FrRecordArgs ra);
 
@@ -7014,7 +7154,9 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 		// against 2.53 ms: the records' waves slow the latency-bound scatter and the one-workgroup-per-CU sort tier down.)
 		const bool dk = p.tile_cap != 0;
 		const size_t lds_c = lds_c_of(p.VC);
-		if (once && plan->pose && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 3, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		if (once && plan->render && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 4, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->render) hipLaunchKernelGGL((k_preprocess_views_c<4, 4, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->pose && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 3, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->pose) hipLaunchKernelGGL((k_preprocess_views_c<4, 3, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->general && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 2, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->general && plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views_c<4, 2, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
@@ -8129,6 +8271,129 @@ extern "C" int fr_fisher_pose_views(const fr_raster_cfg* cfg, const fr_gaussians
 	if ((rc = fr_check_launch("k_fisher_pose_tile"))) return rc;
 	hipLaunchKernelGGL(k_pose_reduce, dim3(V), dim3(64), 0, s, (const double*)part, p.T, (const int*)p.status, out_pose_H, status);
 	return fr_check_launch("k_pose_reduce");
+}
+
+// ---- batched render of candidate views (fr_render_views) --------------------------------------------------------------
+// The workspace is the scorer's (4 columns): the 48-byte render records take the place of the scorer's records.
+extern "C" size_t fr_render_views_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered)
+{
+	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0) return 0;
+	if ((long long)((W + 15) / 16) * ((H + 15) / 16) > FR_MAX_LDS_TILES) return 0;
+	return fr_fisher_layout(P, W, H, n_views, max_rendered, 4).total;
+}
+
+extern "C" int fr_render_views_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, size_t o[8])
+{
+	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0 || !o || (long long)((W + 15) / 16) * ((H + 15) / 16) > FR_MAX_LDS_TILES)
+		return fr_fail(FR_EINVAL, "fr_render_views_workspace_layout: bad argument");
+	const FrFisherLayout L = fr_fisher_layout(P, W, H, n_views, max_rendered, 4);
+	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+	return FR_OK;
+}
+
+extern "C" int fr_render_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* fc,
+                               float* out_color, float* out_features, float* out_depth, float* out_final_T,
+                               void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream)
+{
+	// every argument check comes before any device work
+	int rc = fr_validate(cfg, g, "fr_render_views");
+	if (rc) return rc;
+	if (!fc || fc->n_views <= 0 || !fc->w2c || !status) return fr_fail(FR_EINVAL, "fr_render_views: bad fisher cfg or null status");
+	if (!out_color && !out_features && !out_depth && !out_final_T) return fr_fail(FR_EINVAL, "fr_render_views: no output requested");
+	if (fc->H_inv || fc->out_scores) return fr_fail(FR_EINVAL, "fr_render_views: H_inv / out_scores are for fr_fisher_views");
+	if (fc->out_H) return fr_fail(FR_EINVAL, "fr_render_views: out_H is for fr_fisher_views");
+	if (fc->dL_dpix_image) return fr_fail(FR_EINVAL, "fr_render_views: no upstream-gradient images (there is no backward)");
+	if (fc->reuse_static) return fr_fail(FR_EINVAL, "fr_render_views: reuse_static is not supported");
+	if (g->shs || !g->colors_precomp) return fr_fail(FR_EINVAL, "fr_render_views: needs colors_precomp (no SH colours)");
+	if (g->cov3D_precomp || !(g->scales && g->rotations)) return fr_fail(FR_EINVAL, "fr_render_views: needs scales and rotations (no cov3D_precomp)");
+	if (fc->tile_capacity < 0) return fr_fail(FR_EINVAL, "fr_render_views: negative tile_capacity");
+	if (max_rendered < 0) return fr_fail(FR_EINVAL, "fr_render_views: negative max_rendered");
+	const int P = cfg->P, W = cfg->image_width, H = cfg->image_height, V = fc->n_views;
+	const long long Tt = (long long)((W + 15) / 16) * ((H + 15) / 16);
+	if (Tt > FR_MAX_LDS_TILES) return fr_fail(FR_EINVAL, "fr_render_views: images beyond 4096 tiles are not supported");
+	if (fc->tile_capacity > 0)
+	{
+		const long long need = (long long)V * Tt * (long long)fc->tile_capacity;
+		if (need > max_rendered || need >= (1ll << 32)) return fr_fail(FR_EINVAL, "fr_render_views: n_views * tiles * tile_capacity exceeds max_rendered (or 2^32)");
+	}
+	if (!cfg->bg) return fr_fail(FR_EINVAL, "fr_render_views: null bg");
+	const FrFisherLayout L = fr_fisher_layout(P, W, H, V, max_rendered, 4);
+	if (!workspace || workspace_bytes < L.total)
+		return fr_fail(FR_ENOSPACE, "fr_render_views: workspace smaller than fr_render_views_workspace_bytes()");
+	hipStream_t s = (hipStream_t)stream;
+	char* ws = (char*)workspace;
+	FrParams p;
+	fr_fill_params(p, cfg, g, V);
+	p.prefiltered = 0;
+	p.tile_cnt = (uint32_t*)(ws + L.tile_cnt);
+	p.tile_off = (uint32_t*)(ws + L.tile_off);
+	p.status = (int*)(ws + L.status);
+	p.keys = (uint64_t*)(ws + L.keys);
+	FrFisherArgs f;
+	memset(&f, 0, sizeof(f));
+	constexpr int rstride = FrRecStride<4, 4>::value;
+	f.recA = (const float4*)(ws + L.recq); f.ab_view = (long long)L.PV * rstride; f.ab_stride = rstride;
+	if (P == 0)
+	{
+		// no Gaussians: every list is empty, the tile kernel writes the background, 15.0 and T = 1
+		(void)hipMemsetAsync(p.tile_cnt, 0, (size_t)V * p.T * 4, s);
+		(void)hipMemsetAsync(p.tile_off, 0, (size_t)V * p.T * 4, s);
+		(void)hipMemsetAsync(p.status, 0, 16, s);
+		if (fc->out_vis_count) (void)hipMemsetAsync(fc->out_vis_count, 0, (size_t)V * 4, s);
+		if (fc->out_num_rendered) (void)hipMemsetAsync(fc->out_num_rendered, 0, (size_t)V * 4, s);
+	}
+	else
+	{
+		p.w2c = fc->w2c;
+		if (fc->poses_are_c2w)
+		{
+			float* inv = (float*)(ws + L.w2c_inv);
+			hipLaunchKernelGGL(k_invert_poses, dim3((V + 63) / 64), dim3(64), 0, s, V, fc->w2c, inv);
+			if ((rc = fr_check_launch("k_invert_poses"))) return rc;
+			p.w2c = inv;
+		}
+		p.radii = (int*)(ws + L.radii);
+		p.vis_list = (FrVisEntry*)(ws + L.radii);
+		p.vis_n = (uint32_t*)(ws + L.vis_n);
+		p.splat = (FrSplat*)(ws + L.splat);
+		p.cov3D_out = (float*)(ws + L.cov3D);
+		p.tile_fill = (uint32_t*)(ws + L.tile_fill);
+		p.big_list = (uint32_t*)(ws + L.big_list);
+		p.part_list = (uint32_t*)(ws + L.part_list);
+		const bool deal = (V & 7) == 0 && V <= 1024;
+		p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
+		p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;
+		p.blk_base = (uint32_t*)(ws + L.blk_base);
+		p.key_capacity = max_rendered;
+		if (fc->tile_capacity > 0)
+		{
+			// fixed key segments where the compact-record front end can address them (as fr_fisher_views decides it)
+			const long long nblk_c = (P + FR_THREADS * fr_pick_G_views(P) - 1) / (FR_THREADS * fr_pick_G_views(P));
+			const bool slots_fit = nblk_c * FR_THREADS * fr_pick_G_views(P) < (1ll << 28);
+			if (p.gx <= 255u && p.gy <= 63u && slots_fit) p.tile_cap = (uint32_t)fc->tile_capacity;
+		}
+		(void)fr_plan_views_c(p.T, fr_pick_VC(p.T), p.tile_cap);
+		p.vis_count = fc->out_vis_count;
+		p.num_rendered = fc->out_num_rendered;
+		p.order = fc->order;
+		FrScorerPlan plan;
+		plan.columns = 4;
+		plan.form_a = false;
+		plan.render = true;
+		plan.ra.H_inv = nullptr; plan.ra.hinv_stride = 0;
+		plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
+		plan.ra.comp = (float4*)(ws + L.recq);
+		plan.ra.stride = rstride;
+		plan.ra.slot_idx = nullptr;
+		plan.ra.mt = (const float4*)(ws + L.mt);
+		plan.ra.grp = (const float4*)(ws + L.grp);
+		plan.ra.early = 1;
+		if ((rc = fr_bin_pipeline(p, g, s, &plan))) return rc;
+		f.key_shift = p.tile_cap ? 4 : 0;                   // (fixed segments: keys = depth | slot << 4 | strips)
+	}
+	if (out_features) hipLaunchKernelGGL((k_render_views_tile<6>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, out_color, out_features, out_depth, out_final_T, (int*)status);
+	else hipLaunchKernelGGL((k_render_views_tile<3>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, out_color, out_features, out_depth, out_final_T, (int*)status);
+	return fr_check_launch("k_render_views_tile");
 }
 
 // =========================================================================================================

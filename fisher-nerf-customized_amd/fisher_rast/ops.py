@@ -5,7 +5,8 @@ Four groups of entry points:
     pybind module `_C` (thirdparty/diff-gaussian-rasterization-modified/ext.cpp:14-18,
     rasterize_points.h:18-66); `diff_gaussian_rasterization/_C.py` re-exports them under the reference names.
   * `FisherScorer` -- the batched multi-view scorer behind GaussianSLAM.compute_Hessian / compute_H_train /
-    pose_eval (models/SLAM/gaussian.py:1338-1375, 1503-1570).
+    pose_eval (models/SLAM/gaussian.py:1338-1375, 1503-1570); its `render_views` renders a batch of poses in one call
+    (RGB, depth / silhouette, median depth, final transmittance: fr_render_views).
   * `knn_dist2` -- simple_knn._C.distCUDA2.
   * `popgs_diag_criterion` -- the POp-GS T-opt / D-opt score of a batch of views from their probe rows, and the priors of the
     path evaluation updated in the same pass (tester_gaussians_navigation.py:2147-2178).
@@ -573,6 +574,170 @@ class FisherScorer:
             outs.append(r["pose_H"])
             v0 = v1
         return torch.cat(outs) if outs else torch.zeros((0, 6, 6), dtype=torch.float32, device=self.dev)
+
+
+    # -- batched render of candidate views (fr_render_views) -----------------------------------------------
+    def render_launch(self, w2c, poses_are_c2w=False, features=True, depth=True, final_T=True, render=True, out=None):
+        """Enqueue one batch of renders (no sync).  Returns a dict of device tensors: render [V,3,H,W], depth_sil [V,3,H,W] (the
+        composited (z, 1, z z) of the camera-frame depth; `features`), median_depth [V,1,H,W] (`depth`), final_T [V,H,W], each None
+        when not asked for, and vis_count [V], num_rendered [V], status [4].  On overflow (status[1]) no image byte is written.
+        `out`: a dict that may hold contiguous fp32 device tensors of those shapes under those four names, written instead of fresh ones.
+        Its own workspace, as `pose_launch`: the packed static records of `launch` stay where they are."""
+        d = self.dev
+        w2c = _prep(w2c.reshape(-1, 4, 4), d)
+        V = int(w2c.shape[0])
+        H, W = self.H, self.W
+        if not (render or features or depth or final_T):
+            raise ValueError("render_launch: no output requested")
+
+        given = out or {}
+
+        def new(name, *shape):                              # every element is written (or the status word says overflow, and none is)
+            t = given.get(name)
+            if t is None:
+                return torch.empty(shape, dtype=torch.float32, device=d)
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != d:
+                raise ValueError(f"out['{name}'] must be a contiguous fp32 device tensor of shape {shape}")
+            return t
+        out = dict(render=new("render", V, 3, H, W) if render else None, depth_sil=new("depth_sil", V, 3, H, W) if features else None,
+                   median_depth=new("median_depth", V, 1, H, W) if depth else None, final_T=new("final_T", V, H, W) if final_T else None)
+        vis = torch.empty((V,), dtype=torch.int32, device=d)
+        nr = torch.empty((V,), dtype=torch.int32, device=d)
+        status = torch.empty((4,), dtype=torch.int32, device=d)
+        max_rendered = V * self._keys_per_view()
+        nbytes = int(self.lib.fr_render_views_workspace_bytes(self.P, W, H, V, max_rendered))
+        if nbytes == 0:
+            raise FisherRastError("fr_render_views_workspace_bytes: bad argument (or an image beyond 4096 tiles: render_views loops there)")
+        ws = self._ws.get("render")
+        if ws is None or ws.numel() < nbytes:
+            self._ws["render"] = None
+            ws = self._ws["render"] = torch.empty((nbytes,), dtype=torch.uint8, device=d)
+        self._sync_order()
+        fc = FisherCfg()
+        fc.n_views = V
+        fc.poses_are_c2w = 1 if poses_are_c2w else 0
+        fc.tile_capacity = self.tile_capacity if V * self.tiles * self.tile_capacity < (1 << 32) else 0
+        fc.w2c = ctypes.c_void_p(w2c.data_ptr())
+        fc.out_vis_count = vis.data_ptr()
+        fc.out_num_rendered = nr.data_ptr()
+        fc.order = self.order.data_ptr() if self.order is not None else None
+        with torch.cuda.device(d):
+            _lib.check(self.lib.fr_render_views(ctypes.byref(self.cfg), ctypes.byref(self.g), ctypes.byref(fc),
+                                                _ptr(out["render"]), _ptr(out["depth_sil"]), _ptr(out["median_depth"]), _ptr(out["final_T"]),
+                                                ws.data_ptr(), ws.numel(), max_rendered,
+                                                status.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)),
+                       "fr_render_views")
+        out.update(vis_count=vis, num_rendered=nr, status=status, n_views=V, _keep=(w2c,))
+        return out
+
+    @staticmethod
+    def _invert_poses(m):
+        """The library's pose inverse (k_invert_poses) restated in float64 elementwise ops on the host: the adjugate by cofactor
+        expansion, times 1 / det, rounded once to float -- the same products and sums in the same order, so the same bits."""
+        dev = m.device
+        m = m.detach().cpu().double().reshape(-1, 16)
+        m = [m[:, k] for k in range(16)]
+        inv = [None] * 16
+        inv[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10]
+        inv[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10]
+        inv[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9]
+        inv[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9]
+        inv[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10]
+        inv[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10]
+        inv[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9]
+        inv[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9]
+        inv[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6]
+        inv[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6]
+        inv[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5]
+        inv[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5]
+        inv[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6]
+        inv[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6]
+        inv[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5]
+        inv[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5]
+        det = m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12]
+        r = 1.0 / det
+        return torch.stack([x * r for x in inv], dim=1).float().reshape(-1, 4, 4).to(dev)
+
+    def _render_views_serial(self, w2c, poses_are_c2w, features, depth, final_T):
+        """Images beyond 4096 tiles: view after view through the single-view rasteriser (`rasterize_forward`, the pair path).  The
+        camera-frame means are formed in torch elementwise ops in the order the library uses, ((w0 x + w1 y) + w2 z) + w3, each
+        product and sum rounded on its own, and camera-to-world poses are inverted as the library inverts them (`_invert_poses`),
+        so the images are the ones `fr_render_views` would give."""
+        d = self.dev
+        w2c = _prep(w2c.reshape(-1, 4, 4), d)
+        if poses_are_c2w:
+            w2c = self._invert_poses(w2c)
+        rs = self.rs
+        x, y, z = self.means3D[:, 0], self.means3D[:, 1], self.means3D[:, 2]
+        empty = torch.Tensor([])
+        outs = dict(render=[], depth_sil=[], median_depth=[], final_T=[], vis_count=[], num_rendered=[])
+        for w in w2c:
+            rows = []
+            for r in range(3):
+                t = torch.mul(x, w[r, 0]) + torch.mul(y, w[r, 1])
+                t = t + torch.mul(z, w[r, 2])
+                rows.append(t + w[r, 3])
+            m = torch.stack(rows, dim=1)
+            feats = torch.stack((m[:, 2], torch.ones_like(m[:, 2]), m[:, 2] * m[:, 2]), dim=1)
+            res = rasterize_forward(self.bg, m, self.colors, self.opacities, self.scales, self.rotations, rs.scale_modifier, empty,
+                                    self.view, self.proj, rs.tanfovx, rs.tanfovy, self.H, self.W, empty, rs.sh_degree, self.campos,
+                                    False, features=feats if features else None)
+            nr, color, radii, img = res[0], res[1], res[2], res[5]
+            outs["render"].append(color)
+            outs["median_depth"].append(res[6])
+            if features:
+                outs["depth_sil"].append(res[7])
+            if final_T:
+                off = workspace_layout(self.P, self.W, self.H, 1)["final_T"]
+                outs["final_T"].append(img[off:off + 4 * self.H * self.W].view(torch.float32).reshape(self.H, self.W).clone())
+            outs["vis_count"].append((radii > 0).sum().to(torch.int32).reshape(1))
+            outs["num_rendered"].append(torch.tensor([nr], dtype=torch.int32, device=d))
+        return dict(render=torch.stack(outs["render"]), depth_sil=torch.stack(outs["depth_sil"]) if features else None,
+                    median_depth=torch.stack(outs["median_depth"]) if depth else None,
+                    final_T=torch.stack(outs["final_T"]) if final_T else None,
+                    vis_count=torch.cat(outs["vis_count"]), num_rendered=torch.cat(outs["num_rendered"]))
+
+    def render_views(self, w2c, poses_are_c2w=False, features=True, depth=True, final_T=True):
+        """RGB, depth / silhouette, median depth and final transmittance of every view: what the single-view rasteriser gives for the
+        camera-frame means of the view, bit for bit (include/fisher_rast.h, fr_render_views).  Returns dict(render [V,3,H,W],
+        depth_sil [V,3,H,W], median_depth [V,1,H,W], final_T [V,H,W], vis_count [V], num_rendered [V]) on the device; the optional
+        ones are None when switched off.  Views beyond `max_views_per_launch()` go in several calls; an overflow of the key buffer is
+        redone with a larger one, as in `pose_fisher`: one status read per chunk.  Images beyond 4096 tiles: a loop of single-view
+        renders."""
+        w2c = w2c.reshape(-1, 4, 4)
+        V = int(w2c.shape[0])
+        if self.tiles > 4096:
+            return self._render_views_serial(w2c, poses_are_c2w, features, depth, final_T)
+        chunk = self.max_views_per_launch()
+        outs = []
+        v0 = 0
+        while v0 < V:
+            v1 = min(V, v0 + chunk)
+            while True:
+                r = self.render_launch(w2c[v0:v1], poses_are_c2w, features, depth, final_T)
+                st = r["status"].cpu()
+                if int(st[1]) == 0:
+                    break
+                # overflow: nothing was written -- grow the key buffer (or the fixed segments) and redo this chunk
+                if int(st[3]):
+                    want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
+                    self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0
+                self.per_view_capacity = max(self.per_view_capacity, int(int(st[0]) * 1.25 / (v1 - v0)) + 4096)
+                chunk = min(chunk, self.max_views_per_launch())
+                v1 = min(v1, v0 + chunk)
+            outs.append(r)
+            v0 = v1
+        names = ("render", "depth_sil", "median_depth", "final_T", "vis_count", "num_rendered")
+        if len(outs) == 1:
+            return {k: outs[0][k] for k in names}
+        if not outs:
+            H, W = self.H, self.W
+            shapes = dict(render=(0, 3, H, W), depth_sil=(0, 3, H, W), median_depth=(0, 1, H, W), final_T=(0, H, W))
+            on = dict(render=True, depth_sil=features, median_depth=depth, final_T=final_T)
+            res = {k: torch.zeros(shapes[k], dtype=torch.float32, device=self.dev) if on[k] else None for k in shapes}
+            res.update(vis_count=torch.zeros((0,), dtype=torch.int32, device=self.dev), num_rendered=torch.zeros((0,), dtype=torch.int32, device=self.dev))
+            return res
+        return {k: (torch.cat([o[k] for o in outs]) if outs[0][k] is not None else None) for k in names}
 
 
 def spatial_order_of(means3D: torch.Tensor) -> torch.Tensor:

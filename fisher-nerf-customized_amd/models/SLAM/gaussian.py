@@ -4,6 +4,7 @@
 In scope (same names, arguments and return conventions as the reference):
     compute_Hessian (1503-1570)   compute_H_train (1338-1348)   pose_eval (1354-1375)
     render_at_pose (555-579)      gs_pts_cnt (1350-1352)        gaussian_points / cur_frame_idx (1590-1598)
+    render_at_poses (new: render_at_pose for a batch of poses in one call, RenderOps)
     pause / resume / color_refinement / stop (1600-1614)
 The SLAM loop itself (init, track_rgbd, densify, keyframe selection ...) is NOT rebuilt: it is reference
 Python that stays as it is.  `FisherOps.install(cls)` grafts the accelerated methods onto the reference class
@@ -280,7 +281,36 @@ class PoseFisherOps:
         return target_cls
 
 
-class GaussianSLAM(FisherOps, PoseFisherOps):
+class RenderOps:
+    """Mixin with the batched render of candidate poses (fr_render_views, include/fisher_rast.h): `render_at_pose` for V poses in one
+    call -- the reference renders every candidate it scores, one pose at a time (models/SLAM/gaussian_object.py:1640, 1668).
+    `render_at_pose` itself stays as it is; this is a new name.  Needs FisherOps' `_scorer` / `_stack_poses` (install FisherOps first)."""
+
+    def render_at_poses(self, c2ws):
+        """{"render": [V,3,H,W], "depth": [V,1,H,W], "silhouette": [V,1,H,W]} for V camera-to-world poses (tensor, array or list),
+        batched through the scorer of the current map.  Per pose: the RGB render, and channels 0 / 1 of the (z, 1, z z) render over
+        the camera-frame means -- depth and silhouette (1 - silhouette = how much of the view the map does not explain).  The
+        library inverts the poses; the camera-frame means are formed in the fixed order DESIGN.md section 2 states.
+        The depth is the camera-frame z of the pose: `render_at_pose` takes it through `self.first_frame_w2c`, which is the identity
+        in this product (GaussianSLAM.__init__); on a class whose first frame is not the identity the two "depth" images differ."""
+        res = self._scorer().render_views(self._stack_poses(c2ws), poses_are_c2w=True, depth=False, final_T=False)
+        depth_sil = res["depth_sil"]
+        return {"render": res["render"], "depth": depth_sil[:, 0:1], "silhouette": depth_sil[:, 1:2]}
+
+    def render_views(self, w2cs, features=True, depth=True, final_T=True):
+        """The full result of FisherScorer.render_views for V world->camera poses: render [V,3,H,W], depth_sil [V,3,H,W] (z, 1, z z),
+        median_depth [V,1,H,W], final_T [V,H,W], vis_count [V], num_rendered [V] (the optional ones None when switched off)."""
+        return self._scorer().render_views(self._stack_poses(w2cs), features=features, depth=depth, final_T=final_T)
+
+    @classmethod
+    def install(cls, target_cls):
+        """Graft the two methods onto the reference's class (after FisherOps.install / ObjectFisherOps.install)."""
+        for name in ("render_at_poses", "render_views"):
+            setattr(target_cls, name, getattr(cls, name))
+        return target_cls
+
+
+class GaussianSLAM(FisherOps, PoseFisherOps, RenderOps):
     """Standalone carrier of the operator surface: a Gaussian map (param dict), a camera and keyframes."""
 
     def __init__(self, config=None, params=None, intrinsics=None, width=None, height=None, device="cuda"):

@@ -28,6 +28,9 @@
  *                           (V x [forward + backward(power=2) + cat + sum]) as one batched call
  *   fr_fisher_pose_views <- the pose_H of compute_Hessian(return_pose=True) that the path objective uses
  *                           (tester_gaussians_navigation.py:1689-1701; a placeholder eye(6) in the reference)
+ *   fr_render_views      <- the render_at_pose(c2w) calls inside the candidate loops of pose_eval_popgs / pose_eval_popgs_blocks
+ *                           (models/SLAM/gaussian_object.py:1640, 1668; the image dump of pose_eval, 1606-1607): render_at_pose
+ *                           (models/SLAM/gaussian.py:555-579) for V poses -- V x [transform + two rasteriser forwards] as one batched call
  *   fr_popgs_diag_criterion <- the T-opt / D-opt criterion and prior update inside path_evaluation_popgs
  *                           (tester_gaussians_navigation.py:2147-2178, models/SLAM/gaussian_object.py:1705-1719)
  *   fr_densify_stats / fr_densify_masks / fr_prune_mask <- the statistics of get_loss / densify / prune_gaussians
@@ -249,7 +252,7 @@ size_t fr_fisher_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n_view
  *     Gaussians (>= P), one per visible (view, Gaussian) at slot = workgroup * its Gaussians + rank among the workgroup's visible
  *     splats of the view: 80 B (score form with fixed key segments: {x, y, k3, log2 o} {-cx/2, -cy, -cz/2, r+g+b} + 12 polynomial
  *     coefficients), 96 B (score form with packed lists, A-form of the 4-column out_H kernel), 112 / 208 B (general out_H form, 4 / 11
- *     columns); dense [V,P] x 64 B with the single-view front end,
+ *     columns), 48 B (render form of fr_render_views); dense [V,P] x 64 B with the single-view front end,
  * [5] tile_scores f32[V,T], [6] status i32[4], [7] visible-list lengths u32[V, blocks] */
 int fr_fisher_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns,
                                size_t offsets[8]);
@@ -288,6 +291,31 @@ size_t fr_fisher_pose_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n
 int fr_fisher_pose_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, size_t offsets[9]);
 int fr_fisher_pose_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* cfg_f, float* out_pose_H,
                          void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream);
+
+/* ---- batched render of candidate views: RGB, depth / silhouette, median depth, final transmittance -------------------
+ * View v is exactly what fr_forward / fr_forward_pair produce for means3D = m with the camera of cfg, where
+ *     m_i = ((w0 x + w1 y) + w2 z) + w3   per row of w2c[v], in binary32 without fused multiply-add
+ * and the second feature array is (m_i.z, 1, m_i.z * m_i.z): get_depth_and_silhouette with the identity first_frame_w2c
+ * (models/SLAM/utils/slam_helpers.py:268-279).  Contributor rules forward.cu:338-366; out = C + T * bg on all six channels.
+ * Bit for bit: the front end writes one 48-byte record per visible (view, Gaussian) -- {x, y, ext, opacity} {conic.x, conic.y,
+ * conic.z, depth} {r, g, b, m.z}, the single-view rasteriser's values (`ext`, the conservative half extents, only culls) -- and the
+ * tile kernel composites from them with the single-view kernel's pair arithmetic.  A view's images do not depend on the batch.
+ *   out_color    [V,3,H,W]                              or null
+ *   out_features [V,3,H,W] composited (z, 1, z*z)       or null
+ *   out_depth    [V,1,H,W] median depth (default 15.0)  or null
+ *   out_final_T  [V,H,W]                                or null      (at least one of the four)
+ * fr_fisher_cfg fields used: n_views, w2c, poses_are_c2w, out_vis_count (Gaussians with radius > 0), out_num_rendered (the
+ * reference's rectangle count), tile_capacity, order.  H_inv / out_scores, out_H, dL_dpix_image, reuse_static, SH colours
+ * (colors_precomp is required), cov3D_precomp, four null outputs and images beyond 4096 tiles are rejected (FR_EINVAL); every
+ * check is made before any device work.  status as fr_fisher_views; on overflow nothing is written (no output byte changes).
+ * No device allocation, no host synchronisation, no atomics on the images.
+ * fr_render_views_workspace_bytes is a host-only query (0 for a bad argument or an image beyond 4096 tiles); the layout's offsets
+ * [0..7] are those of fr_fisher_workspace_layout(.., columns = 4), [4] holding the compact [V][PV] x 48 B render records. */
+size_t fr_render_views_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered);
+int fr_render_views_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, size_t offsets[8]);
+int fr_render_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* cfg_f,
+                    float* out_color, float* out_features, float* out_depth, float* out_final_T,
+                    void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream);
 
 /* ---- POp-GS diagonal criteria over probe rows ("T-opt/D-opt variants") ---------------------
  * The reference scores a pose from the diagonal estimator with a chain of torch ops over [11 P] vectors and, along a path, folds
