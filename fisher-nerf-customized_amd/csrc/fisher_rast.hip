@@ -640,6 +640,7 @@ struct FrRecordArgs {
 	float4* comp;                // [V][PV][stride], PV = workgroups * 256 G
 	uint32_t* slot_idx;          // [V][PV]: slot -> Gaussian index (k_fisher_tile_v3h / _v3g flush by index)
 	int stride;                  // float4 per compact record: 6 ({recA, recB} + 4), or 7 / 13 in the general out_H form (fr_fisher_record_general)
+	float* slot_acc;             // [V][PV] or null: per-slot accumulators of k_fisher_point_tile, cleared where a record is written (SLOTS)
 };
 // floats per Gaussian of the packed static record (k_pack_static): {mean 3, cov3D 6, rgb 3, (scale 3, rot 4), H_inv C}
 template <int C> struct FrPackSize { static constexpr int value = (C >= 11) ? 32 : 16; };
@@ -943,9 +944,11 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 // transform, phase B's view products (fr_preprocess_one<true>) and phase C's (fr_mean_rows_unit<true, true>) drop out, and with
 // them the 16 registers of the matrix; phases A and B stay bit-identical to the general instantiation.  The hint is checked: a
 // workgroup that finds another matrix in p.view raises the overflow flag (nothing is scored) and status[3] bit 1 (FisherScorer throws).
-template <int C, int AF, bool DK, bool IDV = false>
+// SLOTS (fr_fisher_point_views; score form only): the slot -> index table that the out_H forms write, and the slot's accumulator cleared.
+template <int C, int AF, bool DK, bool IDV = false, bool SLOTS = false>
 __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, FrRecordArgs ra)
 {
+	static_assert(!SLOTS || (AF == 0 && !IDV), "the slot table is an option of the general score form (the out_H forms always write it)");
 	static_assert((C == 4 || C == 11) && AF >= 0 && AF <= 4 && !((AF == 1 || AF >= 3) && C != 4), "records modes: score form, A-form (4 columns), general out_H form, pose form (4 columns), render form (4 columns)");
 	static_assert(!IDV || (C == 4 && AF == 0 && DK), "the identity-view front end is the 4-column score form's with fixed key segments");
 	constexpr int RS = FrRecStride<C, AF, DK>::value; // float4 per compact record
@@ -1311,7 +1314,8 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views_c(FrParams p, F
 					en.xy0 = park[10 * FR_THREADS + r]; en.xy1 = park[11 * FR_THREADS + r];
 					*(uint4*)(p.vis_list + ((size_t)v * nblk + blockIdx.x) * cap + (rk & 0xffffu)) = *(const uint4*)&en;
 				}
-				if constexpr (AF == 1 || AF == 2) ra.slot_idx[(size_t)v * PV + slot] = p.order ? p.order[idx] : idx;    // (the out_H kernels go back to the caller's index)
+				if constexpr (AF == 1 || AF == 2 || SLOTS) ra.slot_idx[(size_t)v * PV + slot] = p.order ? p.order[idx] : idx;    // (the out_H kernels go back to the caller's index)
+				if constexpr (SLOTS) ra.slot_acc[(size_t)v * PV + slot] = 0.f;
 			}
 		}
 		// what is left over moves to the front of the list
@@ -5199,6 +5203,203 @@ __global__ __launch_bounds__(FR_THREADS) void k_reduce_scores(const float* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Per-Gaussian view scores (fr_fisher_point_views): point[v, i] = sum_c cur_H[v, i, c] H_inv[(v,) i, c], the H_inv-contracted
+// diagonal of ONE view per (view, Gaussian) -- the `pointScores` of the reference's candidate scan (models/SLAM/gaussian.py:1285-1325).
+// The scorer's records already hold the contracted pair factor S_i = (opacity G_i)^2 (F_i(u) + k3_i); per Gaussian the contraction
+// is sum_pixels S_i (p_i - X b_i)^2, and X is known only at the end of a pixel: the two front-to-back passes of k_fisher_tile_v3h
+// (whole lists), with ONE double accumulator per candidate whatever the number of columns.
+//   records  the score form of the front end: 80 bytes with fixed key segments ({x, y, k3, log2 o} {recB} + 12 coefficients), 96 bytes
+//            with packed lists ({x, y, ext, log2 o} {recB} + 12 coefficients + {k3}); parked as the 80-byte form either way
+//            (pass 1 parks the first 32 bytes only)
+//   pass 2   val = con ? (a_un dLda)^2 (F(u) + k3) : 0, quad-combined, one ds_add_f64 per issuing lane; every lane also keeps its own
+//            running sum of val in double: lane -> wave -> workgroup in a fixed order gives tile_scores[v, t], so out_scores is
+//            reproducible and does not depend on the batch
+//   flush    per chunk lane l < m adds acc[l] dL^2 to the accumulator of its candidate's SLOT: one global float atomic per
+//            (strip, candidate) (the out_H kernels: 4 or 11).  Float atomic sums depend on arrival order: point[v, i] may differ in
+//            its last bits between two calls.
+// k_point_finish then walks the visible slots of every view: slot -> index, out_point_scores, unsigned atomicMax into out_point_max.
+template <bool DK, bool FULL>
+struct FrParkPoint {
+	__device__ __forceinline__ unsigned long long operator()(const float4* __restrict__ rec, size_t sA, const float4*, size_t,
+	                                                         uint32_t id, float4* e, float strip_lo, float tile_x0) const
+	{
+		const float4* r = rec + sA * id;
+		const float4 a = r[0], b4 = r[1];
+		e[1] = b4;
+		if constexpr (FULL) { e[2] = r[2]; e[3] = r[3]; e[4] = r[4]; }
+		if constexpr (DK)
+		{
+			// no extents in the 80-byte record: the footprint rows come from the conic alone (k_fisher_tile_v4's rule)
+			e[0] = a;
+			return (unsigned long long)fr_footprint_rows2(a, b4, strip_lo, tile_x0) |
+			       ((unsigned long long)fr_footprint_rows2(a, b4, strip_lo + 2.0f, tile_x0) << 32);
+		}
+		else
+		{
+			if constexpr (FULL) e[0] = make_float4(a.x, a.y, r[5].x, a.w);      // k3 takes the place of the extents, which only the footprint needs
+			else e[0] = a;
+			return fr_footprint_mask<16, 4>(a, b4, strip_lo, tile_x0);
+		}
+	}
+};
+// F(u) + k3 of one pair from the parked 80-byte record: fr_walk_geom's Horner evaluation (u = -conic d)
+__device__ __forceinline__ float fr_point_poly(const FrWalkRec3& r, float dx, float dy)
+{
+#pragma clang fp contract(fast)
+	const float ux = __builtin_fmaf(r.b4.x, dx, __builtin_fmaf(r.b4.x, dx, r.b4.y * dy));
+	const float uy = __builtin_fmaf(2.0f * r.b4.z, dy, r.b4.y * dx);
+	const float A0 = r.q0.x + uy * (r.q0.y + uy * r.q0.z);
+	const float A1 = r.q0.w + uy * (r.q1.x + uy * r.q1.y);
+	const float A2 = r.q1.z + uy * (r.q1.w + uy * r.q2.x);
+	const float A3 = r.q2.y + uy * r.q2.z;
+	const float uy2 = uy * uy;
+	const float in3 = A3 + ux * r.q2.w;
+	const float in2 = A2 + ux * in3;
+	const float in1 = uy * A1 + ux * in2;
+	return (r.a.z + uy2 * A0) + ux * in1;
+}
+// Waves per SIMD: 66 registers and 24.6 KB of LDS allow six workgroups per CU.  Measured on the 64-view benchmark call (500k Gaussians,
+// 4 / 11 columns, whole launch sequence): 2.64 / 2.83 ms capped at 4 as k_fisher_tile_v3h is, 2.32 / 2.52 ms at 6 -- the walk is a chain of
+// dependent LDS reads and arithmetic, more waves hide more of it (tools/build_variant.sh pw4 -UFR_AB -DFR_POINT_WAVES=4).
+#ifndef FR_POINT_WAVES
+#define FR_POINT_WAVES 6
+#endif
+template <bool DK>
+__global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(4, FR_POINT_WAVES)))
+void k_fisher_point_tile(FrParams p, FrFisherArgs f, float* __restrict__ slot_acc)
+{
+	__shared__ uint32_t s_q[4][FR_QCAP];
+	__shared__ float4 s_ent[4][64][FR_ENT3_F4];
+	__shared__ double s_acc[4][64];
+	__shared__ double s_red[4];
+	if (p.status[1]) return;
+	const int tid = threadIdx.x, lane = tid & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	uint32_t tile; int v;
+	fr_tile_of_block(p, tile, v);
+	const uint32_t tx = tile % p.gx, ty = tile / p.gx;
+	const uint32_t bx0 = tx * FR_BLOCK_X, by0 = ty * FR_BLOCK_Y + (uint32_t)wave * 4u;
+	const uint32_t pxx = bx0 + (uint32_t)(lane & 15), pxy = by0 + (uint32_t)(lane >> 4);
+	const bool inside = pxx < (uint32_t)p.W && pxy < (uint32_t)p.H;
+	const float pfx = (float)pxx, pfy = (float)pxy;
+	const size_t vt = (size_t)v * p.T + tile;
+	const uint32_t n = p.tile_cnt[vt];
+	const uint64_t* gk = p.keys + p.tile_off[vt];
+	const float4* rec = f.recA + (size_t)v * f.ab_view;
+	const size_t sA = (size_t)f.ab_stride;
+	uint32_t* wq = s_q[wave];
+	float4 (*ent)[FR_ENT3_F4] = s_ent[wave];
+	double* acc = s_acc[wave];
+	const uint32_t ent_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)&s_ent[wave][0][0];
+	const float strip_lo = (float)by0, tile_x0 = (float)bx0;
+
+	// ---- pass 1 (k_fisher_tile_v3h's): X
+	float T = 1.0f;
+	double Cg = 0.0;
+	bool done = !inside;
+	auto pass1 = [&](uint32_t, uint32_t, unsigned long long emask) {
+		unsigned long long mask = fr_wave_transpose64(emask, lane);
+		if (done) mask = 0ull;
+		while (mask != 0ull)
+		{
+			const int j = __ffsll((long long)mask) - 1;
+			mask &= mask - 1ull;
+			const uint32_t addr = ent_lds + (uint32_t)j * (FR_ENT3_F4 * 16);
+			fr_v4f a, b4;
+			asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)" : "=&v"(a), "=&v"(b4) : "v"(addr) : "memory");
+			const FrPairAlpha g = fr_pair_alpha(a, b4, pfx, pfy);
+			bool con;
+			if (fr_prefix_update(g, b4.w, T, Cg, con)) { mask = 0ull; done = true; }
+		}
+	};
+	fr_strip_pass<16, 4, 0, decltype(pass1), FR_ENT3_F4, FrParkPoint<DK, false>>(gk, n, rec, sA, nullptr, 0, wq, ent, lane, strip_lo, tile_x0, f.key_shift, wave, done, pass1);
+	const double X = Cg + (double)(T * (p.bg[0] + p.bg[1] + p.bg[2]));
+
+	// ---- pass 2: the same recurrences (hence the same contributors), the pair's contracted square
+	T = 1.0f; Cg = 0.0; done = !inside;
+	const float dL2 = f.dL * f.dL;
+	float* dst = slot_acc + (size_t)v * (size_t)f.slot_view;
+	double lsum = 0.0;
+	auto pass2 = [&](uint32_t m, uint32_t my_id, unsigned long long emask) {
+		acc[lane] = 0.0;
+		unsigned long long mask = fr_wave_transpose64(emask, lane);
+		if (done) mask = 0ull;
+		while (mask != 0ull)
+		{
+			const int j = __ffsll((long long)mask) - 1;
+			mask &= mask - 1ull;
+			const uint32_t addr = ent_lds + (uint32_t)j * (FR_ENT3_F4 * 16);
+			FrWalkRec3 r;
+			asm volatile("ds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:16\n\tds_read_b128 %2, %5 offset:32\n\t"
+			             "ds_read_b128 %3, %5 offset:48\n\tds_read_b128 %4, %5 offset:64\n\t"
+			             "s_waitcnt lgkmcnt(0)"
+			             : "=&v"(r.a), "=&v"(r.b4), "=&v"(r.q0), "=&v"(r.q1), "=&v"(r.q2) : "v"(addr) : "memory");
+			const FrPairAlpha g = fr_pair_alpha(r.a, r.b4, pfx, pfy);
+			const float T_i = T;
+			bool con;
+			const bool kill = fr_prefix_update(g, r.b4.w, T, Cg, con);
+			float h[1];
+			{
+#pragma clang fp contract(fast)
+				const float bi = __builtin_amdgcn_rcpf(g.om1);
+				const float dLda = T_i * r.b4.w - (float)(X - Cg) * bi;           // as k_fisher_tile_v3h writes it
+				const float w = g.a_un * dLda;
+				h[0] = con ? (w * w) * fr_point_poly(r, g.dx, g.dy) : 0.f;
+			}
+			lsum += (double)h[0];
+			const bool issue = fr_quad_combine<1>(con ? j : -1, h, lane);
+			FR_ABL(if (f.debug_mode != 29))
+			if (issue) atomicAdd(&acc[j], (double)h[0]);
+			if (kill) { mask = 0ull; done = true; }
+		}
+		__builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's own ds_add instructions have retired
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		// flush: one float atomic per (strip, candidate), to the candidate's slot
+		const float a = ((uint32_t)lane < m) ? (float)acc[lane] * dL2 : 0.f;
+		FR_ABL(if (f.debug_mode != 28))       // 28: the walk without its global atomics
+		if (a != 0.f) atomicAdd(dst + my_id, a);
+		__builtin_amdgcn_wave_barrier();
+	};
+	fr_strip_pass<16, 4, 3, decltype(pass2), FR_ENT3_F4, FrParkPoint<DK, true>>(gk, n, rec, sA, nullptr, 0, wq, ent, lane, strip_lo, tile_x0, f.key_shift, wave, done, pass2);
+	// the view's score: lanes -> wave -> workgroup, always in this order
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o, 64);
+	if (lane == 0) s_red[wave] = lsum;
+	__syncthreads();
+	if (tid == 0) f.tile_scores[vt] = (float)(((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) * (double)dL2);
+}
+
+// out_point_scores = 0 unless the call overflowed (then no output byte changes)
+__global__ __launch_bounds__(FR_THREADS) void k_point_clear(float* __restrict__ out, unsigned long long n, const int* __restrict__ status)
+{
+	if (status[1]) return;
+	for (unsigned long long i = (unsigned long long)blockIdx.x * FR_THREADS + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * FR_THREADS) out[i] = 0.f;
+}
+// One workgroup per 256 slots of a (view, projection workgroup): the visible ones (vis_n) go back to their Gaussian's index.  The sums
+// are non-negative up to the rounding of the polynomial; a negative one (or -0) is written as +0, so that the maximum can be taken on
+// the bit patterns -- exact and independent of the order.
+__global__ __launch_bounds__(FR_THREADS) void k_point_finish(int P, int V, uint32_t nblk, uint32_t cap, const uint32_t* __restrict__ vis_n,
+                                                             const uint32_t* __restrict__ slot_idx, const float* __restrict__ slot_acc,
+                                                             float* __restrict__ out_point_scores, uint32_t* __restrict__ out_point_max,
+                                                             const int* __restrict__ status)
+{
+	if (status[1]) return;
+	const uint32_t per = cap / FR_THREADS;                       // workgroups per projection workgroup
+	const uint32_t per_view = nblk * per;
+	const uint32_t v = blockIdx.x / per_view, w = blockIdx.x % per_view;
+	const uint32_t b = w / per, r = (w % per) * FR_THREADS + threadIdx.x;
+	if (v >= (uint32_t)V || r >= vis_n[(size_t)v * nblk + b]) return;
+	const size_t slot = (size_t)v * nblk * cap + (size_t)b * cap + r;
+	const uint32_t idx = slot_idx[slot];
+	if (idx >= (uint32_t)P) return;
+	const float s0 = slot_acc[slot];
+	const float s = s0 > 0.f ? s0 : 0.f;
+	if (out_point_scores) out_point_scores[(size_t)v * P + idx] = s;
+	if (out_point_max && s > 0.f) atomicMax(&out_point_max[idx], __float_as_uint(s));
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Generic fused backward of ONE view with grad_power (renderCUDAFused, backward.cu:850-1140).
 struct FrBwdArgs {
 	const float* dL_dpix;        // [3][H][W]
@@ -7096,7 +7297,8 @@ struct FrJoinGuard {
 
 // Score-only mode: the front end also produces the scorer's per-(view, Gaussian) records (k_pack_static, then phase C of
 // k_preprocess_views; with the single-view front end, k_fisher_records after k_scatter_keys, beside the sorts, on the second side stream).
-struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; bool pose = false; bool view_identity = false; bool render = false; };   // render: the 48-byte records of k_render_views_tile (fr_render_views)   // view_identity: fr_fisher_cfg.view_is_identity   // pose: the records of k_fisher_pose_tile (fr_fisher_pose_views)   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
+struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; bool pose = false; bool view_identity = false; bool render = false; bool point = false; };   // point: score form + slot table + cleared accumulators (fr_fisher_point_views)
+//   // render: the 48-byte records of k_render_views_tile (fr_render_views)   // view_identity: fr_fisher_cfg.view_is_identity   // pose: the records of k_fisher_pose_tile (fr_fisher_pose_views)   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
 template <int C> __global__ void k_pack_static(FrParams p, const float* __restrict__ H_inv, float* __restrict__ packed, float4* __restrict__ mt, float4* __restrict__ grp);
 template <int C, bool LIST, bool FORM_A> __global__ void k_fisher_records(FrParams p, FrRecordArgs ra);
 
@@ -7164,6 +7366,10 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 		else if (once && plan->general) hipLaunchKernelGGL((k_preprocess_views_c<11, 2, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->form_a && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 1, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->form_a) hipLaunchKernelGGL((k_preprocess_views_c<4, 1, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->point && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, true, false, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->point && plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, false, false, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->point && dk) hipLaunchKernelGGL((k_preprocess_views_c<11, 0, true, false, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+		else if (once && plan->point) hipLaunchKernelGGL((k_preprocess_views_c<11, 0, false, false, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->columns == 4 && dk && plan->view_identity) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, true, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
 		else if (once && plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
@@ -8394,6 +8600,165 @@ extern "C" int fr_render_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	if (out_features) hipLaunchKernelGGL((k_render_views_tile<6>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, out_color, out_features, out_depth, out_final_T, (int*)status);
 	else hipLaunchKernelGGL((k_render_views_tile<3>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, out_color, out_features, out_depth, out_final_T, (int*)status);
 	return fr_check_launch("k_render_views_tile");
+}
+
+// ---- per-Gaussian view scores and their running maximum (fr_fisher_point_views) -------------------------------------------
+// The scorer's workspace and behind it the per-slot accumulators f32 [V][PV].
+static size_t fr_point_total(int64_t P, int64_t W, int64_t H, int64_t V, int64_t max_rendered, int columns)
+{
+	const FrFisherLayout L = fr_fisher_layout(P, W, H, V, max_rendered, columns);
+	return fr_align(L.total + (size_t)V * L.PV * 4);
+}
+
+extern "C" size_t fr_fisher_point_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns)
+{
+	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0 || (columns != 4 && columns != 11)) return 0;
+	if ((long long)((W + 15) / 16) * ((H + 15) / 16) > FR_MAX_LDS_TILES) return 0;
+	return fr_point_total(P, W, H, n_views, max_rendered, columns);
+}
+
+extern "C" int fr_fisher_point_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns, size_t o[9])
+{
+	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0 || (columns != 4 && columns != 11) || !o ||
+	    (long long)((W + 15) / 16) * ((H + 15) / 16) > FR_MAX_LDS_TILES)
+		return fr_fail(FR_EINVAL, "fr_fisher_point_workspace_layout: bad argument");
+	const FrFisherLayout L = fr_fisher_layout(P, W, H, n_views, max_rendered, columns);
+	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+	o[8] = L.total;
+	return FR_OK;
+}
+
+extern "C" int fr_fisher_point_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* fc,
+                                     float* out_point_scores, float* out_point_max,
+                                     void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream)
+{
+	// every argument check comes before any device work
+	int rc = fr_validate(cfg, g, "fr_fisher_point_views");
+	if (rc) return rc;
+	if (!fc || fc->n_views <= 0 || !fc->w2c || !status) return fr_fail(FR_EINVAL, "fr_fisher_point_views: bad fisher cfg or null status");
+	if (fc->columns != 4 && fc->columns != 11) return fr_fail(FR_EINVAL, "fr_fisher_point_views: columns must be 4 or 11");
+	if (fc->out_H) return fr_fail(FR_EINVAL, "fr_fisher_point_views: out_H is for fr_fisher_views");
+	if (fc->dL_dpix_image) return fr_fail(FR_EINVAL, "fr_fisher_point_views: no per-pixel upstream-gradient images (constant dL_dpix only)");
+	if (fc->reuse_static) return fr_fail(FR_EINVAL, "fr_fisher_point_views: reuse_static is not supported");
+	if (!fc->H_inv) return fr_fail(FR_EINVAL, "fr_fisher_point_views: needs H_inv");
+	if (!out_point_scores && !out_point_max) return fr_fail(FR_EINVAL, "fr_fisher_point_views: no output requested");
+	if (!g->colors_precomp) return fr_fail(FR_EINVAL, "fr_fisher_point_views: needs colors_precomp");
+	if (g->cov3D_precomp || !(g->scales && g->rotations)) return fr_fail(FR_EINVAL, "fr_fisher_point_views: needs scales and rotations (no cov3D_precomp)");
+	if (fc->tile_capacity < 0) return fr_fail(FR_EINVAL, "fr_fisher_point_views: negative tile_capacity");
+	if (max_rendered < 0) return fr_fail(FR_EINVAL, "fr_fisher_point_views: negative max_rendered");
+	const int P = cfg->P, W = cfg->image_width, H = cfg->image_height, V = fc->n_views, C = fc->columns;
+	const long long Tt = (long long)((W + 15) / 16) * ((H + 15) / 16);
+	if (Tt > FR_MAX_LDS_TILES) return fr_fail(FR_EINVAL, "fr_fisher_point_views: images beyond 4096 tiles are not supported");
+	if (fc->tile_capacity > 0)
+	{
+		const long long need = (long long)V * Tt * (long long)fc->tile_capacity;
+		if (need > max_rendered || need >= (1ll << 32)) return fr_fail(FR_EINVAL, "fr_fisher_point_views: n_views * tiles * tile_capacity exceeds max_rendered (or 2^32)");
+	}
+	hipStream_t s = (hipStream_t)stream;
+	if (P == 0)
+	{
+		if (fc->out_scores) (void)hipMemsetAsync(fc->out_scores, 0, (size_t)V * 4, s);
+		if (fc->out_vis_count) (void)hipMemsetAsync(fc->out_vis_count, 0, (size_t)V * 4, s);
+		if (fc->out_num_rendered) (void)hipMemsetAsync(fc->out_num_rendered, 0, (size_t)V * 4, s);
+		(void)hipMemsetAsync(status, 0, 16, s);
+		return fr_check_launch("fr_fisher_point_views (no Gaussians)");
+	}
+	const FrFisherLayout L = fr_fisher_layout(P, W, H, V, max_rendered, C);
+	if (!workspace || workspace_bytes < fr_point_total(P, W, H, V, max_rendered, C))
+		return fr_fail(FR_ENOSPACE, "fr_fisher_point_views: workspace smaller than fr_fisher_point_workspace_bytes()");
+	const long long G = fr_pick_G_views(P);
+	const long long nblk_c = (P + FR_THREADS * G - 1) / (FR_THREADS * G);
+	if ((long long)V * nblk_c * G >= (1ll << 31)) return fr_fail(FR_EINVAL, "fr_fisher_point_views: too many (view, slot) groups for one launch");
+	char* ws = (char*)workspace;
+	FrParams p;
+	fr_fill_params(p, cfg, g, V);
+	p.prefiltered = 0;
+	p.w2c = fc->w2c;
+	if (fc->poses_are_c2w)
+	{
+		float* inv = (float*)(ws + L.w2c_inv);
+		hipLaunchKernelGGL(k_invert_poses, dim3((V + 63) / 64), dim3(64), 0, s, V, fc->w2c, inv);
+		if ((rc = fr_check_launch("k_invert_poses"))) return rc;
+		p.w2c = inv;
+	}
+	p.radii = (int*)(ws + L.radii);
+	p.vis_list = (FrVisEntry*)(ws + L.radii);
+	p.vis_n = (uint32_t*)(ws + L.vis_n);
+	p.splat = (FrSplat*)(ws + L.splat);
+	p.cov3D_out = (float*)(ws + L.cov3D);
+	p.tile_cnt = (uint32_t*)(ws + L.tile_cnt);
+	p.tile_off = (uint32_t*)(ws + L.tile_off);
+	p.tile_fill = (uint32_t*)(ws + L.tile_fill);
+	p.status = (int*)(ws + L.status);
+	p.big_list = (uint32_t*)(ws + L.big_list);
+	p.part_list = (uint32_t*)(ws + L.part_list);
+	const bool deal = (V & 7) == 0 && V <= 1024;
+	p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
+	p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;
+	p.blk_base = (uint32_t*)(ws + L.blk_base);
+	p.keys = (uint64_t*)(ws + L.keys);
+	p.key_capacity = max_rendered;
+	if (fc->tile_capacity > 0)
+	{
+		// fixed key segments where the compact-record front end can address them (as fr_fisher_views decides it)
+		const bool slots_fit = nblk_c * FR_THREADS * G < (1ll << 28);
+		if (p.gx <= 255u && p.gy <= 63u && slots_fit) p.tile_cap = (uint32_t)fc->tile_capacity;
+	}
+	(void)fr_plan_views_c(p.T, fr_pick_VC(p.T), p.tile_cap);
+	p.vis_count = fc->out_vis_count;
+	p.num_rendered = fc->out_num_rendered;
+	p.order = fc->order;
+	const int rstride = p.tile_cap ? 5 : 6;            // the score form: 80 bytes with fixed key segments, else 96
+	float* slot_acc = (float*)(ws + L.total);
+	FrScorerPlan plan;
+	plan.columns = C;
+	plan.form_a = false;
+	plan.point = true;
+	plan.ra.H_inv = fc->H_inv; plan.ra.hinv_stride = fc->H_inv_view_stride;
+	plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
+	plan.ra.comp = (float4*)(ws + L.recq);
+	plan.ra.stride = rstride;
+	plan.ra.slot_idx = (uint32_t*)(ws + L.slot_idx);
+	plan.ra.slot_acc = slot_acc;
+	plan.ra.mt = (const float4*)(ws + L.mt);
+	plan.ra.grp = (const float4*)(ws + L.grp);
+	plan.ra.early = 1;
+	FrFisherArgs f;
+	memset(&f, 0, sizeof(f));
+	f.dL = fc->dL_dpix;
+	f.tile_scores = (float*)(ws + L.tile_scores);
+	f.debug_mode = fr_debug_mode();
+	f.recA = plan.ra.comp; f.ab_view = (long long)L.PV * rstride; f.ab_stride = rstride;
+	f.slot_idx = plan.ra.slot_idx; f.slot_view = (long long)L.PV;
+	if ((rc = fr_bin_pipeline(p, g, s, &plan))) return rc;
+	if ((p.tile_cap ? 5 : 6) != rstride) return fr_fail(FR_EINVAL, "fr_fisher_point_views: the front end left the planned key form");
+	f.key_shift = p.tile_cap ? 4 : 0;                   // (fixed segments: keys = depth | slot << 4 | strips)
+	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	if (g_prof_on)
+	{
+		(void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
+		(void)hipEventRecord(ev0, s);
+	}
+	if (p.tile_cap) hipLaunchKernelGGL((k_fisher_point_tile<true>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, slot_acc);
+	else hipLaunchKernelGGL((k_fisher_point_tile<false>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, slot_acc);
+	if (g_prof_on)
+	{
+		(void)hipEventRecord(ev1, s);
+		g_prof_events.push_back(std::make_pair(ev0, ev1));
+	}
+	if ((rc = fr_check_launch("k_fisher_point_tile"))) return rc;
+	if (out_point_scores)
+	{
+		const unsigned long long n = (unsigned long long)V * (unsigned long long)P;
+		const unsigned long long blocks = (n + FR_THREADS * 4 - 1) / (FR_THREADS * 4);
+		hipLaunchKernelGGL(k_point_clear, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(FR_THREADS), 0, s, out_point_scores, n, (const int*)p.status);
+		if ((rc = fr_check_launch("k_point_clear"))) return rc;
+	}
+	hipLaunchKernelGGL(k_point_finish, dim3((unsigned)((long long)V * nblk_c * G)), dim3(FR_THREADS), 0, s, P, V, (uint32_t)nblk_c, (uint32_t)(FR_THREADS * G),
+	                   (const uint32_t*)p.vis_n, (const uint32_t*)plan.ra.slot_idx, (const float*)slot_acc, out_point_scores, (uint32_t*)out_point_max, (const int*)p.status);
+	if ((rc = fr_check_launch("k_point_finish"))) return rc;
+	hipLaunchKernelGGL(k_reduce_scores, dim3(fc->out_scores ? V : 1), dim3(FR_THREADS), 0, s, f.tile_scores, p.T, p.status, 1, fc->out_scores, status);
+	return fr_check_launch("k_reduce_scores");
 }
 
 // =========================================================================================================

@@ -89,6 +89,7 @@ EXPORTS = (
     "fr_forward", "fr_backward", "fr_backward_scratch_bytes", "fr_backward_ws", "fr_forward_pair", "fr_forward_features", "fr_backward_pair", "fr_backward_pair_scratch_bytes", "fr_backward_pair_ws", "fr_fisher_workspace_bytes", "fr_fisher_views",
     "fr_fisher_pose_workspace_bytes", "fr_fisher_pose_workspace_layout", "fr_fisher_pose_views",
     "fr_render_views_workspace_bytes", "fr_render_views_workspace_layout", "fr_render_views",
+    "fr_fisher_point_workspace_bytes", "fr_fisher_point_workspace_layout", "fr_fisher_point_views",
     "fr_popgs_diag_criterion_workspace_bytes", "fr_popgs_diag_criterion",
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
@@ -216,6 +217,16 @@ def load():
         lib.fr_render_views.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.POINTER(FisherCfg),
                                         _f32p, _f32p, _f32p, _f32p,
                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+    if hasattr(lib, "fr_fisher_point_views"):
+        lib.fr_fisher_point_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_fisher_point_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                        ctypes.c_int32]
+        lib.fr_fisher_point_workspace_layout.restype = ctypes.c_int
+        lib.fr_fisher_point_workspace_layout.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                         ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+        lib.fr_fisher_point_views.restype = ctypes.c_int
+        lib.fr_fisher_point_views.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.POINTER(FisherCfg), _f32p, _f32p,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
     if hasattr(lib, "fr_popgs_diag_criterion"):
         lib.fr_popgs_diag_criterion_workspace_bytes.restype = ctypes.c_size_t
         lib.fr_popgs_diag_criterion_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64]

@@ -215,13 +215,21 @@ def _all_reduce(t: torch.Tensor, op, group=None):
         dist.all_reduce(t, op=op, group=group)
 
 
-def sharded_point_score_max(scorer, w2c_all: torch.Tensor, H_inv: torch.Tensor, group=None, chunk: int = 16) -> torch.Tensor:
+def sharded_point_score_max(scorer, w2c_all: torch.Tensor, H_inv: torch.Tensor, group=None, chunk: int = 16, fused: bool = False) -> torch.Tensor:
     """max over the candidate views of every Gaussian's score sum_c cur_H[v, i, c] * H_inv[i, c] -- the `max_points_score`
-    the reference keeps while it scans the candidates (gaussian.py:1284-1303).  Views sharded, ONE all-reduce(MAX) on [P]."""
+    the reference keeps while it scans the candidates (gaussian.py:1284-1303).  Views sharded, ONE all-reduce(MAX) on [P].
+    `fused`: this rank's views go through `scorer.point_scores` (fr_fisher_point_views: one accumulator per (view, Gaussian), no
+    [chunk, P, columns] tensor; `chunk` is then the scorer's own).  Off by default: the route and the results of before."""
     rank, world = _world(group)
     V = int(w2c_all.shape[0])
     lo, hi = shard_bounds(V, rank, world)
     best = torch.zeros((scorer.P,), dtype=torch.float32, device=w2c_all.device)       # the reference starts from zeros
+    if fused:
+        if hi > lo:
+            scorer.point_scores(w2c_all[lo:hi], H_inv, per_view=False, point_max=best)
+        if _collective(world):
+            _all_reduce(best, dist.ReduceOp.MAX, group)
+        return best
     for v0 in range(lo, hi, chunk):
         w = w2c_all[v0:min(hi, v0 + chunk)]
         cur = torch.zeros((int(w.shape[0]), scorer.P, scorer.columns), dtype=torch.float32, device=w2c_all.device)

@@ -740,6 +740,109 @@ class FisherScorer:
         return {k: (torch.cat([o[k] for o in outs]) if outs[0][k] is not None else None) for k in names}
 
 
+    # -- per-Gaussian view scores and their running maximum (fr_fisher_point_views) -----------------------
+    def point_launch(self, w2c, H_inv, H_inv_per_view=False, per_view=True, out=None, point_max=None, poses_are_c2w=False):
+        """Enqueue one batch of per-Gaussian view scores (no sync): point[v, i] = sum_c cur_H[v, i, c] H_inv[(v,) i, c], the
+        `pointScores` of the reference's candidate scan (models/SLAM/gaussian.py:1285-1325), without a [V, P, columns] tensor.
+        Returns a dict of device tensors: point_scores [V,P] (`per_view`; `out` when given), point_max [P] (`point_max` when given --
+        the running maximum is taken INTO it, so it composes over calls; a fresh one starts from zeros, as the reference does),
+        scores [V], vis_count [V], num_rendered [V], status [4].  On overflow (status[1]) no output byte is written.
+        Its own workspace, as `pose_launch`: the packed static records of `launch` stay where they are."""
+        d = self.dev
+        w2c = _prep(w2c.reshape(-1, 4, 4), d)
+        V = int(w2c.shape[0])
+        P, PC = self.P, self.P * self.columns
+        if H_inv is None:
+            raise ValueError("point_launch needs H_inv")
+        want = (V * PC) if H_inv_per_view else PC
+        if H_inv.numel() != want:
+            raise ValueError(f"H_inv has {H_inv.numel()} elements, expected {want}")
+        H_inv = _prep(H_inv, d)
+
+        def given(t, n, name):
+            if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous() or t.device != d:
+                raise ValueError(f"{name} must be a contiguous fp32 device tensor of {n} elements")
+            return t
+        point = None
+        if out is not None:
+            point = given(out, V * P, "out").view(V, P)
+        elif per_view:
+            point = torch.empty((V, P), dtype=torch.float32, device=d)        # every element is written (or the status word says overflow)
+        pmax = given(point_max, P, "point_max") if point_max is not None else torch.zeros((P,), dtype=torch.float32, device=d)
+        scores = torch.empty((V,), dtype=torch.float32, device=d)
+        vis = torch.empty((V,), dtype=torch.int32, device=d)
+        nr = torch.empty((V,), dtype=torch.int32, device=d)
+        status = torch.empty((4,), dtype=torch.int32, device=d)
+        max_rendered = V * self._keys_per_view()
+        nbytes = int(self.lib.fr_fisher_point_workspace_bytes(P, self.W, self.H, V, max_rendered, self.columns))
+        if nbytes == 0:
+            raise FisherRastError("fr_fisher_point_workspace_bytes: bad argument (or an image beyond 4096 tiles)")
+        ws = self._ws.get("point")
+        if ws is None or ws.numel() < nbytes:
+            self._ws["point"] = None
+            ws = self._ws["point"] = torch.empty((nbytes,), dtype=torch.uint8, device=d)
+        self._sync_order()
+        fc = FisherCfg()
+        fc.n_views, fc.columns, fc.dL_dpix = V, self.columns, self.dL
+        fc.poses_are_c2w = 1 if poses_are_c2w else 0
+        fc.tile_capacity = self.tile_capacity if V * self.tiles * self.tile_capacity < (1 << 32) else 0
+        fc.w2c = ctypes.c_void_p(w2c.data_ptr())
+        fc.H_inv = ctypes.c_void_p(H_inv.data_ptr())
+        fc.H_inv_view_stride = PC if H_inv_per_view else 0
+        fc.out_scores = ctypes.c_void_p(scores.data_ptr())
+        fc.out_vis_count = vis.data_ptr()
+        fc.out_num_rendered = nr.data_ptr()
+        fc.order = self.order.data_ptr() if self.order is not None else None
+        with torch.cuda.device(d):
+            _lib.check(self.lib.fr_fisher_point_views(ctypes.byref(self.cfg), ctypes.byref(self.g), ctypes.byref(fc),
+                                                      _ptr(point), _ptr(pmax), ws.data_ptr(), ws.numel(), max_rendered,
+                                                      status.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)),
+                       "fr_fisher_point_views")
+        return dict(point_scores=point, point_max=pmax, scores=scores, vis_count=vis, num_rendered=nr, status=status, n_views=V,
+                    _keep=(w2c, H_inv))
+
+    def point_scores(self, w2c, H_inv, H_inv_per_view=False, per_view=True, point_max=None, poses_are_c2w=False):
+        """Per-Gaussian scores of every view and their maximum over the views (include/fisher_rast.h, fr_fisher_point_views).
+        Returns dict(scores [V], point_max [P], point_scores [V,P] (when `per_view`), vis_count [V], num_rendered [V]) on the device.
+        `point_max`: a [P] fp32 device tensor of non-negative values to take the maximum into (default: zeros).  Views beyond
+        `max_views_per_launch()` go in several calls into the same maximum; an overflow of the key buffer is redone with a larger one,
+        as in `pose_fisher` (nothing was written): one status read per chunk."""
+        d = self.dev
+        w2c = w2c.reshape(-1, 4, 4)
+        V, P = int(w2c.shape[0]), self.P
+        if point_max is None:
+            point_max = torch.zeros((P,), dtype=torch.float32, device=d)
+        point = torch.empty((V, P), dtype=torch.float32, device=d) if per_view else None
+        chunk = self.max_views_per_launch()
+        outs = []
+        v0 = 0
+        while v0 < V:
+            v1 = min(V, v0 + chunk)
+            while True:
+                hi = H_inv.reshape(V, -1)[v0:v1] if H_inv_per_view else H_inv
+                r = self.point_launch(w2c[v0:v1], hi, H_inv_per_view, per_view, point[v0:v1] if per_view else None, point_max, poses_are_c2w)
+                st = r["status"].cpu()
+                if int(st[1]) == 0:
+                    break
+                # overflow: nothing was written -- grow the key buffer (or the fixed segments) and redo this chunk
+                if int(st[3]):
+                    want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
+                    self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0
+                self.per_view_capacity = max(self.per_view_capacity, int(int(st[0]) * 1.25 / (v1 - v0)) + 4096)
+                chunk = min(chunk, self.max_views_per_launch())
+                v1 = min(v1, v0 + chunk)
+            outs.append(r)
+            v0 = v1
+
+        def cat(k, dtype):
+            return torch.cat([o[k] for o in outs]) if outs else torch.zeros((0,), dtype=dtype, device=d)
+        res = dict(scores=cat("scores", torch.float32), point_max=point_max, vis_count=cat("vis_count", torch.int32),
+                   num_rendered=cat("num_rendered", torch.int32))
+        if per_view:
+            res["point_scores"] = point
+        return res
+
+
 def spatial_order_of(means3D: torch.Tensor) -> torch.Tensor:
     """fr_spatial_order: int32 [P], entry k = index of the k-th Gaussian along the Z-curve of the means (stable for equal codes)."""
     _need_gpu(means3D, "means3D")

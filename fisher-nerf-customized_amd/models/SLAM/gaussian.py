@@ -5,6 +5,7 @@ In scope (same names, arguments and return conventions as the reference):
     compute_Hessian (1503-1570)   compute_H_train (1338-1348)   pose_eval (1354-1375)
     render_at_pose (555-579)      gs_pts_cnt (1350-1352)        gaussian_points / cur_frame_idx (1590-1598)
     render_at_poses (new: render_at_pose for a batch of poses in one call, RenderOps)
+    pose_eval_points (new: the candidate scan of global_planning, 1285-1316 -- per-Gaussian scores and their running maximum, PointScoreOps)
     pause / resume / color_refinement / stop (1600-1614)
 The SLAM loop itself (init, track_rgbd, densify, keyframe selection ...) is NOT rebuilt: it is reference
 Python that stays as it is.  `FisherOps.install(cls)` grafts the accelerated methods onto the reference class
@@ -310,7 +311,40 @@ class RenderOps:
         return target_cls
 
 
-class GaussianSLAM(FisherOps, PoseFisherOps, RenderOps):
+class PointScoreOps:
+    """Mixin with the per-Gaussian scores of candidate poses (fr_fisher_point_views, include/fisher_rast.h): the candidate scan of
+    the reference's `global_planning` (models/SLAM/gaussian.py:1285-1316) -- `pointScores = sum(cur_H * H_train_inv, dim=1)` per
+    candidate and the running `max_points_score` that `prune_invisible` reads -- in one batched call, without a [V, P, columns]
+    tensor.  `pose_eval` itself stays as it is; this is a new name.  Needs FisherOps' `_scorer` / `_stack_poses` / `compute_H_train`
+    (install FisherOps first)."""
+
+    def pose_eval_points(self, poses, random_gaussian_params=None, per_view=False):
+        """(scores cpu fp32 [V], stack(c2w) [V,4,4], max_points_score [P] on the device[, point_scores [V,P] with `per_view`]) for
+        V camera-to-world poses (tensor, array or list).  scores are `pose_eval`'s (the sum over the Gaussians of a view's point
+        scores), with the same 1 / (H_train + H_TRAIN_REG) -- the one `pose_eval` keeps while map and keyframes are unchanged is
+        used when it is there.  max_points_score starts from zeros, as the reference's does.  Habitat's navigability filter of the
+        reference loop stays the caller's: pass the poses that survive it."""
+        extra = random_gaussian_params if self.FISHER_COLUMNS == 11 else None
+        c2w = self._stack_poses(poses)
+        scorer = self._scorer(extra)
+        cached = getattr(self, "_h_inv_cache", None)
+        if cached is not None and cached[0] is scorer and self._same_keyframes(cached[1], self._keyframe_key()):
+            H_inv = cached[2]
+        else:
+            H_inv = torch.reciprocal(self.compute_H_train(extra) + self.H_TRAIN_REG)
+        res = scorer.point_scores(c2w, H_inv, per_view=per_view, poses_are_c2w=True)
+        out = (res["scores"].cpu(), c2w, res["point_max"])
+        return out + (res["point_scores"],) if per_view else out
+
+    @classmethod
+    def install(cls, target_cls):
+        """Graft the method onto the reference's class (after FisherOps.install / ObjectFisherOps.install)."""
+        for name in ("pose_eval_points",):
+            setattr(target_cls, name, getattr(cls, name))
+        return target_cls
+
+
+class GaussianSLAM(FisherOps, PoseFisherOps, RenderOps, PointScoreOps):
     """Standalone carrier of the operator surface: a Gaussian map (param dict), a camera and keyframes."""
 
     def __init__(self, config=None, params=None, intrinsics=None, width=None, height=None, device="cuda"):

@@ -31,6 +31,8 @@
  *   fr_render_views      <- the render_at_pose(c2w) calls inside the candidate loops of pose_eval_popgs / pose_eval_popgs_blocks
  *                           (models/SLAM/gaussian_object.py:1640, 1668; the image dump of pose_eval, 1606-1607): render_at_pose
  *                           (models/SLAM/gaussian.py:555-579) for V poses -- V x [transform + two rasteriser forwards] as one batched call
+ *   fr_fisher_point_views <- the candidate scan of GaussianSLAM.global_planning (models/SLAM/gaussian.py:1285-1325: pointScores per
+ *                           candidate, the running max_points_score that prune_invisible reads) as one batched call
  *   fr_popgs_diag_criterion <- the T-opt / D-opt criterion and prior update inside path_evaluation_popgs
  *                           (tester_gaussians_navigation.py:2147-2178, models/SLAM/gaussian_object.py:1705-1719)
  *   fr_densify_stats / fr_densify_masks / fr_prune_mask <- the statistics of get_loss / densify / prune_gaussians
@@ -316,6 +318,37 @@ int fr_render_views_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_
 int fr_render_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* cfg_f,
                     float* out_color, float* out_features, float* out_depth, float* out_final_T,
                     void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream);
+
+/* ---- per-Gaussian view scores and their running maximum ---------------------------------------------------------------
+ * The candidate scan of GaussianSLAM.global_planning (models/SLAM/gaussian.py:1285-1325, the same loop in gaussian_object.py) asks
+ * "which Gaussians does view v inform, and by how much?": pointScores = sum(cur_H * H_train_inv, dim=1) per candidate, a running
+ * max_points_score over the candidates, prune_invisible on that maximum.  With cur_H[v] what fr_fisher_views accumulates into a
+ * per-view out_H (the dL_dpix^2 factor included):
+ *     point[v, i] = sum_c cur_H[v, i, c] * H_inv[(v,) i, c]
+ * One number per (view, Gaussian): the tile kernel keeps ONE accumulator per candidate whatever `columns` is (the pair's contracted
+ * factor comes from the score records of fr_fisher_views), and no [V, P, columns] tensor exists anywhere.
+ *   out_point_scores [V, P] or null: every element is written; a Gaussian that contributes nothing in view v gets 0.0
+ *   out_point_max    [P] or null:    out_point_max[i] <- max(out_point_max[i], max_v point[v, i]).  The CALLER initialises it (the
+ *                    reference starts from zeros) with non-negative values, so calls over chunks of views compose, and ranks through
+ *                    all_reduce(MAX).  The maximum is taken on the bit patterns (unsigned atomic max): exact, independent of the order;
+ *                    with both outputs given, out_point_max == max(initial, max over v of out_point_scores) of the same call bit for bit.
+ *   at least one of the two.
+ * fr_fisher_cfg fields used: n_views, columns (4 or 11), dL_dpix, w2c, poses_are_c2w, H_inv (required), H_inv_view_stride (0 = one
+ * block shared, else one per view), out_scores (optional: the view's score sum_i point[v, i], summed from per-tile partials in a fixed
+ * order in double -- the same bits from call to call, and independent of the batch), out_vis_count, out_num_rendered, tile_capacity,
+ * order.  out_H, dL_dpix_image, reuse_static, a null H_inv, two null outputs and images beyond 4096 tiles are rejected (FR_EINVAL);
+ * every check is made before any device work.
+ * point[v, i] itself is a sum of global float atomics, one per (16 x 4 pixel strip, Gaussian): their arrival order is not fixed, so two
+ * calls may differ in its last bits.  out_scores and the max identity above do not depend on that order.
+ * status as fr_fisher_views; on overflow no output byte changes.  No device allocation, no host synchronisation.
+ * fr_fisher_point_workspace_bytes is a host-only query (0 for a bad argument or an image beyond 4096 tiles); the layout's offsets
+ * [0..7] are those of fr_fisher_workspace_layout, [8] the per-slot accumulators f32 [n_views, PV] (PV as there). */
+size_t fr_fisher_point_workspace_bytes(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns);
+int fr_fisher_point_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns,
+                                     size_t offsets[9]);
+int fr_fisher_point_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* cfg_f,
+                          float* out_point_scores, float* out_point_max,
+                          void* workspace, size_t workspace_bytes, int64_t max_rendered, int32_t* status, fr_stream_t stream);
 
 /* ---- POp-GS diagonal criteria over probe rows ("T-opt/D-opt variants") ---------------------
  * The reference scores a pose from the diagonal estimator with a chain of torch ops over [11 P] vectors and, along a path, folds

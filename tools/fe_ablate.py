@@ -4,6 +4,8 @@ A -DFR_ABLATE build of the library (tools/_build/, never the package directory) 
     34 = no range claims (no global atomics), 35 = phase A only (frustum test + survivor lists), 36 = phases A + B (no records, no list
     entries), 37 = all phases, every record written to the same few cache lines (the arithmetic without its HBM traffic);
 every mode raises the overflow flag so that the kernels behind the scan return at once -- the time of one launch is the front end's.
+`--outh` / `--point`: the out_H launch of 16 keyframes / the per-Gaussian scores of 64 views with modes 0, 28 (no global atomics), 29 (no
+LDS atomics either).
 One child process per mode (FR_DEBUG_MODE is read once per process)."""
 import os
 import subprocess
@@ -53,6 +55,20 @@ def child(mode):
         torch.cuda.synchronize()
         print("mode", mode, "H_train of 16 keyframes %.3f ms per launch" % (e0.elapsed_time(e1) / 10), flush=True)
         return
+    if "--point" in sys.argv:
+        # the per-Gaussian scores of 64 views (k_fisher_point_tile): 0 = everything, 28 = no global atomics, 29 = no LDS atomics either
+        best = torch.zeros((P,), device=dev)
+        for _ in range(3):
+            sc.point_launch(w2c, Hi, per_view=False, point_max=best)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            sc.point_launch(w2c, Hi, per_view=False, point_max=best)
+        e1.record()
+        torch.cuda.synchronize()
+        print("mode", mode, "point scores of 64 views %.3f ms per launch" % (e0.elapsed_time(e1) / 10), flush=True)
+        return
     for _ in range(3):
         r = sc.launch(w2c, H_inv=Hi)
     torch.cuda.synchronize()
@@ -70,8 +86,8 @@ if __name__ == "__main__":
         child(int(sys.argv[2]))
     else:
         build()
-        outh = ["--outh"] if "--outh" in sys.argv else []
-        modes = [int(a) for a in sys.argv[1:] if a != "--outh"] or ([0, 28, 29] if outh else [30, 31, 32, 33, 34, 35, 36, 37])
+        outh = [a for a in ("--outh", "--point") if a in sys.argv]
+        modes = [int(a) for a in sys.argv[1:] if a not in ("--outh", "--point")] or ([0, 28, 29] if outh else [30, 31, 32, 33, 34, 35, 36, 37])
         for m in modes:
             env = dict(os.environ, FR_DEBUG_MODE=str(m), FISHER_RAST_SO=SO)
             subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", str(m)] + outh, env=env)
