@@ -7030,6 +7030,9 @@ static inline int fr_pick_G_views(long long P)
 	long long gwant = (P + (long long)FR_THREADS * 200) / ((long long)FR_THREADS * 400);
 	return (int)(gwant < 1 ? 1 : (gwant > 8 ? 8 : gwant));
 }
+// the compact lists and records of the multi-view front end: projection workgroups along P, slots (Gaussians) per workgroup
+static inline long long fr_view_block_slots(long long P) { return (long long)FR_THREADS * fr_pick_G_views(P); }
+static inline long long fr_view_blocks(long long P) { return (P + fr_view_block_slots(P) - 1) / fr_view_block_slots(P); }
 static inline int fr_pick_VC(long long T)
 {
 	long long vc = 8192 / (T < 1 ? 1 : T);
@@ -7297,8 +7300,22 @@ struct FrJoinGuard {
 
 // Score-only mode: the front end also produces the scorer's per-(view, Gaussian) records (k_pack_static, then phase C of
 // k_preprocess_views; with the single-view front end, k_fisher_records after k_scatter_keys, beside the sorts, on the second side stream).
-struct FrScorerPlan { int columns; bool form_a; FrRecordArgs ra; bool skip_pack = false; bool general = false; bool pose = false; bool view_identity = false; bool render = false; bool point = false; };   // point: score form + slot table + cleared accumulators (fr_fisher_point_views)
-//   // render: the 48-byte records of k_render_views_tile (fr_render_views)   // view_identity: fr_fisher_cfg.view_is_identity   // pose: the records of k_fisher_pose_tile (fr_fisher_pose_views)   // general: out_H records of k_fisher_tile_v3g   // skip_pack: a view group after the first (the packed static records are per call)     // form_a: out_H mode, the records carry the mean Jacobian (k_fisher_tile_v3h)
+// Which record the front end writes per visible (view, Gaussian): the AF argument of k_preprocess_views_c (FrRecStride)
+enum class FrRecForm {
+	Score,       // score form of k_fisher_tile_v3 / _v4: 96 bytes, 80 with fixed key segments
+	A,           // out_H mode, 4 columns: the records carry the mean Jacobian (k_fisher_tile_v3h)
+	General,     // the other out_H modes: the 112- / 208-byte records of k_fisher_tile_v3g
+	Pose,        // the records of k_fisher_pose_tile (fr_fisher_pose_views)
+	Render,      // the 48-byte records of k_render_views_tile (fr_render_views)
+	Point,       // score form + slot table + cleared accumulators (fr_fisher_point_views)
+};
+struct FrScorerPlan {
+	FrRecForm form = FrRecForm::Score;
+	int columns;
+	FrRecordArgs ra;
+	bool skip_pack = false;          // a view group after the first, or reuse_static: the packed static records are per call
+	bool view_identity = false;      // fr_fisher_cfg.view_is_identity
+};
 template <int C> __global__ void k_pack_static(FrParams p, const float* __restrict__ H_inv, float* __restrict__ packed, float4* __restrict__ mt, float4* __restrict__ grp);
 template <int C, bool LIST, bool FORM_A> __global__ void k_fisher_records(FrParams p, FrRecordArgs ra);
 
@@ -7356,29 +7373,41 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 		// against 2.53 ms: the records' waves slow the latency-bound scatter and the one-workgroup-per-CU sort tier down.)
 		const bool dk = p.tile_cap != 0;
 		const size_t lds_c = lds_c_of(p.VC);
-		if (once && plan->render && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 4, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->render) hipLaunchKernelGGL((k_preprocess_views_c<4, 4, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->pose && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 3, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->pose) hipLaunchKernelGGL((k_preprocess_views_c<4, 3, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->general && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 2, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->general && plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views_c<4, 2, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->general && dk) hipLaunchKernelGGL((k_preprocess_views_c<11, 2, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->general) hipLaunchKernelGGL((k_preprocess_views_c<11, 2, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->form_a && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 1, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->form_a) hipLaunchKernelGGL((k_preprocess_views_c<4, 1, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->point && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, true, false, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->point && plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, false, false, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->point && dk) hipLaunchKernelGGL((k_preprocess_views_c<11, 0, true, false, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->point) hipLaunchKernelGGL((k_preprocess_views_c<11, 0, false, false, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->columns == 4 && dk && plan->view_identity) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, true, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->columns == 4 && dk) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views_c<4, 0, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once && dk) hipLaunchKernelGGL((k_preprocess_views_c<11, 0, true>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
-		else if (once) hipLaunchKernelGGL((k_preprocess_views_c<11, 0, false>), gridV, dim3(FR_THREADS), lds_c, s, p, ra);
+#define FR_VIEWS_C(...) hipLaunchKernelGGL((k_preprocess_views_c<__VA_ARGS__>), gridV, dim3(FR_THREADS), lds_c, s, p, ra)
+		const bool c4 = plan && plan->columns == 4;
+		if (once)
+		{
+			switch (plan->form)
+			{
+			case FrRecForm::Render:
+				if (dk) FR_VIEWS_C(4, 4, true); else FR_VIEWS_C(4, 4, false);
+				break;
+			case FrRecForm::Pose:
+				if (dk) FR_VIEWS_C(4, 3, true); else FR_VIEWS_C(4, 3, false);
+				break;
+			case FrRecForm::General:
+				if (c4) { if (dk) FR_VIEWS_C(4, 2, true); else FR_VIEWS_C(4, 2, false); }
+				else { if (dk) FR_VIEWS_C(11, 2, true); else FR_VIEWS_C(11, 2, false); }
+				break;
+			case FrRecForm::A:
+				if (dk) FR_VIEWS_C(4, 1, true); else FR_VIEWS_C(4, 1, false);
+				break;
+			case FrRecForm::Point:
+				if (c4) { if (dk) FR_VIEWS_C(4, 0, true, false, true); else FR_VIEWS_C(4, 0, false, false, true); }
+				else { if (dk) FR_VIEWS_C(11, 0, true, false, true); else FR_VIEWS_C(11, 0, false, false, true); }
+				break;
+			case FrRecForm::Score:
+				if (c4 && dk && plan->view_identity) FR_VIEWS_C(4, 0, true, true);
+				else if (c4) { if (dk) FR_VIEWS_C(4, 0, true); else FR_VIEWS_C(4, 0, false); }
+				else { if (dk) FR_VIEWS_C(11, 0, true); else FR_VIEWS_C(11, 0, false); }
+				break;
+			}
+		}
+#undef FR_VIEWS_C
 		else if (!plan) hipLaunchKernelGGL((k_preprocess_views<0, false>), gridV, dim3(FR_THREADS), lds, s, p, ra);
 #ifdef FR_AB
-		else if (plan->form_a) hipLaunchKernelGGL((k_preprocess_views<-4, true>), gridV, dim3(FR_THREADS), lds, s, p, ra);
-		else if (plan->columns == 4) hipLaunchKernelGGL((k_preprocess_views<4, true>), gridV, dim3(FR_THREADS), lds, s, p, ra);
+		else if (plan->form == FrRecForm::A) hipLaunchKernelGGL((k_preprocess_views<-4, true>), gridV, dim3(FR_THREADS), lds, s, p, ra);
+		else if (c4) hipLaunchKernelGGL((k_preprocess_views<4, true>), gridV, dim3(FR_THREADS), lds, s, p, ra);
 		else hipLaunchKernelGGL((k_preprocess_views<11, true>), gridV, dim3(FR_THREADS), lds, s, p, ra);
 #else
 		else return fr_fail(FR_EINVAL, "fr_bin_pipeline: a records plan of the multi-view front end needs compact records");
@@ -7415,7 +7444,7 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 		FrSideStream& s2 = fr_side_stream(1);
 		const bool forked2 = s2.ok && hipEventRecord(s2.fork, s) == hipSuccess && hipStreamWaitEvent(s2.stream, s2.fork, 0) == hipSuccess;
 		hipStream_t rs = forked2 ? s2.stream : s;
-		if (plan->form_a) hipLaunchKernelGGL((k_fisher_records<4, false, true>), gridP, dim3(FR_THREADS), 0, rs, p, plan->ra);
+		if (plan->form == FrRecForm::A) hipLaunchKernelGGL((k_fisher_records<4, false, true>), gridP, dim3(FR_THREADS), 0, rs, p, plan->ra);
 		else if (plan->columns == 4) hipLaunchKernelGGL((k_fisher_records<4, false, false>), gridP, dim3(FR_THREADS), 0, rs, p, plan->ra);
 		else hipLaunchKernelGGL((k_fisher_records<11, false, false>), gridP, dim3(FR_THREADS), 0, rs, p, plan->ra);
 		if (forked2) joins.forked(&s2);
@@ -7941,11 +7970,11 @@ static FrFisherLayout fr_fisher_layout(int64_t P, int64_t W, int64_t H, int64_t 
 	size_t o = 0;
 	// radii [V][P] int32 (single-pass front end, images beyond FR_MAX_LDS_TILES tiles) and the compact visible lists
 	// [V][blocks][256 G] x 16 B of the multi-view front end share one region: a launch runs one or the other
-	const size_t nblk_v = (size_t)((P + FR_THREADS * fr_pick_G_views(P) - 1) / (FR_THREADS * fr_pick_G_views(P)));
-	L.radii = o; o = fr_align(o + (size_t)V * nblk_v * (size_t)(FR_THREADS * fr_pick_G_views(P)) * sizeof(FrVisEntry));
+	const size_t nblk_v = (size_t)fr_view_blocks(P);
+	L.radii = o; o = fr_align(o + (size_t)V * nblk_v * (size_t)fr_view_block_slots(P) * sizeof(FrVisEntry));
 	L.vis_n = o; o = fr_align(o + (size_t)V * nblk_v * 4);
 	// [V][P] 32-byte splat records; with compact records the same region is [V][workgroup][256 G] (phase B parks {recA, recB} there)
-	L.PV = nblk_v * (size_t)(FR_THREADS * fr_pick_G_views(P));
+	L.PV = nblk_v * (size_t)fr_view_block_slots(P);
 	const size_t VPV = (size_t)V * (L.PV > (size_t)P ? L.PV : (size_t)P);
 	L.splat = o; o = fr_align(o + VPV * sizeof(FrSplat));
 	// dense: [V][P] x 64 B {12 polynomial coefficients + k3, or A'[15], 1/o^2}; compact: [V][PV] x 96 B {recA, recB, the same}
@@ -7981,12 +8010,18 @@ static FrFisherLayout fr_fisher_layout(int64_t P, int64_t W, int64_t H, int64_t 
 	return L;
 }
 
+// what the four *_workspace_layout functions share
+static void fr_export_offsets(const FrFisherLayout& L, size_t o[8])
+{
+	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+}
+
 extern "C" int fr_fisher_workspace_layout(int32_t P, int32_t W, int32_t H, int32_t n_views, int64_t max_rendered, int32_t columns, size_t o[8])
 {
 	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0 || (columns != 4 && columns != 11) || !o)
 		return fr_fail(FR_EINVAL, "fr_fisher_workspace_layout: bad argument");
 	const FrFisherLayout L = fr_fisher_layout(P, W, H, n_views, max_rendered, columns);
-	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+	fr_export_offsets(L, o);
 	return FR_OK;
 }
 
@@ -8010,15 +8045,32 @@ extern "C" size_t fr_fisher_workspace_bytes(int32_t P, int32_t W, int32_t H, int
 	return fr_fisher_layout(P, W, H, n_views, max_rendered, columns).total;
 }
 
-// score-only mode: the single front-to-back pass over the records (no capacity limit, no fallback kernel)
-static void fr_launch_fisher_v3(FrParams& p, FrFisherArgs f, float4* recq, hipStream_t s)
-{
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	if (g_prof_on)
+// Measurement hook: a pair of events around the dominant kernel(s) of a call, on the stream they run on, from here to the end of the
+// scope.  With profiling off it tests the flag and does nothing else.
+namespace {
+struct FrProfSpan {
+	hipStream_t s; const bool on; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	explicit FrProfSpan(hipStream_t stream) : s(stream), on(g_prof_on)
 	{
+		if (!on) return;
 		(void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
 		(void)hipEventRecord(ev0, s);
 	}
+	~FrProfSpan()
+	{
+		if (!on) return;
+		(void)hipEventRecord(ev1, s);
+		g_prof_events.push_back(std::make_pair(ev0, ev1));
+	}
+	FrProfSpan(const FrProfSpan&) = delete;
+	FrProfSpan& operator=(const FrProfSpan&) = delete;
+};
+}
+
+// score-only mode: the single front-to-back pass over the records (no capacity limit, no fallback kernel)
+static void fr_launch_fisher_v3(FrParams& p, FrFisherArgs f, float4* recq, hipStream_t s)
+{
+	FrProfSpan span(s);
 	// FR_DEBUG_MODE=8: 8 x 8 pixel blocks per wave instead of 16 x 4 strips (A/B runs; measured 5 % slower on MI355X);
 	// FR_DEBUG_MODE=24: the rolling two-chunk window (k_fisher_tile_v3w: 24 % fewer walk iterations, 8 % slower -- see there)
 #ifdef FR_AB
@@ -8029,22 +8081,12 @@ static void fr_launch_fisher_v3(FrParams& p, FrFisherArgs f, float4* recq, hipSt
 #endif
 	if (f.key_shift) hipLaunchKernelGGL(k_fisher_tile_v4, dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f);
 	else hipLaunchKernelGGL((k_fisher_tile_v3<16, 4>), dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f, (const float4*)recq);
-	if (g_prof_on)
-	{
-		(void)hipEventRecord(ev1, s);
-		g_prof_events.push_back(std::make_pair(ev0, ev1));
-	}
 }
 
 // out_H mode with 4 columns and a constant upstream gradient: two front-to-back passes over the records
 static void fr_launch_fisher_v3h(FrParams& p, FrFisherArgs f, float4* recq, FrSegArgs sg, hipStream_t s)
 {
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	if (g_prof_on)
-	{
-		(void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
-		(void)hipEventRecord(ev0, s);
-	}
+	FrProfSpan span(s);
 	if (sg.snapT && p.T * p.V <= FR_SEG_TILES)
 	{
 		// few views: pass 1 per tile with the pixels' state saved at every segment boundary, pass 2 per (tile, segment)
@@ -8054,22 +8096,12 @@ static void fr_launch_fisher_v3h(FrParams& p, FrFisherArgs f, float4* recq, FrSe
 	}
 	else
 	hipLaunchKernelGGL((k_fisher_tile_v3h<16, 4, 0>), dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f, (const float4*)recq, sg);
-	if (g_prof_on)
-	{
-		(void)hipEventRecord(ev1, s);
-		g_prof_events.push_back(std::make_pair(ev0, ev1));
-	}
 }
 
 // the other out_H modes on records: 11 columns and / or an upstream-gradient image
 static void fr_launch_fisher_v3g(FrParams& p, FrFisherArgs f, int columns, bool img, FrSegArgs sg, hipStream_t s)
 {
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	if (g_prof_on)
-	{
-		(void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
-		(void)hipEventRecord(ev0, s);
-	}
+	FrProfSpan span(s);
 	dim3 grid(p.T * p.V), block(FR_THREADS);
 	if (sg.snapT && p.T * p.V <= FR_SEG_TILES)
 	{
@@ -8085,11 +8117,6 @@ static void fr_launch_fisher_v3g(FrParams& p, FrFisherArgs f, int columns, bool 
 	else if (columns == 11) hipLaunchKernelGGL((k_fisher_tile_v3g<11, false, 0>), grid, block, 0, s, p, f, sg);
 	else if (img) hipLaunchKernelGGL((k_fisher_tile_v3g<4, true, 0>), grid, block, 0, s, p, f, sg);
 	else hipLaunchKernelGGL((k_fisher_tile_v3g<4, false, 0>), grid, block, 0, s, p, f, sg);
-	if (g_prof_on)
-	{
-		(void)hipEventRecord(ev1, s);
-		g_prof_events.push_back(std::make_pair(ev0, ev1));
-	}
 }
 
 template <int C>
@@ -8101,20 +8128,11 @@ static void fr_launch_fisher(FrParams& p, FrFisherArgs f, float* packed, uint8_t
 	// wave-private passes over the sorted keys; tiles whose lists do not fit the LDS index are flagged ...
 	f.only_flagged = nullptr;
 	hipLaunchKernelGGL((k_pack_static<C>), dim3((p.P + FR_THREADS - 1) / FR_THREADS), block, 0, s, p, (hi && !per_view) ? f.H_inv : nullptr, packed, (float4*)nullptr, (float4*)nullptr);
-	// measurement hook: events around the dominant kernel only, on the stream it runs on
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	if (g_prof_on)
 	{
-		(void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
-		(void)hipEventRecord(ev0, s);
-	}
-	if (hi && ho) hipLaunchKernelGGL((k_fisher_tile_v2<C, true, true>), grid, block, 0, s, p, f, (const float*)packed, fallback);
-	else if (hi) hipLaunchKernelGGL((k_fisher_tile_v2<C, true, false>), grid, block, 0, s, p, f, (const float*)packed, fallback);
-	else hipLaunchKernelGGL((k_fisher_tile_v2<C, false, true>), grid, block, 0, s, p, f, (const float*)packed, fallback);
-	if (g_prof_on)
-	{
-		(void)hipEventRecord(ev1, s);
-		g_prof_events.push_back(std::make_pair(ev0, ev1));
+		FrProfSpan span(s);                                            // (the dominant kernel only)
+		if (hi && ho) hipLaunchKernelGGL((k_fisher_tile_v2<C, true, true>), grid, block, 0, s, p, f, (const float*)packed, fallback);
+		else if (hi) hipLaunchKernelGGL((k_fisher_tile_v2<C, true, false>), grid, block, 0, s, p, f, (const float*)packed, fallback);
+		else hipLaunchKernelGGL((k_fisher_tile_v2<C, false, true>), grid, block, 0, s, p, f, (const float*)packed, fallback);
 	}
 	// ... and redone by the scan kernel
 	f.only_flagged = fallback;
@@ -8123,13 +8141,114 @@ static void fr_launch_fisher(FrParams& p, FrFisherArgs f, float* packed, uint8_t
 	else hipLaunchKernelGGL((k_fisher_tile<C, false, true>), grid, block, 0, s, p, f);
 }
 
+// ---- what the batched entry points (fr_fisher_views, fr_fisher_pose_views, fr_render_views, fr_fisher_point_views) share ----------
+// The argument checks, with the caller's name in front of every message.  FR_CHK_CFG: fc, w2c, status, n_views (`cfg_what`: the
+// caller's words for it); FR_CHK_MAX_RENDERED: no negative max_rendered; FR_CHK_TILES: no image beyond 4096 tiles (the multi-view
+// front end's limit); FR_CHK_SEGMENTS: no negative tile_capacity, and V T tile_capacity keys fit the key buffer and 32-bit offsets.
+enum { FR_CHK_CFG = 1, FR_CHK_MAX_RENDERED = 2, FR_CHK_TILES = 4, FR_CHK_SEGMENTS = 8, FR_CHK_ALL = 15 };
+static int fr_check_views(const char* who, const char* cfg_what, unsigned checks, const fr_raster_cfg* cfg, const fr_fisher_cfg* fc,
+                          int64_t max_rendered, const int32_t* status)
+{
+	static thread_local char buf[256];
+	auto fail = [&](const char* what) { snprintf(buf, sizeof(buf), "%s: %s", who, what); return fr_fail(FR_EINVAL, buf); };
+	if ((checks & FR_CHK_CFG) && (!fc || fc->n_views <= 0 || !fc->w2c || !status)) return fail(cfg_what);
+	if ((checks & FR_CHK_SEGMENTS) && fc->tile_capacity < 0) return fail("negative tile_capacity");
+	if ((checks & FR_CHK_MAX_RENDERED) && max_rendered < 0) return fail("negative max_rendered");
+	const long long T = (long long)((cfg->image_width + 15) / 16) * ((cfg->image_height + 15) / 16);
+	if ((checks & FR_CHK_TILES) && T > FR_MAX_LDS_TILES) return fail("images beyond 4096 tiles are not supported");
+	if ((checks & FR_CHK_SEGMENTS) && fc->tile_capacity > 0)
+	{
+		const long long need = (long long)fc->n_views * T * (long long)fc->tile_capacity;
+		if (need > max_rendered || need >= (1ll << 32)) return fail("n_views * tiles * tile_capacity exceeds max_rendered (or 2^32)");
+	}
+	return FR_OK;
+}
+
+// No Gaussians: zero scores and counters, a clear status word.
+static void fr_empty_map(const fr_fisher_cfg* fc, int32_t* status, hipStream_t s)
+{
+	const size_t V = (size_t)fc->n_views;
+	if (fc->out_scores) (void)hipMemsetAsync(fc->out_scores, 0, V * 4, s);
+	if (fc->out_vis_count) (void)hipMemsetAsync(fc->out_vis_count, 0, V * 4, s);
+	if (fc->out_num_rendered) (void)hipMemsetAsync(fc->out_num_rendered, 0, V * 4, s);
+	(void)hipMemsetAsync(status, 0, 16, s);
+}
+
+// FrParams of a batched call (after fr_fill_params): the workspace's arrays, the poses (camera-to-world ones are inverted into the
+// workspace here: the launch error is returned), the caller's counters and order, the key buffer.  deal_views: the views are dealt
+// over the XCDs by weight where their count allows it (the front end fills the map).
+static int fr_carve_views(FrParams& p, const FrFisherLayout& L, char* ws, const fr_fisher_cfg* fc, int64_t max_rendered, hipStream_t s,
+                          bool deal_views = true)
+{
+	const int V = p.V;
+	p.prefiltered = 0;            // (candidate views cull by design; status[3] means something else here)
+	p.w2c = fc->w2c;
+	if (fc->poses_are_c2w)
+	{
+		float* inv = (float*)(ws + L.w2c_inv);
+		hipLaunchKernelGGL(k_invert_poses, dim3((V + 63) / 64), dim3(64), 0, s, V, fc->w2c, inv);
+		if (int rc = fr_check_launch("k_invert_poses")) return rc;
+		p.w2c = inv;
+	}
+	p.radii = (int*)(ws + L.radii);          // one region: a launch runs the single-pass front end (radii) or the multi-view one (lists)
+	p.vis_list = (FrVisEntry*)p.radii;
+	p.vis_n = (uint32_t*)(ws + L.vis_n);
+	p.splat = (FrSplat*)(ws + L.splat);
+	p.cov3D_out = (float*)(ws + L.cov3D);
+	p.tile_cnt = (uint32_t*)(ws + L.tile_cnt);
+	p.tile_off = (uint32_t*)(ws + L.tile_off);
+	p.tile_fill = (uint32_t*)(ws + L.tile_fill);
+	p.status = (int*)(ws + L.status);
+	p.big_list = (uint32_t*)(ws + L.big_list);
+	p.part_list = (uint32_t*)(ws + L.part_list);
+	const bool deal = deal_views && (V & 7) == 0 && V <= 1024;
+	p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
+	p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;
+	p.blk_base = (uint32_t*)(ws + L.blk_base);
+	p.keys = (uint64_t*)(ws + L.keys);
+	p.key_capacity = max_rendered;
+	p.vis_count = fc->out_vis_count;
+	p.num_rendered = fc->out_num_rendered;
+	p.order = fc->order;
+	return FR_OK;
+}
+
+// Fixed key segments (tile_capacity keys per (view, tile), placed by k_preprocess_views_c) or packed lists (p.tile_cap = 0): fixed
+// where the front end can address them -- the 8-byte list entries hold tile columns and strip rows in bytes, the keys 28-bit record
+// slots -- and while the LDS cursors fit (fr_plan_views_c).  Decided HERE, before a caller fixes the record stride: the 80-byte score
+// records go with fixed segments only; fr_bin_pipeline plans again and gets the same answer.
+static void fr_plan_fixed_segments(FrParams& p, int tile_capacity)
+{
+	const bool slots_fit = fr_view_blocks(p.P) * fr_view_block_slots(p.P) < (1ll << 28);
+	p.tile_cap = (tile_capacity > 0 && p.gx <= 255u && p.gy <= 63u && slots_fit) ? (uint32_t)tile_capacity : 0u;
+	(void)fr_plan_views_c(p.T, fr_pick_VC(p.T), p.tile_cap);
+}
+
+// Compact records of `rstride` float4 each in the workspace's record region: the plan's FrRecordArgs (no H_inv, the early frustum
+// test on: a caller with other needs says so afterwards) and what the tile kernels read of them through FrFisherArgs.
+static void fr_wire_records(FrScorerPlan& plan, FrFisherArgs& f, const FrFisherLayout& L, char* ws, int rstride, bool slot_table)
+{
+	plan.ra.H_inv = nullptr; plan.ra.hinv_stride = 0;
+	plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
+	plan.ra.mt = (const float4*)(ws + L.mt);
+	plan.ra.grp = (const float4*)(ws + L.grp);
+	plan.ra.early = 1;
+	plan.ra.comp = (float4*)(ws + L.recq);
+	plan.ra.stride = rstride;
+	plan.ra.slot_idx = slot_table ? (uint32_t*)(ws + L.slot_idx) : nullptr;
+	plan.ra.slot_acc = nullptr;
+	f.recA = plan.ra.comp; f.ab_view = (long long)L.PV * rstride; f.ab_stride = rstride;
+	f.recQ = plan.ra.comp + 2; f.q_view = (long long)L.PV * rstride; f.q_stride = rstride;
+	f.slot_idx = plan.ra.slot_idx; f.slot_view = (long long)L.PV;
+}
+
 extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* fc,
                                void* workspace, size_t workspace_bytes, int64_t max_rendered,
                                int32_t* status, fr_stream_t stream)
 {
 	int rc = fr_validate(cfg, g, "fr_fisher_views");
 	if (rc) return rc;
-	if (!fc || fc->n_views <= 0 || !fc->w2c || !status) return fr_fail(FR_EINVAL, "fr_fisher_views: bad fisher cfg");
+	if ((rc = fr_check_views("fr_fisher_views", "bad fisher cfg", FR_CHK_CFG, cfg, fc, max_rendered, status))) return rc;
 	if (fc->columns != 4 && fc->columns != 11) return fr_fail(FR_EINVAL, "fr_fisher_views: columns must be 4 or 11");
 	if (!g->colors_precomp) return fr_fail(FR_EINVAL, "fr_fisher_views: needs colors_precomp (the reference always passes rgb_colors)");
 	if (fc->columns == 11 && !(g->scales && g->rotations)) return fr_fail(FR_EINVAL, "fr_fisher_views: columns=11 needs scales and rotations");
@@ -8141,10 +8260,7 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	hipStream_t s = (hipStream_t)stream;
 	if (P == 0)
 	{
-		if (fc->out_scores) (void)hipMemsetAsync(fc->out_scores, 0, (size_t)V * 4, s);
-		if (fc->out_vis_count) (void)hipMemsetAsync(fc->out_vis_count, 0, (size_t)V * 4, s);
-		if (fc->out_num_rendered) (void)hipMemsetAsync(fc->out_num_rendered, 0, (size_t)V * 4, s);
-		(void)hipMemsetAsync(status, 0, 16, s);
+		fr_empty_map(fc, status, s);
 		return FR_OK;
 	}
 	FrFisherLayout L = fr_fisher_layout(P, W, H, V, max_rendered, fc->columns);
@@ -8152,48 +8268,11 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	char* ws = (char*)workspace;
 	FrParams p;
 	fr_fill_params(p, cfg, g, V);
-	p.prefiltered = 0;            // (candidate views cull by design; status[3] means something else here)
-	p.w2c = fc->w2c;
-	if (fc->poses_are_c2w)
-	{
-		float* inv = (float*)(ws + L.w2c_inv);
-		hipLaunchKernelGGL(k_invert_poses, dim3((V + 63) / 64), dim3(64), 0, s, V, fc->w2c, inv);
-		if ((rc = fr_check_launch("k_invert_poses"))) return rc;
-		p.w2c = inv;
-	}
-	p.radii = (int*)(ws + L.radii);
-	p.vis_list = (FrVisEntry*)(ws + L.radii);
-	p.vis_n = (uint32_t*)(ws + L.vis_n);
-	p.splat = (FrSplat*)(ws + L.splat);
-	p.cov3D_out = (float*)(ws + L.cov3D);
-	p.tile_cnt = (uint32_t*)(ws + L.tile_cnt);
-	p.tile_off = (uint32_t*)(ws + L.tile_off);
-	p.tile_fill = (uint32_t*)(ws + L.tile_fill);
-	p.status = (int*)(ws + L.status);
-	p.big_list = (uint32_t*)(ws + L.big_list);
-	p.part_list = (uint32_t*)(ws + L.part_list);
 	// the views dealt over the XCDs by weight (FR_DEBUG_MODE=27: in index order, for A/B runs)
-	const bool deal = (V & 7) == 0 && V <= 1024 && fr_debug_mode() != 27;
-	p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
-	p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;
-	p.blk_base = (uint32_t*)(ws + L.blk_base);
-	p.keys = (uint64_t*)(ws + L.keys);
-	p.key_capacity = max_rendered;
-	if (fc->tile_capacity < 0) return fr_fail(FR_EINVAL, "fr_fisher_views: negative tile_capacity");
-	if (fc->tile_capacity > 0)
-	{
-		// fixed key segments: V T tile_capacity keys must fit the key buffer (and 32-bit offsets)
-		const long long need = (long long)V * p.T * (long long)fc->tile_capacity;
-		if (need > max_rendered || need >= (1ll << 32)) return fr_fail(FR_EINVAL, "fr_fisher_views: n_views * tiles * tile_capacity exceeds max_rendered (or 2^32)");
-		// (else packed lists: the 8-byte list entries hold tile columns and strip rows in bytes, the keys 28-bit record slots;
-		// FR_DEBUG_MODE 8 / 24: tile kernels that do not read the keys' strip bits)
-		const long long nblk_c = (P + FR_THREADS * fr_pick_G_views(P) - 1) / (FR_THREADS * fr_pick_G_views(P));
-		const bool slots_fit = nblk_c * FR_THREADS * fr_pick_G_views(P) < (1ll << 28);
-		// (FR_DEBUG_MODE 20: the parking form of the projection kernel, which fills packed lists only)
-		if (p.gx <= 255u && p.gy <= 63u && slots_fit && fr_debug_mode() != 8 && fr_debug_mode() != 24 && fr_debug_mode() != 20) p.tile_cap = (uint32_t)fc->tile_capacity;
-	}
-	p.vis_count = fc->out_vis_count;
-	p.num_rendered = fc->out_num_rendered;
+	if ((rc = fr_carve_views(p, L, ws, fc, max_rendered, s, fr_debug_mode() != 27))) return rc;
+	// (this entry point alone takes images beyond 4096 tiles -- the dense single-view front end -- and any max_rendered; its
+	// tile_capacity is checked here, behind the empty map and the workspace)
+	if ((rc = fr_check_views("fr_fisher_views", nullptr, FR_CHK_SEGMENTS, cfg, fc, max_rendered, status))) return rc;
 	FrFisherArgs f;
 	f.dL = fc->dL_dpix;
 	f.dL_img = fc->dL_dpix_image; f.dL_stride = fc->dL_image_view_stride;
@@ -8212,41 +8291,33 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	// records too, through the multi-view front end; FR_DEBUG_MODE=22 keeps round 2's two-pass kernel (k_fisher_tile_v2) for A/B runs
 	const bool multi_fe = p.vis_list != nullptr && p.T <= FR_MAX_LDS_TILES;
 	const bool v3g = !fc->H_inv && fc->out_H && !v3h && multi_fe && !g->cov3D_precomp && f.debug_mode != 1 && f.debug_mode != 9 && f.debug_mode != 22 && f.debug_mode != 19;
-	FrScorerPlan plan;
-	plan.form_a = v3h;
-	plan.general = v3g;
-	plan.columns = fc->columns;
-	plan.view_identity = fc->view_is_identity != 0;
-	plan.ra.H_inv = fc->H_inv; plan.ra.hinv_stride = fc->H_inv_view_stride;
-	plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
 	// compact records with the multi-view front end (the same condition fr_bin_pipeline uses for it); FR_DEBUG_MODE=19: dense (A/B runs)
 	const bool compact = (v3 || v3h || v3g) && multi_fe && f.debug_mode != 19;
-	if (!compact) p.tile_cap = 0;                   // (fixed key segments are filled by the compact-record front end only)
-	else (void)fr_plan_views_c(p.T, fr_pick_VC(p.T), p.tile_cap);      // ... and only while their LDS cursors fit (decided HERE, before the stride)
+	// fixed key segments are filled by the compact-record front end only (FR_DEBUG_MODE 8 / 24: tile kernels that do not read the keys'
+	// strip bits; 20: the parking form of the projection kernel, which fills packed lists only)
+	if (compact && f.debug_mode != 8 && f.debug_mode != 24 && f.debug_mode != 20) fr_plan_fixed_segments(p, fc->tile_capacity);
+	else p.tile_cap = 0;
 	// float4 per record: the general out_H forms 13 / 7, the score form 5 with fixed key segments (80 bytes: FrRecStride), else 6
 	const int rstride = v3g ? (fc->columns == 11 ? 13 : 7) : ((v3 && p.tile_cap) ? 5 : 6);
-	plan.ra.comp = compact ? (float4*)(ws + L.recq) : nullptr;
-	plan.ra.stride = rstride;
-	plan.ra.slot_idx = (compact && (v3h || v3g)) ? (uint32_t*)(ws + L.slot_idx) : nullptr;
-	if (compact)
+	FrScorerPlan plan;
+	plan.form = v3h ? FrRecForm::A : v3g ? FrRecForm::General : FrRecForm::Score;
+	plan.columns = fc->columns;
+	plan.view_identity = fc->view_is_identity != 0;
+	fr_wire_records(plan, f, L, ws, rstride, v3h || v3g);
+	plan.ra.H_inv = fc->H_inv; plan.ra.hinv_stride = fc->H_inv_view_stride;
+	// the early frustum test needs a positive semi-definite cov3D: the one k_cov3d builds, not a caller's precomputed one;
+	// FR_DEBUG_MODE=15 switches it off (A/B runs)
+	plan.ra.early = (g->cov3D_precomp || f.debug_mode == 15) ? 0 : 1;
+	if (!compact)
 	{
-		f.recA = plan.ra.comp; f.ab_view = (long long)L.PV * rstride; f.ab_stride = rstride;
-		f.recQ = plan.ra.comp + 2; f.q_view = (long long)L.PV * rstride; f.q_stride = rstride;
-		f.slot_idx = plan.ra.slot_idx; f.slot_view = (long long)L.PV;
-	}
-	else
-	{
+		// dense records: [V][P] splat records and [V][P] x 64 B behind them
+		plan.ra.comp = nullptr; plan.ra.slot_idx = nullptr;
 		f.recA = (const float4*)p.splat; f.ab_view = (long long)P * 2; f.ab_stride = 2;
 		f.recQ = plan.ra.recq; f.q_view = (long long)P * 4; f.q_stride = 4;
 		f.slot_idx = nullptr; f.slot_view = 0;
+		// the processing order is honoured where the compact-record front end runs (it is a layout hint: the other paths ignore it)
+		p.order = nullptr;
 	}
-	// the early frustum test needs a positive semi-definite cov3D: the one k_cov3d builds, not a caller's precomputed one;
-	// FR_DEBUG_MODE=15 switches it off (A/B runs)
-	plan.ra.mt = (const float4*)(ws + L.mt);
-	plan.ra.grp = (const float4*)(ws + L.grp);
-	plan.ra.early = (g->cov3D_precomp || f.debug_mode == 15) ? 0 : 1;
-	// the processing order is honoured where the compact-record front end runs (it is a layout hint: the other paths ignore it)
-	p.order = compact ? fc->order : nullptr;
 
 	// ---- view groups (off by default: fr_pick_groups has the measurement).  The front end (projection, records, scan, scatter,
 	// sorts: ~1.1 ms at 500k Gaussians x 64 views) waits on memory for half its wave cycles, the tile kernel (~1.0 ms) is bound by
@@ -8261,8 +8332,7 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	const bool use_side = n_groups > 1 && tside.ok;
 	hipStream_t ts = use_side ? tside.stream : s;                  // the tile kernels' stream
 	static thread_local hipEvent_t front_done[FR_MAX_GROUPS] = { nullptr, nullptr, nullptr, nullptr };
-	const size_t nblk_v = (size_t)((P + FR_THREADS * fr_pick_G_views(P) - 1) / (FR_THREADS * fr_pick_G_views(P)));
-	const size_t cap_v = (size_t)(FR_THREADS * fr_pick_G_views(P));
+	const size_t nblk_v = (size_t)fr_view_blocks(P), cap_v = (size_t)fr_view_block_slots(P);
 	const size_t rec_view = compact ? L.PV : (size_t)P;            // records per view in the splat / record regions
 	struct TileJoin {                                              // the caller's stream waits for the tile stream on every way out
 		hipStream_t s; FrSideStream* side; bool on;
@@ -8362,7 +8432,7 @@ extern "C" int fr_fisher_pose_workspace_layout(int32_t P, int32_t W, int32_t H, 
 	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0 || !o)
 		return fr_fail(FR_EINVAL, "fr_fisher_pose_workspace_layout: bad argument");
 	const FrFisherLayout L = fr_fisher_layout(P, W, H, n_views, max_rendered, 4);
-	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+	fr_export_offsets(L, o);
 	o[8] = fr_pose_part_offset(P, W, H, n_views, max_rendered);
 	return FR_OK;
 }
@@ -8373,29 +8443,20 @@ extern "C" int fr_fisher_pose_views(const fr_raster_cfg* cfg, const fr_gaussians
 	// every argument check comes before any device work
 	int rc = fr_validate(cfg, g, "fr_fisher_pose_views");
 	if (rc) return rc;
-	if (!fc || fc->n_views <= 0 || !fc->w2c || !status || !out_pose_H) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: bad fisher cfg or null output");
+	if ((rc = fr_check_views("fr_fisher_pose_views", "bad fisher cfg or null output", FR_CHK_ALL, cfg, fc, max_rendered, status))) return rc;
+	if (!out_pose_H) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: bad fisher cfg or null output");
 	if (fc->H_inv || fc->out_scores) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: H_inv / out_scores are for fr_fisher_views");
 	if (fc->out_H) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: out_H is for fr_fisher_views");
 	if (fc->dL_dpix_image) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: no per-pixel upstream-gradient images (constant dL_dpix only)");
 	if (fc->reuse_static) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: reuse_static is not supported");
 	if (!g->colors_precomp) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: needs colors_precomp");
 	if (!(g->scales && g->rotations)) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: needs scales and rotations");
-	if (fc->tile_capacity < 0) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: negative tile_capacity");
 	const int P = cfg->P, W = cfg->image_width, H = cfg->image_height, V = fc->n_views;
-	const long long Tt = (long long)((W + 15) / 16) * ((H + 15) / 16);
-	if (Tt > FR_MAX_LDS_TILES) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: images beyond 4096 tiles are not supported");
-	if (fc->tile_capacity > 0)
-	{
-		const long long need = (long long)V * Tt * (long long)fc->tile_capacity;
-		if (need > max_rendered || need >= (1ll << 32)) return fr_fail(FR_EINVAL, "fr_fisher_pose_views: n_views * tiles * tile_capacity exceeds max_rendered (or 2^32)");
-	}
 	hipStream_t s = (hipStream_t)stream;
 	if (P == 0)
 	{
 		(void)hipMemsetAsync(out_pose_H, 0, (size_t)V * 36 * 4, s);
-		if (fc->out_vis_count) (void)hipMemsetAsync(fc->out_vis_count, 0, (size_t)V * 4, s);
-		if (fc->out_num_rendered) (void)hipMemsetAsync(fc->out_num_rendered, 0, (size_t)V * 4, s);
-		(void)hipMemsetAsync(status, 0, 16, s);
+		fr_empty_map(fc, status, s);
 		return fr_check_launch("fr_fisher_pose_views (no Gaussians)");
 	}
 	const FrFisherLayout L = fr_fisher_layout(P, W, H, V, max_rendered, 4);
@@ -8404,75 +8465,21 @@ extern "C" int fr_fisher_pose_views(const fr_raster_cfg* cfg, const fr_gaussians
 	char* ws = (char*)workspace;
 	FrParams p;
 	fr_fill_params(p, cfg, g, V);
-	p.prefiltered = 0;
-	p.w2c = fc->w2c;
-	if (fc->poses_are_c2w)
-	{
-		float* inv = (float*)(ws + L.w2c_inv);
-		hipLaunchKernelGGL(k_invert_poses, dim3((V + 63) / 64), dim3(64), 0, s, V, fc->w2c, inv);
-		if ((rc = fr_check_launch("k_invert_poses"))) return rc;
-		p.w2c = inv;
-	}
-	p.radii = (int*)(ws + L.radii);
-	p.vis_list = (FrVisEntry*)(ws + L.radii);
-	p.vis_n = (uint32_t*)(ws + L.vis_n);
-	p.splat = (FrSplat*)(ws + L.splat);
-	p.cov3D_out = (float*)(ws + L.cov3D);
-	p.tile_cnt = (uint32_t*)(ws + L.tile_cnt);
-	p.tile_off = (uint32_t*)(ws + L.tile_off);
-	p.tile_fill = (uint32_t*)(ws + L.tile_fill);
-	p.status = (int*)(ws + L.status);
-	p.big_list = (uint32_t*)(ws + L.big_list);
-	p.part_list = (uint32_t*)(ws + L.part_list);
-	const bool deal = (V & 7) == 0 && V <= 1024;
-	p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
-	p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;
-	p.blk_base = (uint32_t*)(ws + L.blk_base);
-	p.keys = (uint64_t*)(ws + L.keys);
-	p.key_capacity = max_rendered;
-	if (fc->tile_capacity > 0)
-	{
-		// fixed key segments where the compact-record front end can address them (as fr_fisher_views decides it)
-		const long long nblk_c = (P + FR_THREADS * fr_pick_G_views(P) - 1) / (FR_THREADS * fr_pick_G_views(P));
-		const bool slots_fit = nblk_c * FR_THREADS * fr_pick_G_views(P) < (1ll << 28);
-		if (p.gx <= 255u && p.gy <= 63u && slots_fit) p.tile_cap = (uint32_t)fc->tile_capacity;
-	}
-	(void)fr_plan_views_c(p.T, fr_pick_VC(p.T), p.tile_cap);
-	p.vis_count = fc->out_vis_count;
-	p.num_rendered = fc->out_num_rendered;
-	p.order = fc->order;
-	constexpr int rstride = FrRecStride<4, 3>::value;
+	if ((rc = fr_carve_views(p, L, ws, fc, max_rendered, s))) return rc;
+	fr_plan_fixed_segments(p, fc->tile_capacity);
 	FrScorerPlan plan;
+	plan.form = FrRecForm::Pose;
 	plan.columns = 4;
-	plan.form_a = false;
-	plan.pose = true;
-	plan.ra.H_inv = nullptr; plan.ra.hinv_stride = 0;
-	plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
-	plan.ra.comp = (float4*)(ws + L.recq);
-	plan.ra.stride = rstride;
-	plan.ra.slot_idx = nullptr;
-	plan.ra.mt = (const float4*)(ws + L.mt);
-	plan.ra.grp = (const float4*)(ws + L.grp);
-	plan.ra.early = 1;
 	FrFisherArgs f;
 	memset(&f, 0, sizeof(f));
 	f.dL = fc->dL_dpix;
-	f.recA = plan.ra.comp; f.ab_view = (long long)L.PV * rstride; f.ab_stride = rstride;
-	f.recQ = plan.ra.comp + 2; f.q_view = (long long)L.PV * rstride; f.q_stride = rstride;
+	fr_wire_records(plan, f, L, ws, FrRecStride<4, 3>::value, false);
 	if ((rc = fr_bin_pipeline(p, g, s, &plan))) return rc;
 	f.key_shift = p.tile_cap ? 4 : 0;                   // (fixed segments: keys = depth | slot << 4 | strips)
 	double* part = (double*)(ws + fr_pose_part_offset(P, W, H, V, max_rendered));
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	if (g_prof_on)
 	{
-		(void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
-		(void)hipEventRecord(ev0, s);
-	}
-	hipLaunchKernelGGL(k_fisher_pose_tile, dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, part);
-	if (g_prof_on)
-	{
-		(void)hipEventRecord(ev1, s);
-		g_prof_events.push_back(std::make_pair(ev0, ev1));
+		FrProfSpan span(s);
+		hipLaunchKernelGGL(k_fisher_pose_tile, dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, part);
 	}
 	if ((rc = fr_check_launch("k_fisher_pose_tile"))) return rc;
 	hipLaunchKernelGGL(k_pose_reduce, dim3(V), dim3(64), 0, s, (const double*)part, p.T, (const int*)p.status, out_pose_H, status);
@@ -8493,7 +8500,7 @@ extern "C" int fr_render_views_workspace_layout(int32_t P, int32_t W, int32_t H,
 	if (P < 0 || W <= 0 || H <= 0 || n_views <= 0 || max_rendered < 0 || !o || (long long)((W + 15) / 16) * ((H + 15) / 16) > FR_MAX_LDS_TILES)
 		return fr_fail(FR_EINVAL, "fr_render_views_workspace_layout: bad argument");
 	const FrFisherLayout L = fr_fisher_layout(P, W, H, n_views, max_rendered, 4);
-	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+	fr_export_offsets(L, o);
 	return FR_OK;
 }
 
@@ -8504,7 +8511,7 @@ extern "C" int fr_render_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	// every argument check comes before any device work
 	int rc = fr_validate(cfg, g, "fr_render_views");
 	if (rc) return rc;
-	if (!fc || fc->n_views <= 0 || !fc->w2c || !status) return fr_fail(FR_EINVAL, "fr_render_views: bad fisher cfg or null status");
+	if ((rc = fr_check_views("fr_render_views", "bad fisher cfg or null status", FR_CHK_ALL, cfg, fc, max_rendered, status))) return rc;
 	if (!out_color && !out_features && !out_depth && !out_final_T) return fr_fail(FR_EINVAL, "fr_render_views: no output requested");
 	if (fc->H_inv || fc->out_scores) return fr_fail(FR_EINVAL, "fr_render_views: H_inv / out_scores are for fr_fisher_views");
 	if (fc->out_H) return fr_fail(FR_EINVAL, "fr_render_views: out_H is for fr_fisher_views");
@@ -8512,17 +8519,8 @@ extern "C" int fr_render_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	if (fc->reuse_static) return fr_fail(FR_EINVAL, "fr_render_views: reuse_static is not supported");
 	if (g->shs || !g->colors_precomp) return fr_fail(FR_EINVAL, "fr_render_views: needs colors_precomp (no SH colours)");
 	if (g->cov3D_precomp || !(g->scales && g->rotations)) return fr_fail(FR_EINVAL, "fr_render_views: needs scales and rotations (no cov3D_precomp)");
-	if (fc->tile_capacity < 0) return fr_fail(FR_EINVAL, "fr_render_views: negative tile_capacity");
-	if (max_rendered < 0) return fr_fail(FR_EINVAL, "fr_render_views: negative max_rendered");
-	const int P = cfg->P, W = cfg->image_width, H = cfg->image_height, V = fc->n_views;
-	const long long Tt = (long long)((W + 15) / 16) * ((H + 15) / 16);
-	if (Tt > FR_MAX_LDS_TILES) return fr_fail(FR_EINVAL, "fr_render_views: images beyond 4096 tiles are not supported");
-	if (fc->tile_capacity > 0)
-	{
-		const long long need = (long long)V * Tt * (long long)fc->tile_capacity;
-		if (need > max_rendered || need >= (1ll << 32)) return fr_fail(FR_EINVAL, "fr_render_views: n_views * tiles * tile_capacity exceeds max_rendered (or 2^32)");
-	}
 	if (!cfg->bg) return fr_fail(FR_EINVAL, "fr_render_views: null bg");
+	const int P = cfg->P, W = cfg->image_width, H = cfg->image_height, V = fc->n_views;
 	const FrFisherLayout L = fr_fisher_layout(P, W, H, V, max_rendered, 4);
 	if (!workspace || workspace_bytes < L.total)
 		return fr_fail(FR_ENOSPACE, "fr_render_views: workspace smaller than fr_render_views_workspace_bytes()");
@@ -8530,70 +8528,23 @@ extern "C" int fr_render_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	char* ws = (char*)workspace;
 	FrParams p;
 	fr_fill_params(p, cfg, g, V);
-	p.prefiltered = 0;
-	p.tile_cnt = (uint32_t*)(ws + L.tile_cnt);
-	p.tile_off = (uint32_t*)(ws + L.tile_off);
-	p.status = (int*)(ws + L.status);
-	p.keys = (uint64_t*)(ws + L.keys);
+	if ((rc = fr_carve_views(p, L, ws, fc, max_rendered, s, P > 0))) return rc;      // (no Gaussians: no front end fills the view map)
+	FrScorerPlan plan;
+	plan.form = FrRecForm::Render;
+	plan.columns = 4;
 	FrFisherArgs f;
 	memset(&f, 0, sizeof(f));
-	constexpr int rstride = FrRecStride<4, 4>::value;
-	f.recA = (const float4*)(ws + L.recq); f.ab_view = (long long)L.PV * rstride; f.ab_stride = rstride;
+	fr_wire_records(plan, f, L, ws, FrRecStride<4, 4>::value, false);
 	if (P == 0)
 	{
 		// no Gaussians: every list is empty, the tile kernel writes the background, 15.0 and T = 1
 		(void)hipMemsetAsync(p.tile_cnt, 0, (size_t)V * p.T * 4, s);
 		(void)hipMemsetAsync(p.tile_off, 0, (size_t)V * p.T * 4, s);
-		(void)hipMemsetAsync(p.status, 0, 16, s);
-		if (fc->out_vis_count) (void)hipMemsetAsync(fc->out_vis_count, 0, (size_t)V * 4, s);
-		if (fc->out_num_rendered) (void)hipMemsetAsync(fc->out_num_rendered, 0, (size_t)V * 4, s);
+		fr_empty_map(fc, p.status, s);
 	}
 	else
 	{
-		p.w2c = fc->w2c;
-		if (fc->poses_are_c2w)
-		{
-			float* inv = (float*)(ws + L.w2c_inv);
-			hipLaunchKernelGGL(k_invert_poses, dim3((V + 63) / 64), dim3(64), 0, s, V, fc->w2c, inv);
-			if ((rc = fr_check_launch("k_invert_poses"))) return rc;
-			p.w2c = inv;
-		}
-		p.radii = (int*)(ws + L.radii);
-		p.vis_list = (FrVisEntry*)(ws + L.radii);
-		p.vis_n = (uint32_t*)(ws + L.vis_n);
-		p.splat = (FrSplat*)(ws + L.splat);
-		p.cov3D_out = (float*)(ws + L.cov3D);
-		p.tile_fill = (uint32_t*)(ws + L.tile_fill);
-		p.big_list = (uint32_t*)(ws + L.big_list);
-		p.part_list = (uint32_t*)(ws + L.part_list);
-		const bool deal = (V & 7) == 0 && V <= 1024;
-		p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
-		p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;
-		p.blk_base = (uint32_t*)(ws + L.blk_base);
-		p.key_capacity = max_rendered;
-		if (fc->tile_capacity > 0)
-		{
-			// fixed key segments where the compact-record front end can address them (as fr_fisher_views decides it)
-			const long long nblk_c = (P + FR_THREADS * fr_pick_G_views(P) - 1) / (FR_THREADS * fr_pick_G_views(P));
-			const bool slots_fit = nblk_c * FR_THREADS * fr_pick_G_views(P) < (1ll << 28);
-			if (p.gx <= 255u && p.gy <= 63u && slots_fit) p.tile_cap = (uint32_t)fc->tile_capacity;
-		}
-		(void)fr_plan_views_c(p.T, fr_pick_VC(p.T), p.tile_cap);
-		p.vis_count = fc->out_vis_count;
-		p.num_rendered = fc->out_num_rendered;
-		p.order = fc->order;
-		FrScorerPlan plan;
-		plan.columns = 4;
-		plan.form_a = false;
-		plan.render = true;
-		plan.ra.H_inv = nullptr; plan.ra.hinv_stride = 0;
-		plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
-		plan.ra.comp = (float4*)(ws + L.recq);
-		plan.ra.stride = rstride;
-		plan.ra.slot_idx = nullptr;
-		plan.ra.mt = (const float4*)(ws + L.mt);
-		plan.ra.grp = (const float4*)(ws + L.grp);
-		plan.ra.early = 1;
+		fr_plan_fixed_segments(p, fc->tile_capacity);
 		if ((rc = fr_bin_pipeline(p, g, s, &plan))) return rc;
 		f.key_shift = p.tile_cap ? 4 : 0;                   // (fixed segments: keys = depth | slot << 4 | strips)
 	}
@@ -8623,7 +8574,7 @@ extern "C" int fr_fisher_point_workspace_layout(int32_t P, int32_t W, int32_t H,
 	    (long long)((W + 15) / 16) * ((H + 15) / 16) > FR_MAX_LDS_TILES)
 		return fr_fail(FR_EINVAL, "fr_fisher_point_workspace_layout: bad argument");
 	const FrFisherLayout L = fr_fisher_layout(P, W, H, n_views, max_rendered, columns);
-	o[0] = L.tile_cnt; o[1] = L.tile_off; o[2] = L.keys; o[3] = L.splat; o[4] = L.recq; o[5] = L.tile_scores; o[6] = L.status; o[7] = L.vis_n;
+	fr_export_offsets(L, o);
 	o[8] = L.total;
 	return FR_OK;
 }
@@ -8635,7 +8586,7 @@ extern "C" int fr_fisher_point_views(const fr_raster_cfg* cfg, const fr_gaussian
 	// every argument check comes before any device work
 	int rc = fr_validate(cfg, g, "fr_fisher_point_views");
 	if (rc) return rc;
-	if (!fc || fc->n_views <= 0 || !fc->w2c || !status) return fr_fail(FR_EINVAL, "fr_fisher_point_views: bad fisher cfg or null status");
+	if ((rc = fr_check_views("fr_fisher_point_views", "bad fisher cfg or null status", FR_CHK_ALL, cfg, fc, max_rendered, status))) return rc;
 	if (fc->columns != 4 && fc->columns != 11) return fr_fail(FR_EINVAL, "fr_fisher_point_views: columns must be 4 or 11");
 	if (fc->out_H) return fr_fail(FR_EINVAL, "fr_fisher_point_views: out_H is for fr_fisher_views");
 	if (fc->dL_dpix_image) return fr_fail(FR_EINVAL, "fr_fisher_point_views: no per-pixel upstream-gradient images (constant dL_dpix only)");
@@ -8644,107 +8595,43 @@ extern "C" int fr_fisher_point_views(const fr_raster_cfg* cfg, const fr_gaussian
 	if (!out_point_scores && !out_point_max) return fr_fail(FR_EINVAL, "fr_fisher_point_views: no output requested");
 	if (!g->colors_precomp) return fr_fail(FR_EINVAL, "fr_fisher_point_views: needs colors_precomp");
 	if (g->cov3D_precomp || !(g->scales && g->rotations)) return fr_fail(FR_EINVAL, "fr_fisher_point_views: needs scales and rotations (no cov3D_precomp)");
-	if (fc->tile_capacity < 0) return fr_fail(FR_EINVAL, "fr_fisher_point_views: negative tile_capacity");
-	if (max_rendered < 0) return fr_fail(FR_EINVAL, "fr_fisher_point_views: negative max_rendered");
 	const int P = cfg->P, W = cfg->image_width, H = cfg->image_height, V = fc->n_views, C = fc->columns;
-	const long long Tt = (long long)((W + 15) / 16) * ((H + 15) / 16);
-	if (Tt > FR_MAX_LDS_TILES) return fr_fail(FR_EINVAL, "fr_fisher_point_views: images beyond 4096 tiles are not supported");
-	if (fc->tile_capacity > 0)
-	{
-		const long long need = (long long)V * Tt * (long long)fc->tile_capacity;
-		if (need > max_rendered || need >= (1ll << 32)) return fr_fail(FR_EINVAL, "fr_fisher_point_views: n_views * tiles * tile_capacity exceeds max_rendered (or 2^32)");
-	}
 	hipStream_t s = (hipStream_t)stream;
 	if (P == 0)
 	{
-		if (fc->out_scores) (void)hipMemsetAsync(fc->out_scores, 0, (size_t)V * 4, s);
-		if (fc->out_vis_count) (void)hipMemsetAsync(fc->out_vis_count, 0, (size_t)V * 4, s);
-		if (fc->out_num_rendered) (void)hipMemsetAsync(fc->out_num_rendered, 0, (size_t)V * 4, s);
-		(void)hipMemsetAsync(status, 0, 16, s);
+		fr_empty_map(fc, status, s);
 		return fr_check_launch("fr_fisher_point_views (no Gaussians)");
 	}
 	const FrFisherLayout L = fr_fisher_layout(P, W, H, V, max_rendered, C);
 	if (!workspace || workspace_bytes < fr_point_total(P, W, H, V, max_rendered, C))
 		return fr_fail(FR_ENOSPACE, "fr_fisher_point_views: workspace smaller than fr_fisher_point_workspace_bytes()");
-	const long long G = fr_pick_G_views(P);
-	const long long nblk_c = (P + FR_THREADS * G - 1) / (FR_THREADS * G);
+	const long long G = fr_pick_G_views(P), nblk_c = fr_view_blocks(P);
 	if ((long long)V * nblk_c * G >= (1ll << 31)) return fr_fail(FR_EINVAL, "fr_fisher_point_views: too many (view, slot) groups for one launch");
 	char* ws = (char*)workspace;
 	FrParams p;
 	fr_fill_params(p, cfg, g, V);
-	p.prefiltered = 0;
-	p.w2c = fc->w2c;
-	if (fc->poses_are_c2w)
-	{
-		float* inv = (float*)(ws + L.w2c_inv);
-		hipLaunchKernelGGL(k_invert_poses, dim3((V + 63) / 64), dim3(64), 0, s, V, fc->w2c, inv);
-		if ((rc = fr_check_launch("k_invert_poses"))) return rc;
-		p.w2c = inv;
-	}
-	p.radii = (int*)(ws + L.radii);
-	p.vis_list = (FrVisEntry*)(ws + L.radii);
-	p.vis_n = (uint32_t*)(ws + L.vis_n);
-	p.splat = (FrSplat*)(ws + L.splat);
-	p.cov3D_out = (float*)(ws + L.cov3D);
-	p.tile_cnt = (uint32_t*)(ws + L.tile_cnt);
-	p.tile_off = (uint32_t*)(ws + L.tile_off);
-	p.tile_fill = (uint32_t*)(ws + L.tile_fill);
-	p.status = (int*)(ws + L.status);
-	p.big_list = (uint32_t*)(ws + L.big_list);
-	p.part_list = (uint32_t*)(ws + L.part_list);
-	const bool deal = (V & 7) == 0 && V <= 1024;
-	p.view_work = deal ? (uint32_t*)(ws + L.view_work) : nullptr;
-	p.view_perm = deal ? (uint32_t*)(ws + L.view_perm) : nullptr;
-	p.blk_base = (uint32_t*)(ws + L.blk_base);
-	p.keys = (uint64_t*)(ws + L.keys);
-	p.key_capacity = max_rendered;
-	if (fc->tile_capacity > 0)
-	{
-		// fixed key segments where the compact-record front end can address them (as fr_fisher_views decides it)
-		const bool slots_fit = nblk_c * FR_THREADS * G < (1ll << 28);
-		if (p.gx <= 255u && p.gy <= 63u && slots_fit) p.tile_cap = (uint32_t)fc->tile_capacity;
-	}
-	(void)fr_plan_views_c(p.T, fr_pick_VC(p.T), p.tile_cap);
-	p.vis_count = fc->out_vis_count;
-	p.num_rendered = fc->out_num_rendered;
-	p.order = fc->order;
+	if ((rc = fr_carve_views(p, L, ws, fc, max_rendered, s))) return rc;
+	fr_plan_fixed_segments(p, fc->tile_capacity);
 	const int rstride = p.tile_cap ? 5 : 6;            // the score form: 80 bytes with fixed key segments, else 96
 	float* slot_acc = (float*)(ws + L.total);
 	FrScorerPlan plan;
+	plan.form = FrRecForm::Point;
 	plan.columns = C;
-	plan.form_a = false;
-	plan.point = true;
-	plan.ra.H_inv = fc->H_inv; plan.ra.hinv_stride = fc->H_inv_view_stride;
-	plan.ra.packed = (const float*)(ws + L.packed); plan.ra.recq = (float4*)(ws + L.recq);
-	plan.ra.comp = (float4*)(ws + L.recq);
-	plan.ra.stride = rstride;
-	plan.ra.slot_idx = (uint32_t*)(ws + L.slot_idx);
-	plan.ra.slot_acc = slot_acc;
-	plan.ra.mt = (const float4*)(ws + L.mt);
-	plan.ra.grp = (const float4*)(ws + L.grp);
-	plan.ra.early = 1;
 	FrFisherArgs f;
 	memset(&f, 0, sizeof(f));
 	f.dL = fc->dL_dpix;
 	f.tile_scores = (float*)(ws + L.tile_scores);
 	f.debug_mode = fr_debug_mode();
-	f.recA = plan.ra.comp; f.ab_view = (long long)L.PV * rstride; f.ab_stride = rstride;
-	f.slot_idx = plan.ra.slot_idx; f.slot_view = (long long)L.PV;
+	fr_wire_records(plan, f, L, ws, rstride, true);
+	plan.ra.H_inv = fc->H_inv; plan.ra.hinv_stride = fc->H_inv_view_stride;
+	plan.ra.slot_acc = slot_acc;
 	if ((rc = fr_bin_pipeline(p, g, s, &plan))) return rc;
 	if ((p.tile_cap ? 5 : 6) != rstride) return fr_fail(FR_EINVAL, "fr_fisher_point_views: the front end left the planned key form");
 	f.key_shift = p.tile_cap ? 4 : 0;                   // (fixed segments: keys = depth | slot << 4 | strips)
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	if (g_prof_on)
 	{
-		(void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
-		(void)hipEventRecord(ev0, s);
-	}
-	if (p.tile_cap) hipLaunchKernelGGL((k_fisher_point_tile<true>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, slot_acc);
-	else hipLaunchKernelGGL((k_fisher_point_tile<false>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, slot_acc);
-	if (g_prof_on)
-	{
-		(void)hipEventRecord(ev1, s);
-		g_prof_events.push_back(std::make_pair(ev0, ev1));
+		FrProfSpan span(s);
+		if (p.tile_cap) hipLaunchKernelGGL((k_fisher_point_tile<true>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, slot_acc);
+		else hipLaunchKernelGGL((k_fisher_point_tile<false>), dim3(p.T * V), dim3(FR_THREADS), 0, s, p, f, slot_acc);
 	}
 	if ((rc = fr_check_launch("k_fisher_point_tile"))) return rc;
 	if (out_point_scores)

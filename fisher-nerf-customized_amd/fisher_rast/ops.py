@@ -310,7 +310,7 @@ class FisherScorer:
                                  and bool(torch.equal(self.view.reshape(4, 4).cpu(), torch.eye(4, dtype=self.view.dtype))))
         self._ws = {}
         self._static_key, self._static_hinv = None, None
-        self.per_view_capacity = max(int(0.75 * self.P), 1 << 16)
+        self.per_view_capacity = int(max(0.75 * self.P, 1 << 16))
         # Fixed key segments (fr_fisher_cfg.tile_capacity): every (view, tile) owns `tile_capacity` key slots, the projection
         # kernel places the keys itself and the scan / scatter kernels drop out of the launch sequence.  16384 keys (the largest
         # list the in-LDS sort tiers take) x 8 B = 128 KiB per tile -- 32 MiB per 256 x 256 view of the 288 GB; a longer list
@@ -374,25 +374,84 @@ class FisherScorer:
     def _keys_per_view(self):
         return max(self.per_view_capacity, self.tiles * self.tile_capacity)
 
-    def _workspace(self, V, max_rendered, slot=0):
-        nbytes = int(self.lib.fr_fisher_workspace_bytes(self.P, self.W, self.H, V, max_rendered, self.columns))
-        if nbytes == 0:
-            raise FisherRastError("fr_fisher_workspace_bytes: bad argument")
+    def _workspace(self, nbytes, slot=0):
+        """The workspace of `slot`, grown on demand and never shrunk.  Slot 0 is `launch`'s; "pose", "render" and "point" have one each,
+        so the packed static records of `launch` stay where they are."""
         ws = self._ws.get(slot)
         if ws is None or ws.numel() < nbytes:
             self._ws[slot] = None
             ws = self._ws[slot] = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
         return ws
 
+    def _batch(self, w2c, poses_are_c2w):
+        """What every batched launch starts with: (w2c [V,4,4] contiguous fp32 on the device, V, vis_count [V], num_rendered [V],
+        status [4], max_rendered, a FisherCfg with the fields all four entry points share), the spatial order brought up to date."""
+        d = self.dev
+        w2c = _prep(w2c.reshape(-1, 4, 4), d)
+        V = int(w2c.shape[0])
+        # zero-filled / fully written by the library itself (k_zero_many, k_scan_tiles, k_reduce_scores): no fill kernels here
+        vis = torch.empty((V,), dtype=torch.int32, device=d)
+        nr = torch.empty((V,), dtype=torch.int32, device=d)
+        status = torch.empty((4,), dtype=torch.int32, device=d)
+        self._sync_order()
+        fc = FisherCfg()
+        fc.n_views, fc.columns, fc.dL_dpix = V, self.columns, self.dL
+        fc.poses_are_c2w = 1 if poses_are_c2w else 0
+        fc.tile_capacity = self.tile_capacity if V * self.tiles * self.tile_capacity < (1 << 32) else 0
+        fc.w2c = ctypes.c_void_p(w2c.data_ptr())
+        fc.out_vis_count = vis.data_ptr()
+        fc.out_num_rendered = nr.data_ptr()
+        fc.order = self.order.data_ptr() if self.order is not None else None
+        return w2c, V, vis, nr, status, V * self._keys_per_view(), fc
+
+    def _call(self, name, fc, outputs, ws, max_rendered, status):
+        """One batched entry point of the library on this scorer's device and the current stream; `outputs`: the pointers it takes
+        between the fisher cfg and the workspace."""
+        with torch.cuda.device(self.dev):
+            _lib.check(getattr(self.lib, name)(ctypes.byref(self.cfg), ctypes.byref(self.g), ctypes.byref(fc), *outputs,
+                                               ws.data_ptr(), ws.numel(), max_rendered, status.data_ptr(), _stream(self.dev)), name)
+
+    def _chunks(self, V, launch):
+        """The launches that cover V views: `launch(v0, v1)` enqueues views [v0, v1) and returns the dict of its `*_launch` method;
+        yields those dicts, one per chunk of at most `max_views_per_launch()` views.  One read of the 16-byte status word per
+        attempt.  On overflow NOTHING was scored, accumulated or written (every kernel behind the scan returns on the overflow flag,
+        include/fisher_rast.h), so outputs are as they were: the buffers grow and the chunk -- a shorter one where the larger
+        buffers ask for it, which is why `launch` slices per call -- is redone.
+        status[3]: bit 0 = a tile list longer than its fixed segment (k_tile_lists, every entry point), bit 1 = the camera's view
+        matrix is not the identity `view_is_identity` promised (k_preprocess_views_c of fr_fisher_views alone: only `launch` sets
+        the hint); nothing else is written there, the batched entry points clear `prefiltered`."""
+        chunk = self.max_views_per_launch()
+        v0 = 0
+        while v0 < V:
+            v1 = min(V, v0 + chunk)
+            while True:
+                r = launch(v0, v1)
+                st = r["status"].cpu()
+                if int(st[1]) == 0:
+                    break
+                if int(st[3]) & 2:
+                    raise FisherRastError("FisherScorer.view_is_identity is set, but the camera's view matrix is not the identity "
+                                          "(nothing was scored)")
+                if int(st[3]) & 1:
+                    # (st[2] = the longest list) longer segments, or packed lists
+                    want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
+                    self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0
+                self.per_view_capacity = max(self.per_view_capacity, int(int(st[0]) * 1.25 / (v1 - v0)) + 4096)
+                chunk = min(chunk, self.max_views_per_launch())
+                v1 = min(v1, v0 + chunk)
+            yield r
+            v0 = v1
+
     def launch(self, w2c, H_inv=None, H_inv_per_view=False, out_H=None, out_H_per_view=False, dL_image=None, poses_are_c2w=False):
         """Enqueue one batch (no sync).  w2c: [V,4,4] world->camera on the device (camera->world with `poses_are_c2w`: the
         library inverts them).
         Returns a dict of device tensors: scores [V] (if H_inv), vis_count [V], num_rendered [V], status [4]."""
         d = self.dev
-        w2c = _prep(w2c.reshape(-1, 4, 4), d)
-        V = int(w2c.shape[0])
-        C = self.columns
-        PC = self.P * C
+        # ONE fr_fisher_views call per launch: a call accumulates into out_H all or nothing (overflow: nothing), which is what lets
+        # `run` simply redo a batch.  (Round 3 could cut a batch into view groups on separate streams; it measured slower -- 2.47 ms
+        # against 2.08 ms per step -- and a group that had not overflowed would have been added to out_H twice by the redo.)
+        w2c, V, vis, nr, status, max_rendered, fc = self._batch(w2c, poses_are_c2w)
+        PC = self.P * self.columns
         scores = None
         if H_inv is not None:
             H_inv = _prep(H_inv, d)
@@ -400,47 +459,30 @@ class FisherScorer:
             if H_inv.numel() != want:
                 raise ValueError(f"H_inv has {H_inv.numel()} elements, expected {want}")
             scores = torch.empty((V,), dtype=torch.float32, device=d)     # every element is written (or the status word says overflow)
-        if out_H is not None:
-            want = (V * PC) if out_H_per_view else PC
-            if out_H.numel() != want or out_H.dtype != torch.float32 or not out_H.is_contiguous() or out_H.device != d:
-                raise ValueError("out_H must be a contiguous fp32 device tensor of [V,]P*columns elements")
-        HW3 = 3 * int(self.rs.image_height) * int(self.rs.image_width)
-        if dL_image is not None:
-            # per view an upstream-gradient image [V,3,H,W] (or one [3,H,W] shared): the random probes of the POp-GS estimators
-            if out_H is None or H_inv is not None:
-                raise ValueError("dL_image goes with out_H (no H_inv)")
-            dL_image = _prep(dL_image, d)
-            if dL_image.numel() not in (HW3, V * HW3):
-                raise ValueError(f"dL_image has {dL_image.numel()} elements, expected {HW3} or {V * HW3}")
-        # zero-filled / fully written by the library itself (k_zero_many, k_scan_tiles, k_reduce_scores): no fill kernels here
-        vis = torch.empty((V,), dtype=torch.int32, device=d)
-        nr = torch.empty((V,), dtype=torch.int32, device=d)
-        status = torch.empty((4,), dtype=torch.int32, device=d)
-        # ONE fr_fisher_views call per launch: a call accumulates into out_H all or nothing (overflow: nothing), which is what lets
-        # `run` simply redo a batch.  (Round 3 could cut a batch into view groups on separate streams; it measured slower -- 2.47 ms
-        # against 2.08 ms per step -- and a group that had not overflowed would have been added to out_H twice by the redo.)
-        max_rendered = V * self._keys_per_view()
-        ws = self._workspace(V, max_rendered)
-        self._sync_order()
-        fc = FisherCfg()
-        fc.n_views, fc.columns, fc.dL_dpix = V, C, self.dL
-        fc.poses_are_c2w = 1 if poses_are_c2w else 0
-        fc.tile_capacity = self.tile_capacity if V * self.tiles * self.tile_capacity < (1 << 32) else 0
-        fc.w2c = ctypes.c_void_p(w2c.data_ptr())
-        if H_inv is not None:
             fc.H_inv = ctypes.c_void_p(H_inv.data_ptr())
             fc.H_inv_view_stride = PC if H_inv_per_view else 0
             fc.out_scores = ctypes.c_void_p(scores.data_ptr())
         if out_H is not None:
+            want = (V * PC) if out_H_per_view else PC
+            if out_H.numel() != want or out_H.dtype != torch.float32 or not out_H.is_contiguous() or out_H.device != d:
+                raise ValueError("out_H must be a contiguous fp32 device tensor of [V,]P*columns elements")
             fc.out_H = ctypes.c_void_p(out_H.data_ptr())
             fc.out_H_view_stride = PC if out_H_per_view else 0
         if dL_image is not None:
+            # per view an upstream-gradient image [V,3,H,W] (or one [3,H,W] shared): the random probes of the POp-GS estimators
+            if out_H is None or H_inv is not None:
+                raise ValueError("dL_image goes with out_H (no H_inv)")
+            HW3 = 3 * int(self.rs.image_height) * int(self.rs.image_width)
+            dL_image = _prep(dL_image, d)
+            if dL_image.numel() not in (HW3, V * HW3):
+                raise ValueError(f"dL_image has {dL_image.numel()} elements, expected {HW3} or {V * HW3}")
             fc.dL_dpix_image = ctypes.c_void_p(dL_image.data_ptr())
             fc.dL_image_view_stride = HW3 if dL_image.numel() != HW3 else 0
-        fc.out_vis_count = vis.data_ptr()
-        fc.out_num_rendered = nr.data_ptr()
-        fc.order = self.order.data_ptr() if self.order is not None else None
         fc.view_is_identity = 1 if self.view_is_identity else 0
+        nbytes = int(self.lib.fr_fisher_workspace_bytes(self.P, self.W, self.H, V, max_rendered, self.columns))
+        if nbytes == 0:
+            raise FisherRastError("fr_fisher_workspace_bytes: bad argument")
+        ws = self._workspace(nbytes)
         # the per-Gaussian static records (means, cov3D, colours, shared H_inv rows) are packed into the workspace by every call; a call
         # that finds there what it would write -- same workspace and layout, same shared H_inv tensor in the same version, the map's
         # tensors (and the order) at the same addresses in the same versions -- skips that kernel (fr_fisher_cfg.reuse_static)
@@ -453,11 +495,7 @@ class FisherScorer:
             skey = None
         fc.reuse_static = 1 if (skey is not None and self._static_key == skey and self._static_hinv is shared) else 0
         self._static_key, self._static_hinv = None, None            # (set again once the call has been enqueued without an error)
-        with torch.cuda.device(d):
-            _lib.check(self.lib.fr_fisher_views(ctypes.byref(self.cfg), ctypes.byref(self.g), ctypes.byref(fc),
-                                                ws.data_ptr(), ws.numel(), max_rendered,
-                                                status.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)),
-                       "fr_fisher_views")
+        self._call("fr_fisher_views", fc, (), ws, max_rendered, status)
         self._static_key, self._static_hinv = skey, shared
         return dict(scores=scores, vis_count=vis, num_rendered=nr, status=status, n_views=V, _keep=(w2c, H_inv, dL_image))
 
@@ -465,44 +503,13 @@ class FisherScorer:
         """launch() + overflow handling.  Synchronises once (to read the 16-byte status word)."""
         w2c = w2c.reshape(-1, 4, 4)
         V = int(w2c.shape[0])
-        chunk = self.max_views_per_launch()
-        outs = []
-        v0 = 0
-        while v0 < V:
-            v1 = min(V, v0 + chunk)
-            hi = H_inv
-            if H_inv is not None and H_inv_per_view:
-                hi = H_inv.reshape(V, -1)[v0:v1]
-            oh = out_H
-            if out_H is not None and out_H_per_view:
-                oh = out_H.view(V, -1)[v0:v1]
-            while True:
-                dl = dL_image
-                if dL_image is not None and dL_image.dim() == 4 and dL_image.shape[0] == V:
-                    dl = dL_image[v0:v1]
-                r = self.launch(w2c[v0:v1], hi, H_inv_per_view, oh, out_H_per_view, dl, poses_are_c2w)
-                st = r["status"].cpu()
-                if int(st[1]) == 0:
-                    break
-                if int(st[3]) & 2:
-                    raise FisherRastError("FisherScorer.view_is_identity is set, but the camera's view matrix is not the identity "
-                                          "(nothing was scored)")
-                # tile-instance buffer too small: NOTHING was scored or accumulated (every kernel behind the scan returns on the
-                # overflow flag, include/fisher_rast.h), so out_H is as it was: grow and redo this chunk
-                if int(st[3]) & 1:
-                    # a tile list longer than its fixed segment (st[2] = the longest): longer segments, or packed lists
-                    want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
-                    self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0
-                self.per_view_capacity = max(self.per_view_capacity, int(int(st[0]) * 1.25 / (v1 - v0)) + 4096)
-                chunk = min(chunk, self.max_views_per_launch())
-                if v1 - v0 > chunk:
-                    v1 = v0 + chunk
-                    if H_inv is not None and H_inv_per_view:
-                        hi = H_inv.reshape(V, -1)[v0:v1]
-                    if out_H is not None and out_H_per_view:
-                        oh = out_H.view(V, -1)[v0:v1]
-            outs.append(r)
-            v0 = v1
+
+        def launch(v0, v1):
+            hi = H_inv.reshape(V, -1)[v0:v1] if (H_inv is not None and H_inv_per_view) else H_inv
+            oh = out_H.view(V, -1)[v0:v1] if (out_H is not None and out_H_per_view) else out_H
+            dl = dL_image[v0:v1] if (dL_image is not None and dL_image.dim() == 4 and dL_image.shape[0] == V) else dL_image
+            return self.launch(w2c[v0:v1], hi, H_inv_per_view, oh, out_H_per_view, dl, poses_are_c2w)
+        outs = list(self._chunks(V, launch))
         res = dict(vis_count=torch.cat([o["vis_count"] for o in outs]),
                    num_rendered=torch.cat([o["num_rendered"] for o in outs]))
         res["scores"] = torch.cat([o["scores"] for o in outs]) if H_inv is not None else None
@@ -514,37 +521,15 @@ class FisherScorer:
         a contiguous fp32 device tensor of 36 V elements), vis_count [V], num_rendered [V], status [4].  Its own workspace: the packed
         static records of `launch` stay where they are."""
         d = self.dev
-        w2c = _prep(w2c.reshape(-1, 4, 4), d)
-        V = int(w2c.shape[0])
+        w2c, V, vis, nr, status, max_rendered, fc = self._batch(w2c, poses_are_c2w)
         if out is not None and (out.numel() != 36 * V or out.dtype != torch.float32 or not out.is_contiguous() or out.device != d):
             raise ValueError("out must be a contiguous fp32 device tensor of V*36 elements")
         # every element is written (or the status word says overflow, and none is)
         pose_H = out.view(V, 6, 6) if out is not None else torch.empty((V, 6, 6), dtype=torch.float32, device=d)
-        vis = torch.empty((V,), dtype=torch.int32, device=d)
-        nr = torch.empty((V,), dtype=torch.int32, device=d)
-        status = torch.empty((4,), dtype=torch.int32, device=d)
-        max_rendered = V * self._keys_per_view()
         nbytes = int(self.lib.fr_fisher_pose_workspace_bytes(self.P, self.W, self.H, V, max_rendered))
         if nbytes == 0:
             raise FisherRastError("fr_fisher_pose_workspace_bytes: bad argument")
-        ws = self._ws.get("pose")
-        if ws is None or ws.numel() < nbytes:
-            self._ws["pose"] = None
-            ws = self._ws["pose"] = torch.empty((nbytes,), dtype=torch.uint8, device=d)
-        self._sync_order()
-        fc = FisherCfg()
-        fc.n_views, fc.columns, fc.dL_dpix = V, self.columns, self.dL
-        fc.poses_are_c2w = 1 if poses_are_c2w else 0
-        fc.tile_capacity = self.tile_capacity if V * self.tiles * self.tile_capacity < (1 << 32) else 0
-        fc.w2c = ctypes.c_void_p(w2c.data_ptr())
-        fc.out_vis_count = vis.data_ptr()
-        fc.out_num_rendered = nr.data_ptr()
-        fc.order = self.order.data_ptr() if self.order is not None else None
-        with torch.cuda.device(d):
-            _lib.check(self.lib.fr_fisher_pose_views(ctypes.byref(self.cfg), ctypes.byref(self.g), ctypes.byref(fc),
-                                                     ctypes.c_void_p(pose_H.data_ptr()), ws.data_ptr(), ws.numel(), max_rendered,
-                                                     status.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)),
-                       "fr_fisher_pose_views")
+        self._call("fr_fisher_pose_views", fc, (ctypes.c_void_p(pose_H.data_ptr()),), self._workspace(nbytes, "pose"), max_rendered, status)
         return dict(pose_H=pose_H, vis_count=vis, num_rendered=nr, status=status, n_views=V, _keep=(w2c,))
 
     def pose_fisher(self, w2c, poses_are_c2w=False):
@@ -553,28 +538,8 @@ class FisherScorer:
         `max_views_per_launch()` go in several calls; an overflow of the key buffer is redone with a larger one, as in `run`.
         Synchronises once per call (the status word).  The same for 4- and 11-column scorers."""
         w2c = w2c.reshape(-1, 4, 4)
-        V = int(w2c.shape[0])
-        chunk = self.max_views_per_launch()
-        outs = []
-        v0 = 0
-        while v0 < V:
-            v1 = min(V, v0 + chunk)
-            while True:
-                r = self.pose_launch(w2c[v0:v1], poses_are_c2w)
-                st = r["status"].cpu()
-                if int(st[1]) == 0:
-                    break
-                # overflow: nothing was written -- grow the key buffer (or the fixed segments) and redo this chunk
-                if int(st[3]):
-                    want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
-                    self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0
-                self.per_view_capacity = max(self.per_view_capacity, int(int(st[0]) * 1.25 / (v1 - v0)) + 4096)
-                chunk = min(chunk, self.max_views_per_launch())
-                v1 = min(v1, v0 + chunk)
-            outs.append(r["pose_H"])
-            v0 = v1
+        outs = [r["pose_H"] for r in self._chunks(int(w2c.shape[0]), lambda v0, v1: self.pose_launch(w2c[v0:v1], poses_are_c2w))]
         return torch.cat(outs) if outs else torch.zeros((0, 6, 6), dtype=torch.float32, device=self.dev)
-
 
     # -- batched render of candidate views (fr_render_views) -----------------------------------------------
     def render_launch(self, w2c, poses_are_c2w=False, features=True, depth=True, final_T=True, render=True, out=None):
@@ -584,8 +549,7 @@ class FisherScorer:
         `out`: a dict that may hold contiguous fp32 device tensors of those shapes under those four names, written instead of fresh ones.
         Its own workspace, as `pose_launch`: the packed static records of `launch` stay where they are."""
         d = self.dev
-        w2c = _prep(w2c.reshape(-1, 4, 4), d)
-        V = int(w2c.shape[0])
+        w2c, V, vis, nr, status, max_rendered, fc = self._batch(w2c, poses_are_c2w)       # (columns and dL_dpix are set too: the library ignores them here)
         H, W = self.H, self.W
         if not (render or features or depth or final_T):
             raise ValueError("render_launch: no output requested")
@@ -601,32 +565,11 @@ class FisherScorer:
             return t
         out = dict(render=new("render", V, 3, H, W) if render else None, depth_sil=new("depth_sil", V, 3, H, W) if features else None,
                    median_depth=new("median_depth", V, 1, H, W) if depth else None, final_T=new("final_T", V, H, W) if final_T else None)
-        vis = torch.empty((V,), dtype=torch.int32, device=d)
-        nr = torch.empty((V,), dtype=torch.int32, device=d)
-        status = torch.empty((4,), dtype=torch.int32, device=d)
-        max_rendered = V * self._keys_per_view()
         nbytes = int(self.lib.fr_render_views_workspace_bytes(self.P, W, H, V, max_rendered))
         if nbytes == 0:
             raise FisherRastError("fr_render_views_workspace_bytes: bad argument (or an image beyond 4096 tiles: render_views loops there)")
-        ws = self._ws.get("render")
-        if ws is None or ws.numel() < nbytes:
-            self._ws["render"] = None
-            ws = self._ws["render"] = torch.empty((nbytes,), dtype=torch.uint8, device=d)
-        self._sync_order()
-        fc = FisherCfg()
-        fc.n_views = V
-        fc.poses_are_c2w = 1 if poses_are_c2w else 0
-        fc.tile_capacity = self.tile_capacity if V * self.tiles * self.tile_capacity < (1 << 32) else 0
-        fc.w2c = ctypes.c_void_p(w2c.data_ptr())
-        fc.out_vis_count = vis.data_ptr()
-        fc.out_num_rendered = nr.data_ptr()
-        fc.order = self.order.data_ptr() if self.order is not None else None
-        with torch.cuda.device(d):
-            _lib.check(self.lib.fr_render_views(ctypes.byref(self.cfg), ctypes.byref(self.g), ctypes.byref(fc),
-                                                _ptr(out["render"]), _ptr(out["depth_sil"]), _ptr(out["median_depth"]), _ptr(out["final_T"]),
-                                                ws.data_ptr(), ws.numel(), max_rendered,
-                                                status.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)),
-                       "fr_render_views")
+        self._call("fr_render_views", fc, (_ptr(out["render"]), _ptr(out["depth_sil"]), _ptr(out["median_depth"]), _ptr(out["final_T"])),
+                   self._workspace(nbytes, "render"), max_rendered, status)
         out.update(vis_count=vis, num_rendered=nr, status=status, n_views=V, _keep=(w2c,))
         return out
 
@@ -708,25 +651,7 @@ class FisherScorer:
         V = int(w2c.shape[0])
         if self.tiles > 4096:
             return self._render_views_serial(w2c, poses_are_c2w, features, depth, final_T)
-        chunk = self.max_views_per_launch()
-        outs = []
-        v0 = 0
-        while v0 < V:
-            v1 = min(V, v0 + chunk)
-            while True:
-                r = self.render_launch(w2c[v0:v1], poses_are_c2w, features, depth, final_T)
-                st = r["status"].cpu()
-                if int(st[1]) == 0:
-                    break
-                # overflow: nothing was written -- grow the key buffer (or the fixed segments) and redo this chunk
-                if int(st[3]):
-                    want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
-                    self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0
-                self.per_view_capacity = max(self.per_view_capacity, int(int(st[0]) * 1.25 / (v1 - v0)) + 4096)
-                chunk = min(chunk, self.max_views_per_launch())
-                v1 = min(v1, v0 + chunk)
-            outs.append(r)
-            v0 = v1
+        outs = list(self._chunks(V, lambda v0, v1: self.render_launch(w2c[v0:v1], poses_are_c2w, features, depth, final_T)))
         names = ("render", "depth_sil", "median_depth", "final_T", "vis_count", "num_rendered")
         if len(outs) == 1:
             return {k: outs[0][k] for k in names}
@@ -749,8 +674,7 @@ class FisherScorer:
         scores [V], vis_count [V], num_rendered [V], status [4].  On overflow (status[1]) no output byte is written.
         Its own workspace, as `pose_launch`: the packed static records of `launch` stay where they are."""
         d = self.dev
-        w2c = _prep(w2c.reshape(-1, 4, 4), d)
-        V = int(w2c.shape[0])
+        w2c, V, vis, nr, status, max_rendered, fc = self._batch(w2c, poses_are_c2w)
         P, PC = self.P, self.P * self.columns
         if H_inv is None:
             raise ValueError("point_launch needs H_inv")
@@ -770,34 +694,13 @@ class FisherScorer:
             point = torch.empty((V, P), dtype=torch.float32, device=d)        # every element is written (or the status word says overflow)
         pmax = given(point_max, P, "point_max") if point_max is not None else torch.zeros((P,), dtype=torch.float32, device=d)
         scores = torch.empty((V,), dtype=torch.float32, device=d)
-        vis = torch.empty((V,), dtype=torch.int32, device=d)
-        nr = torch.empty((V,), dtype=torch.int32, device=d)
-        status = torch.empty((4,), dtype=torch.int32, device=d)
-        max_rendered = V * self._keys_per_view()
         nbytes = int(self.lib.fr_fisher_point_workspace_bytes(P, self.W, self.H, V, max_rendered, self.columns))
         if nbytes == 0:
             raise FisherRastError("fr_fisher_point_workspace_bytes: bad argument (or an image beyond 4096 tiles)")
-        ws = self._ws.get("point")
-        if ws is None or ws.numel() < nbytes:
-            self._ws["point"] = None
-            ws = self._ws["point"] = torch.empty((nbytes,), dtype=torch.uint8, device=d)
-        self._sync_order()
-        fc = FisherCfg()
-        fc.n_views, fc.columns, fc.dL_dpix = V, self.columns, self.dL
-        fc.poses_are_c2w = 1 if poses_are_c2w else 0
-        fc.tile_capacity = self.tile_capacity if V * self.tiles * self.tile_capacity < (1 << 32) else 0
-        fc.w2c = ctypes.c_void_p(w2c.data_ptr())
         fc.H_inv = ctypes.c_void_p(H_inv.data_ptr())
         fc.H_inv_view_stride = PC if H_inv_per_view else 0
         fc.out_scores = ctypes.c_void_p(scores.data_ptr())
-        fc.out_vis_count = vis.data_ptr()
-        fc.out_num_rendered = nr.data_ptr()
-        fc.order = self.order.data_ptr() if self.order is not None else None
-        with torch.cuda.device(d):
-            _lib.check(self.lib.fr_fisher_point_views(ctypes.byref(self.cfg), ctypes.byref(self.g), ctypes.byref(fc),
-                                                      _ptr(point), _ptr(pmax), ws.data_ptr(), ws.numel(), max_rendered,
-                                                      status.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)),
-                       "fr_fisher_point_views")
+        self._call("fr_fisher_point_views", fc, (_ptr(point), _ptr(pmax)), self._workspace(nbytes, "point"), max_rendered, status)
         return dict(point_scores=point, point_max=pmax, scores=scores, vis_count=vis, num_rendered=nr, status=status, n_views=V,
                     _keep=(w2c, H_inv))
 
@@ -813,26 +716,11 @@ class FisherScorer:
         if point_max is None:
             point_max = torch.zeros((P,), dtype=torch.float32, device=d)
         point = torch.empty((V, P), dtype=torch.float32, device=d) if per_view else None
-        chunk = self.max_views_per_launch()
-        outs = []
-        v0 = 0
-        while v0 < V:
-            v1 = min(V, v0 + chunk)
-            while True:
-                hi = H_inv.reshape(V, -1)[v0:v1] if H_inv_per_view else H_inv
-                r = self.point_launch(w2c[v0:v1], hi, H_inv_per_view, per_view, point[v0:v1] if per_view else None, point_max, poses_are_c2w)
-                st = r["status"].cpu()
-                if int(st[1]) == 0:
-                    break
-                # overflow: nothing was written -- grow the key buffer (or the fixed segments) and redo this chunk
-                if int(st[3]):
-                    want = (int(int(st[2]) * 1.25) + 1023) // 1024 * 1024
-                    self.tile_capacity = want if self.tiles * want * 8 <= self.MAX_KEY_BYTES_PER_VIEW else 0
-                self.per_view_capacity = max(self.per_view_capacity, int(int(st[0]) * 1.25 / (v1 - v0)) + 4096)
-                chunk = min(chunk, self.max_views_per_launch())
-                v1 = min(v1, v0 + chunk)
-            outs.append(r)
-            v0 = v1
+
+        def launch(v0, v1):
+            hi = H_inv.reshape(V, -1)[v0:v1] if H_inv_per_view else H_inv
+            return self.point_launch(w2c[v0:v1], hi, H_inv_per_view, per_view, point[v0:v1] if per_view else None, point_max, poses_are_c2w)
+        outs = list(self._chunks(V, launch))
 
         def cat(k, dtype):
             return torch.cat([o[k] for o in outs]) if outs else torch.zeros((0,), dtype=dtype, device=d)

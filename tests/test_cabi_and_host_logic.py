@@ -93,6 +93,88 @@ def test_argument_validation_without_gpu(lib):
     assert lib.fr_knn_dist2(-5, None, None, None, 0, None) == 1
 
 
+BATCHED = {   # entry point -> (output pointers between the fisher cfg and the workspace, fr_fisher_cfg fields it needs besides w2c)
+    "fr_fisher_views": (0, ("H_inv", "out_scores")),
+    "fr_fisher_pose_views": (1, ()),
+    "fr_render_views": (4, ()),
+    "fr_fisher_point_views": (2, ("H_inv",)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(BATCHED))
+def test_batched_entry_points_share_their_argument_checks(lib, name):
+    """The checks the four view-batched entry points share, each under the caller's own name and before any device work: host
+    addresses that nothing dereferences stand in for device memory.  Where fr_fisher_views differs, the difference is recorded."""
+    from fisher_rast._lib import RasterCfg, Gaussians, FisherCfg
+    n_out, needs = BATCHED[name]
+    buf = ctypes.create_string_buffer(64)
+    addr = ctypes.cast(buf, ctypes.c_void_p)
+    EINVAL, ENOSPACE, ROOMY = 1, 3, 1 << 40
+    views = name == "fr_fisher_views"
+
+    def call(edit=None, fc_null=False, status=addr, ws=None, ws_bytes=0, max_rendered=0):
+        cfg, g, fc = RasterCfg(), Gaussians(), FisherCfg()
+        cfg.P, cfg.image_width, cfg.image_height = 10, 64, 48                      # 12 tiles
+        cfg.bg = cfg.viewmatrix = cfg.projmatrix = addr
+        g.means3D = g.colors_precomp = g.opacities = g.scales = g.rotations = addr
+        fc.n_views, fc.columns, fc.dL_dpix, fc.w2c = 1, 4, 1e-3, addr
+        for f in needs:
+            setattr(fc, f, addr)
+        if edit:
+            edit(fc)
+        rc = getattr(lib, name)(ctypes.byref(cfg), ctypes.byref(g), None if fc_null else ctypes.byref(fc), *([addr] * n_out),
+                                ws, ws_bytes, max_rendered, status, None)
+        return rc, lib.fr_last_error()
+
+    def rejected(**kw):
+        rc, msg = call(**kw)
+        assert rc == EINVAL and msg.startswith(name.encode() + b":"), (kw, rc, msg)
+        return msg
+
+    rejected(fc_null=True)
+    rejected(edit=lambda fc: setattr(fc, "n_views", 0))
+    rejected(edit=lambda fc: setattr(fc, "w2c", None))
+    rejected(status=None)
+    # (a workspace that would do: fr_fisher_views looks at tile_capacity behind its workspace check, the others before it)
+    assert b"tile_capacity" in rejected(edit=lambda fc: setattr(fc, "tile_capacity", -1), ws=addr, ws_bytes=ROOMY)
+    assert b"exceeds max_rendered" in rejected(edit=lambda fc: setattr(fc, "tile_capacity", 1024), ws=addr, ws_bytes=ROOMY, max_rendered=12 * 1024 - 1)
+    rc, msg = call(edit=lambda fc: setattr(fc, "tile_capacity", 1024), max_rendered=12 * 1024)
+    assert rc == ENOSPACE and msg.startswith(name.encode() + b":") and b"workspace" in msg       # well-formed, as far as the workspace
+    assert call()[0] == ENOSPACE
+    # fr_fisher_views as it is: tile_capacity only behind the workspace check, and no check of max_rendered of its own
+    assert call(edit=lambda fc: setattr(fc, "tile_capacity", -1))[0] == (ENOSPACE if views else EINVAL)
+    rc, msg = call(max_rendered=-1)
+    assert rc == (ENOSPACE if views else EINVAL) and (views or b"max_rendered" in msg)
+
+
+def test_chunk_and_redo_driver_host_logic():
+    """FisherScorer._chunks on a stand-in scorer (no device): five views, three per launch until the buffers have grown and two from
+    then on.  The overflowed chunk is redone shorter, the growth follows the status word, bit 0 of status[3] alone grows the
+    segments, bit 1 raises, and no views means no launch."""
+    from fisher_rast.ops import FisherScorer
+    from fisher_rast._lib import FisherRastError
+
+    def stand_in(tile_capacity):
+        sc = FisherScorer.__new__(FisherScorer)
+        sc.tiles, sc.tile_capacity, sc.per_view_capacity = 12, tile_capacity, 64
+        sc.max_views_per_launch = lambda: 3 if sc.per_view_capacity == 64 else 2
+        return sc
+
+    for tile_capacity, st3 in ((16, 1), (0, 0)):
+        sc, calls = stand_in(tile_capacity), []
+
+        def launch(v0, v1):
+            calls.append((v0, v1))
+            st = [9000, 1, 700, st3] if sc.per_view_capacity == 64 else [9000, 0, 700, 0]
+            return dict(status=torch.tensor(st, dtype=torch.int32), views=(v0, v1))
+        assert [r["views"] for r in sc._chunks(5, launch)] == [(0, 2), (2, 4), (4, 5)]
+        assert calls == [(0, 3), (0, 2), (2, 4), (4, 5)]
+        assert sc.per_view_capacity == int(9000 * 1.25 / 3) + 4096 and sc.tile_capacity == (1024 if st3 else 0)
+    with pytest.raises(FisherRastError, match="view_is_identity"):
+        list(stand_in(16)._chunks(5, lambda v0, v1: dict(status=torch.tensor([0, 1, 0, 2], dtype=torch.int32))))
+    assert list(stand_in(0)._chunks(0, None)) == []
+
+
 def test_product_never_imports_oracle():
     """The oracle is test infrastructure: nothing under the product package may reference it."""
     pkg = os.path.join(ROOT, "fisher-nerf-customized_amd")
