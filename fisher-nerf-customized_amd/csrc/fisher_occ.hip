@@ -54,13 +54,23 @@ struct OccUpdateArgs {
 	int cam_col, cam_row;
 };
 
-// astar.py:214: occ_map[2, cam_z-1:cam_z+2, cam_x-1:cam_x+2] = 1e3 (clipped to the map like the slice)
+// one bound of a Python slice over `dim` entries: a negative bound counts from the end, then both clamp to [0, dim]
+__device__ __forceinline__ int occ_slice_bound(int v, int dim)
+{
+	if (v < 0) v += dim;
+	v = v < 0 ? 0 : v;
+	return v > dim ? dim : v;
+}
+
+// astar.py:214: occ_map[2, cam_z-1:cam_z+2, cam_x-1:cam_x+2] = 1e3 with the slice's own rules: past the last row / column
+// the block is clipped, but in row 0 (column 0) the slice starts at -1, which counts from the end, and is EMPTY: nothing is
+// written (AstarPlanner.init marks its block with the same slice)
 __global__ void k_occ_mark_cam(OccUpdateArgs a, float* __restrict__ occ_map)
 {
 	const int t = threadIdx.x;
 	if (t >= 9) return;
-	const int r = a.cam_row - 1 + t / 3, c = a.cam_col - 1 + t % 3;
-	if (r < 0 || r >= a.g.gh || c < 0 || c >= a.g.gw) return;
+	const int r = occ_slice_bound(a.cam_row - 1, a.g.gh) + t / 3, c = occ_slice_bound(a.cam_col - 1, a.g.gw) + t % 3;
+	if (r >= occ_slice_bound(a.cam_row + 2, a.g.gh) || c >= occ_slice_bound(a.cam_col + 2, a.g.gw)) return;
 	occ_map[(size_t)2 * a.g.gw * a.g.gh + (size_t)r * a.g.gw + c] = 1e3f;
 }
 

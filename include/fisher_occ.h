@@ -46,7 +46,9 @@ size_t fr_occ_workspace_bytes(const fr_occ_cfg* cfg);
 /* update_occ_map.  depth: [H][W] float32 (device).  intr = {fx, fy, cx, cy} and c2w (row-major 4x4) are HOST arrays;
  * sample_fracs (HOST, n_samples <= 32): the fractions of the depth sampled along each ray, the last one being the depth
  * point itself (the reference: linspace(1e-3, 0.95, 11) with the last set to 1).  cam_col / cam_row: the camera's cell
- * (astar.py:211-213, computed by the caller exactly as the reference does on the host). */
+ * (astar.py:211-213, computed by the caller exactly as the reference does on the host).  The 3 x 3 block round it is
+ * marked with the rules of the reference's slice [cam-1 : cam+2]: clipped past the last row / column, empty when the
+ * camera is in row 0 or column 0 (the slice then starts at -1, which counts from the end). */
 int fr_occ_update(const fr_occ_cfg* cfg, const float* depth, int32_t W, int32_t H, int32_t downsample,
                   const float intr[4], const float c2w[16], const float* sample_fracs, int32_t n_samples,
                   int32_t cam_col, int32_t cam_row, float* occ_map,
