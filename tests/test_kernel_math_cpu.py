@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import cameras as C
 from scenes import random_scene, intrinsics, rel_err
 
 c_f = ctypes.POINTER(ctypes.c_float)
@@ -25,21 +26,36 @@ def test_expf_bit_exact(oracle, harness):
     assert np.array_equal(y.view(np.uint32), oracle.expf(x).view(np.uint32))
 
 
-@pytest.mark.parametrize("W,H,seed", [(256, 256, 0), (200, 120, 1), (64, 48, 2)])
-def test_preprocess_bit_exact(oracle, harness, W, H, seed):
+# the unit camera at three image sizes (W, H, seed), then every camera of tests/cameras.py with every scale modifier (camera, modifier, seed)
+PREPROCESS = [(256, 256, 0), (200, 120, 1), (64, 48, 2)] + [(cam, mod, 3 + k) for k, cam in enumerate(C.CAMERAS) for mod in (1.0, 1.7, 0.4)]
+
+
+@pytest.mark.parametrize("which", PREPROCESS, ids=lambda w: f"{w[0]}-{w[1]}-{w[2]}" if isinstance(w[0], int) else f"{w[0]}-m{w[1]:g}")
+def test_preprocess_bit_exact(oracle, harness, which):
     P = 5000
-    sc = random_scene(P, seed, zmin=-0.5, zmax=8.0, spread=1.6, scale=0.05)
-    # a few splats hugging the camera (appendix B.1) and far outside the frustum (B.2)
-    sc["means3D"][:50, 2] = np.random.default_rng(seed).uniform(0.0005, 0.2, 50)
-    sc["means3D"][50:100, 0] *= 4
     w2c = np.eye(4, dtype=np.float32)
     w2c[:3, :3] = np.array([[0.96, 0, 0.28], [0, 1, 0], [-0.28, 0, 0.96]], np.float32)
     w2c[:3, 3] = [0.3, -0.1, 0.2]
-    cam = oracle.setup_camera(W, H, intrinsics(W, H), w2c)
+    if isinstance(which[0], int):
+        W, H, seed = which
+        mod = 1.0
+        sc = random_scene(P, seed, zmin=-0.5, zmax=8.0, spread=1.6, scale=0.05)
+        cam = oracle.setup_camera(W, H, intrinsics(W, H), w2c)
+    else:
+        c = C.case(which[0], which[1], w2c)
+        W, H, mod, seed = c.W, c.H, c.scale_modifier, which[2]
+        sc = C.frustum_scene(c, P, seed, zmin=-0.5, zmax=8.0, scale=0.05)
+        cam = C.oracle_camera(oracle, c)
+    # a few splats hugging the camera (appendix B.1) and far outside the frustum (B.2)
+    sc["means3D"][:50, 2] = np.random.default_rng(seed).uniform(0.0005, 0.2, 50)
+    sc["means3D"][50:100, 0] *= 4
     fwd = oracle.rasterize_forward(cam, sc["means3D"], sc["opacities"], colors_precomp=sc["colors"],
                                    scales=sc["scales"], rotations=sc["rotations"])
+    if not isinstance(which[0], int):
+        cx, cy = C.clamp_counts(oracle, cam, sc["means3D"], fwd)
+        assert cx >= 20 and cy >= 20, (cx, cy)
     cov3D = np.zeros((P, 6), np.float32)
-    harness.h_cov3d(ctypes.c_int(P), P_(sc["scales"]), ctypes.c_float(1.0), P_(sc["rotations"]), P_(cov3D))
+    harness.h_cov3d(ctypes.c_int(P), P_(sc["scales"]), ctypes.c_float(mod), P_(sc["rotations"]), P_(cov3D))
     vis = fwd["radii"] > 0
     assert np.array_equal(cov3D[vis], fwd["cov3D"][vis])
     radii = np.zeros(P, np.int32); depths = np.zeros(P, np.float32); m2d = np.zeros((P, 2), np.float32)
@@ -85,7 +101,8 @@ def test_sh_forward_bit_exact(oracle, harness, deg):
     assert np.array_equal(cl[vis], fwd["clamped"][vis])
 
 
-def test_leaf_jacobians_match_oracle_chain(oracle, harness):
+@pytest.mark.parametrize("mod", [1.0, 1.7])
+def test_leaf_jacobians_match_oracle_chain(oracle, harness, mod):
     """One Gaussian, one-hot pixel, power 1: the oracle's per-pair chain (backward.cu:276-475,532-583) gives
     u = (dL_dmean2D, dL_dconic) and the leaves; the kernels' Jacobian matrices applied to that u must agree."""
     W, H = 96, 64
@@ -93,14 +110,13 @@ def test_leaf_jacobians_match_oracle_chain(oracle, harness):
     w2c = np.eye(4, dtype=np.float32)
     w2c[:3, :3] = np.array([[0.8, 0, 0.6], [0, 1, 0], [-0.6, 0, 0.8]], np.float32)
     w2c[:3, 3] = [0.1, 0.05, 0.3]
-    cam = oracle.setup_camera(W, H, intrinsics(W, H), w2c)
+    cam = oracle.setup_camera(W, H, intrinsics(W, H), w2c)._replace(scale_modifier=mod)
     view = np.ascontiguousarray(cam.viewmatrix, np.float32); proj = np.ascontiguousarray(cam.projmatrix, np.float32)
     checked = 0
     clamp_cases = 0
     errs = []
     for trial in range(300):
         sc = random_scene(1, 100 + trial, zmin=0.4, zmax=5.0, spread=1.5, scale=0.15)
-        mod = 1.0
         fwd = oracle.rasterize_forward(cam, sc["means3D"], sc["opacities"], colors_precomp=sc["colors"],
                                        scales=sc["scales"], rotations=sc["rotations"])
         if fwd["radii"][0] == 0:
@@ -131,4 +147,5 @@ def test_leaf_jacobians_match_oracle_chain(oracle, harness):
         if abs(pv[0] / pv[2]) > 1.3 * cam.tanfovx or abs(pv[1] / pv[2]) > 1.3 * cam.tanfovy:
             clamp_cases += 1
     assert checked > 100
+    assert clamp_cases > 0          # the clamped branch of backward.cu:175,262 (x_grad_mul / y_grad_mul = 0) was among them
     assert np.median(errs) < 2e-6

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import cameras as C
 from scenes import random_scene, intrinsics, rel_err
 
 
@@ -95,7 +96,13 @@ def test_stable_tie_order(oracle):
 # ------------------------------------------------------------------------------------------------------
 def dense_render(means, scales, rot, op, col, m2d, cam, visible, dtype=torch.float64):
     """Independent differentiable splat renderer: every pixel against every Gaussian, sorted by depth,
-    same thresholds as forward.cu:331-380 applied as (non-differentiable) masks."""
+    same thresholds as forward.cu:331-380 applied as (non-differentiable) masks.  Returns C + T bg and T.
+    Two conventions of the reference's backward that autograd of the plain formulas would not reproduce (neither shows under the
+    unit camera with modifier 1, where no visible splat is clamped):
+      * backward.cu:175,262 (computeCov2DCUDA) and 309,396 (its relocated copy): where t.x / t.z is clamped (x_grad_mul = 0) no
+        gradient passes through t.x at all, not even through the t.z in lim * t.z -- so the clamped t.x is a constant here;
+      * backward.cu:429-459 (computeCov3D): dL_dscale is taken with respect to the modified scale s * mod, i.e. it lacks the
+        factor mod -- the caller divides autograd's scale gradient by cam.scale_modifier."""
     W, H = cam.image_width, cam.image_height
     view = torch.tensor(cam.viewmatrix, dtype=dtype).reshape(4, 4).T   # back to row-major math matrix
     proj = torch.tensor(cam.projmatrix, dtype=dtype).reshape(4, 4).T
@@ -111,12 +118,14 @@ def dense_render(means, scales, rot, op, col, m2d, cam, visible, dtype=torch.flo
     R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
                      2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
                      2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(P, 3, 3)
-    S = torch.diag_embed(scales)
+    S = torch.diag_embed(scales * cam.scale_modifier)
     Sigma = R @ S @ S @ R.transpose(1, 2)
     fx, fy = W / (2 * cam.tanfovx), H / (2 * cam.tanfovy)
     tz = pv[:, 2]
-    tx = torch.clamp(pv[:, 0] / tz, -1.3 * cam.tanfovx, 1.3 * cam.tanfovx) * tz
-    ty = torch.clamp(pv[:, 1] / tz, -1.3 * cam.tanfovy, 1.3 * cam.tanfovy) * tz
+    rx, ry = pv[:, 0] / tz, pv[:, 1] / tz
+    limx, limy = 1.3 * cam.tanfovx, 1.3 * cam.tanfovy
+    tx = torch.where((rx < -limx) | (rx > limx), (torch.clamp(rx, -limx, limx) * tz).detach(), pv[:, 0])
+    ty = torch.where((ry < -limy) | (ry > limy), (torch.clamp(ry, -limy, limy) * tz).detach(), pv[:, 1])
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -fx * tx / tz ** 2, zero, fy / tz, -fy * ty / tz ** 2], 1).reshape(P, 2, 3)
     A = J @ view[:3, :3]
@@ -147,42 +156,72 @@ def dense_render(means, scales, rot, op, col, m2d, cam, visible, dtype=torch.flo
         w = torch.where(ok, alpha_c * T, torch.zeros_like(T))
         C = C + col[i][:, None, None] * w[None]
         T = torch.where(ok, test_T, T)
-    return C, T
+    bg = torch.tensor(np.asarray(cam.bg, np.float64), dtype=dtype)
+    return C + T[None] * bg[:, None, None], T
 
 
-@pytest.mark.parametrize("seed", [0, 1])
-def test_power1_matches_autograd_of_dense_renderer(oracle, seed):
-    W = H = 16   # a single tile: the tile's list is exactly the set of visible Gaussians
+def _one_tile_case(which, oracle):
+    """(camera, scene, P): the unit camera (which = a seed) or a 16 x 16 variant of a case of tests/cameras.py -- a single tile, so
+    the tile's list is exactly the set of visible Gaussians"""
+    W = H = 16
     P = 40
-    sc = random_scene(P, seed, zmin=1.0, zmax=4.0, spread=0.6, scale=0.08, opacity_mean=0.0)
+    if isinstance(which, int):
+        sc = random_scene(P, which, zmin=1.0, zmax=4.0, spread=0.6, scale=0.08, opacity_mean=0.0)
+        cam = oracle.setup_camera(W, H, intrinsics(W, H), np.eye(4))
+    else:
+        camera, mod, rotated, seed = which
+        c = C.scaled(C.case(camera, mod, C.pose(0.25, (0.1, -0.05, 0.2)) if rotated else np.eye(4)), W, H)
+        sc = C.frustum_scene(c, P, seed, zmin=1.0, zmax=4.0, scale=0.08, opacity_mean=0.0, factor=1.5)
+        cam = C.oracle_camera(oracle, c)
     sc["opacities"] = np.clip(sc["opacities"], 0.05, 0.9)  # keep alpha below the 0.99 clamp (appendix B.3)
-    cam = oracle.setup_camera(W, H, intrinsics(W, H), np.eye(4))
+    return cam, sc, P
+
+
+# (camera, scale modifier, rotated view, seed): seeds at which some visible splat is clamped
+ONE_TILE = [("narrow_wide", 1.0, False, 0), ("narrow_wide", 1.7, True, 1), ("offcentre", 1.7, False, 2), ("offcentre", 1.0, True, 3),
+            ("offcentre", 0.4, True, 4)]
+
+
+@pytest.mark.parametrize("which", [0, 1] + ONE_TILE, ids=lambda w: str(w) if isinstance(w, int) else f"{w[0]}-m{w[1]:g}-{'rot' if w[2] else 'id'}")
+def test_power1_matches_autograd_of_dense_renderer(oracle, which):
+    cam, sc, P = _one_tile_case(which, oracle)
+    W, H = cam.image_width, cam.image_height
     fwd = oracle.rasterize_forward(cam, sc["means3D"], sc["opacities"], colors_precomp=sc["colors"],
                                    scales=sc["scales"], rotations=sc["rotations"])
-    rng = np.random.default_rng(seed + 10)
+    if not isinstance(which, int):
+        cx, cy = C.clamp_counts(oracle, cam, sc["means3D"], fwd)
+        assert cx + cy > 0 and (fwd["radii"] > 0).sum() >= 15, (cx, cy, int((fwd["radii"] > 0).sum()))
+        assert np.abs(cam.bg).max() > 0 and (fwd["final_T"] > 0.01).any()
+    rng = np.random.default_rng((which if isinstance(which, int) else which[3]) + 10)
     dL = rng.normal(size=(3, H, W)).astype(np.float32)
     g = oracle.rasterize_backward(cam, fwd, dL, 1)
 
     t = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in sc.items()}
     m2d = torch.zeros(P, 3, dtype=torch.float64, requires_grad=True)
-    C, T = dense_render(t["means3D"], t["scales"], t["rotations"], t["opacities"], t["colors"], m2d, cam, fwd["radii"] > 0)
-    assert rel_err(fwd["color"], C.detach().numpy()) < 2e-5
+    Cimg, T = dense_render(t["means3D"], t["scales"], t["rotations"], t["opacities"], t["colors"], m2d, cam, fwd["radii"] > 0)
+    assert rel_err(fwd["color"], Cimg.detach().numpy()) < 2e-5
     assert rel_err(fwd["final_T"], T.detach().numpy()) < 2e-5
-    (C * torch.tensor(dL, dtype=torch.float64)).sum().backward()
+    (Cimg * torch.tensor(dL, dtype=torch.float64)).sum().backward()
     for name, ref in (("dL_dmeans3D", t["means3D"].grad), ("dL_dcolors", t["colors"].grad),
-                      ("dL_dopacity", t["opacities"].grad.reshape(-1, 1)), ("dL_dscales", t["scales"].grad),
+                      ("dL_dopacity", t["opacities"].grad.reshape(-1, 1)), ("dL_dscales", t["scales"].grad / cam.scale_modifier),
                       ("dL_drotations", t["rotations"].grad), ("dL_dmeans2D", m2d.grad)):
         assert rel_err(g[name], ref.numpy()) < 2e-4, name
 
 
-def test_power2_identity(oracle):
+@pytest.mark.parametrize("which", [3] + ONE_TILE[1:3], ids=lambda w: "unit" if isinstance(w, int) else f"{w[0]}-m{w[1]:g}-{'rot' if w[2] else 'id'}")
+def test_power2_identity(oracle, which):
     """Sum over pixels of squared one-hot-pixel gradients == the power-2 pass (backward.cu:1095-1137)."""
     W = H = 16
-    P = 60
-    sc = random_scene(P, 3, zmin=0.8, zmax=4.0, spread=0.7, scale=0.08)
-    cam = oracle.setup_camera(W, H, intrinsics(W, H), np.eye(4))
+    if isinstance(which, int):
+        P = 60
+        sc = random_scene(P, which, zmin=0.8, zmax=4.0, spread=0.7, scale=0.08)
+        cam = oracle.setup_camera(W, H, intrinsics(W, H), np.eye(4))
+    else:
+        cam, sc, P = _one_tile_case(which, oracle)
     fwd = oracle.rasterize_forward(cam, sc["means3D"], sc["opacities"], colors_precomp=sc["colors"],
                                    scales=sc["scales"], rotations=sc["rotations"])
+    if not isinstance(which, int):
+        assert sum(C.clamp_counts(oracle, cam, sc["means3D"], fwd)) > 0
     gs = 1e-3
     g2 = oracle.rasterize_backward(cam, fwd, np.full((3, H, W), gs, np.float32), 2)
     names = ("dL_dmeans3D", "dL_dopacity", "dL_dscales", "dL_drotations", "dL_dcolors", "dL_dmeans2D", "dL_dcov3D")
