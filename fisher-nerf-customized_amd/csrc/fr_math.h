@@ -838,3 +838,25 @@ FR_HD void fr_sh_backward_jacobian(int deg, fr_f3 pos, fr_f3 campos, const float
 		Dm[2][c] = (-d0.x * d0.z * ddx - d0.y * d0.z * ddy + (sum2 - d0.z * d0.z) * ddz) * invsum32;
 	}
 }
+
+// ---- POp-GS diagonal criteria (fr_popgs.hip) --------------------------------------------------------------
+// One entry's term.  ss = sum_k row_k^2 (fp32, one rounding per probe), p = prior_in.  J is returned for the write-back.
+// T-opt: 1 / max(prior + J, c), the caller negates the sum.
+// D-opt: log max(post, c) - log max(prior, c) as log1p(d / base) with base = max(prior, c) and d = J when the prior is not clamped
+// (then post >= prior is not either), max(post, c) - c when it is.  J == 0 (or, under a clamped prior, post <= c) gives exactly 0, and
+// the term never is the difference of two rounded logarithms.  A quotient beyond fp32 (a prior of 1e-12 under an estimate of 1e27) takes the two logarithms,
+// which are then far apart.
+template <bool DOPT>
+FR_HD float popgs_term(float ss, float inv_or_K, bool k_is_pow2, float p, float lam, float c, float& J)
+{
+	J = k_is_pow2 ? ss * inv_or_K : ss / inv_or_K;
+	const float prior = p + lam;
+	const float post = prior + J;
+	if (!DOPT) return 1.0f / fmaxf(post, c);
+	const bool free_prior = prior >= c;
+	const float base = free_prior ? prior : c;
+	const float d = free_prior ? J : fmaxf(post, c) - c;
+	const float q = d / base;
+	if (q < 3.0e38f) return log1pf(q);
+	return logf(d) - logf(base);
+}

@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "fr_internal.h"
+#include "fr_math.h"
 
 #define POPGS_THREADS 256
 #define POPGS_MAX_BLOCKS_PER_VIEW 96     // 21 paths x 96 = 2016 workgroups: one resident set of 256 CUs x 8
@@ -41,27 +42,7 @@ struct PopgsArgs {
 	float lam, clamp;
 };
 
-// One entry's term.  ss = sum_k row_k^2 (fp32, one rounding per probe), p = prior_in.  J is returned for the write-back.
-// T-opt: 1 / max(prior + J, c), the caller negates the sum.
-// D-opt: log max(post, c) - log max(prior, c) as log1p(d / base) with base = max(prior, c) and d = J when the prior is not clamped
-// (then post >= prior is not either), max(post, c) - c when it is.  J == 0 (or post <= c) gives exactly 0, and the term never is the
-// difference of two rounded logarithms.  A quotient beyond fp32 (a prior of 1e-12 under an estimate of 1e27) takes the two logarithms,
-// which are then far apart.
-template <bool DOPT>
-__device__ __forceinline__ float popgs_term(float ss, float inv_or_K, bool k_is_pow2, float p, float lam, float c, float& J)
-{
-	J = k_is_pow2 ? ss * inv_or_K : ss / inv_or_K;
-	const float prior = p + lam;
-	const float post = prior + J;
-	if (!DOPT) return 1.0f / fmaxf(post, c);
-	const bool free_prior = prior >= c;
-	const float base = free_prior ? prior : c;
-	const float d = free_prior ? J : fmaxf(post, c) - c;
-	const float q = d / base;
-	if (q < 3.0e38f) return log1pf(q);
-	return logf(d) - logf(base);
-}
-
+// (one entry's term: popgs_term of fr_math.h, which the CPU harness compiles too)
 template <bool VEC>
 __device__ __forceinline__ float4 popgs_load4(const float* base, long long e, long long E)
 {

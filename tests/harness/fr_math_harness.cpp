@@ -169,4 +169,15 @@ void h_leaves_from_rows_g(const float* mean, const float* cov3D, const float* sc
 	for (int r = 0; r < 7; r++) out[3 + r] = Cg[r][0] * gm[2] + Cg[r][1] * gm[3] + Cg[r][2] * gm[4];
 }
 
+// One entry's term of fr_popgs_diag_criterion at n (ss, p) pairs, with the divisor formed as k_popgs_criterion forms it
+// (1 / K and a multiply for a power of two, K and a divide otherwise).  ss = sum_k row_k^2, p = prior_in, c = the clamp.
+void h_popgs_term(int n, int dopt, const float* ss, int K, const float* p, float lam, float c, float* term_out, float* J_out)
+{
+	const bool pow2 = (K & (K - 1)) == 0;
+	const float kdiv = pow2 ? 1.0f / (float)K : (float)K;
+	for (int i = 0; i < n; i++)
+		term_out[i] = dopt ? popgs_term<true>(ss[i], kdiv, pow2, p[i], lam, c, J_out[i])
+		                   : popgs_term<false>(ss[i], kdiv, pow2, p[i], lam, c, J_out[i]);
+}
+
 }

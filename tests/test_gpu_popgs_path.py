@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from popgs_cases import restate as _restate
+
 pytestmark = pytest.mark.gpu
 
 CLAMP = 1e-12
@@ -21,20 +23,6 @@ def _slam(gpu, P, W, H, seed):
 def _draws(n, H, W, seed):
     g = torch.Generator().manual_seed(seed)
     return [torch.randn((3, H, W), generator=g) for _ in range(n)]
-
-
-def _restate(rows, prior, lam, crit):
-    """float64 NumPy on the float32 inputs: J, scores [V], prior + J.  rows [V,K,E], prior [E] or [V,E]."""
-    r = rows.astype(np.float64)
-    J = (r * r).sum(axis=1) / r.shape[1]
-    pin = np.broadcast_to(prior.astype(np.float64), J.shape)
-    pr = pin + np.float64(np.float32(lam))                 # lam as the ABI carries it
-    post = pr + J
-    if crit == "topt":
-        s = -(1.0 / np.maximum(post, CLAMP)).sum(axis=1)
-    else:
-        s = (np.log(np.maximum(post, CLAMP)) - np.log(np.maximum(pr, CLAMP))).sum(axis=1)
-    return s, pin + J
 
 
 @pytest.fixture(scope="module", params=[(10000, 256, 1), (3001, 96, 9)], ids=["config1_P10000", "odd_P3001"])
