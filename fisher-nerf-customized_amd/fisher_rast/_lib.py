@@ -83,6 +83,23 @@ class OccCfg(ctypes.Structure):
     ]
 
 
+FR_LOSS_L1_SUM, FR_LOSS_L1_MEAN, FR_LOSS_L1_MASKED_MEAN = 0, 1, 2
+
+
+class ImageLossCfg(ctypes.Structure):
+    """fr_image_loss_cfg (include/fisher_rast.h)"""
+    _fields_ = [
+        ("C", ctypes.c_int32),
+        ("H", ctypes.c_int32),
+        ("W", ctypes.c_int32),
+        ("w_l1", ctypes.c_float),
+        ("w_ssim", ctypes.c_float),
+        ("l1_denom", ctypes.c_int32),
+        ("mask_channels", ctypes.c_int32),
+        ("mask_weights_ssim_map", ctypes.c_int32),
+    ]
+
+
 # every symbol include/fisher_rast.h and include/fisher_occ.h declare
 EXPORTS = (
     "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
@@ -91,6 +108,7 @@ EXPORTS = (
     "fr_render_views_workspace_bytes", "fr_render_views_workspace_layout", "fr_render_views",
     "fr_fisher_point_workspace_bytes", "fr_fisher_point_workspace_layout", "fr_fisher_point_views",
     "fr_popgs_diag_criterion_workspace_bytes", "fr_popgs_diag_criterion",
+    "fr_image_loss_workspace_bytes", "fr_image_loss_forward", "fr_image_loss_backward",
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
@@ -100,7 +118,7 @@ _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_math.h", "fr_loss_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -234,6 +252,14 @@ def load():
         lib.fr_popgs_diag_criterion.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _f32p, _f32p, ctypes.c_int64, _f32p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    if hasattr(lib, "fr_image_loss_forward"):
+        lib.fr_image_loss_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_image_loss_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+        lib.fr_image_loss_forward.restype = ctypes.c_int
+        lib.fr_image_loss_forward.argtypes = [ctypes.POINTER(ImageLossCfg), _f32p, _f32p, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_image_loss_backward.restype = ctypes.c_int
+        lib.fr_image_loss_backward.argtypes = [ctypes.POINTER(ImageLossCfg), _f32p, _f32p, ctypes.c_void_p, _f32p, _f32p, _f32p, ctypes.c_void_p]
     lib.fr_densify_stats.restype = ctypes.c_int
     lib.fr_densify_stats.argtypes = [ctypes.c_int32, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]
     lib.fr_densify_masks.restype = ctypes.c_int

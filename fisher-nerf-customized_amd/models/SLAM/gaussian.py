@@ -241,10 +241,12 @@ class FisherOps:
         return scorer.run(self._as_w2c(w2cs), H_inv=H_inv_per_view, H_inv_per_view=True)["scores"]
 
     @classmethod
-    def install(cls, target_cls, patch_get_loss=False):
+    def install(cls, target_cls, patch_get_loss=False, fused_loss=False):
         """Graft the accelerated methods onto the reference's class.  `patch_get_loss=True` also replaces the
         module-level `get_loss` of the module `target_cls` lives in by the fused-render form (`make_get_loss`); off by default --
-        a caller that only wants the Fisher scorer keeps the reference's training step untouched."""
+        a caller that only wants the Fisher scorer keeps the reference's training step untouched.  With `fused_loss=True` as well,
+        that get_loss takes its loss terms from this package's `calc_loss` (`calc_loss_mask` where the module has one: the object
+        class) -- the fused L1 + SSIM kernels, no host synchronisation -- instead of the reference module's own; off by default."""
         for name in ("_device", "_as_w2c", "_stack_poses", "_scorer", "_scorer_key", "_keyframe_key", "_same_keyframes", "_PARAM_KEYS", "compute_Hessian", "compute_H_train",
                      "pose_eval", "path_scores"):
             setattr(target_cls, name, getattr(cls, name))
@@ -253,7 +255,11 @@ class FisherOps:
         import sys
         mod = sys.modules.get(target_cls.__module__)
         if patch_get_loss and mod is not None and all(hasattr(mod, n) for n in ("get_loss", "transform_to_frame", "calc_loss")):
-            mod.get_loss = make_get_loss(mod.transform_to_frame, mod.calc_loss)
+            loss_fn = mod.calc_loss
+            if fused_loss:
+                from models.SLAM.utils import slam_helpers as _sh
+                loss_fn = _sh.calc_loss_mask if hasattr(mod, "calc_loss_mask") else _sh.calc_loss
+            mod.get_loss = make_get_loss(mod.transform_to_frame, loss_fn)
         if not hasattr(target_cls, "FISHER_COLUMNS"):
             target_cls.FISHER_COLUMNS = cls.FISHER_COLUMNS
         target_cls.H_TRAIN_REG = cls.H_TRAIN_REG

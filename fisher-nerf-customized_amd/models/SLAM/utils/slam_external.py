@@ -2,7 +2,10 @@
 get_loss, models/SLAM/gaussian.py:289-291) on MI355X: each torch-op chain of the reference is one kernel pass over the
 Gaussians (fr_densify_stats / fr_densify_masks / fr_prune_mask, include/fisher_rast.h).
 
-Only the statistics and the masks are accelerated.  What the reference then DOES with a mask -- cloning / splitting the
+`calc_ssim` / `calc_ssim_masked` (slam_external.py:89-120, 144-193) are the fused image-loss kernels (fr_image_loss_forward /
+fr_image_loss_backward through fisher_rast/image_loss.py): one forward launch pair, one backward launch, no host synchronisation.
+
+Of densification, only the statistics and the masks are accelerated.  What the reference then DOES with a mask -- cloning / splitting the
 parameter tensors, rebuilding the Adam state (cat_params_to_optimizer, remove_points) -- is optimiser bookkeeping that stays
 reference Python; `densify_masks` / `prune_mask` hand it the same boolean tensors it computes itself.
 """
@@ -11,6 +14,7 @@ import ctypes
 import torch
 
 from fisher_rast import _lib
+from fisher_rast import image_loss as _il
 
 
 def _stream(dev):
@@ -90,3 +94,36 @@ def prune_mask(params, opacity_thresh, big_thresh=None):
         _lib.check(_lib.load().fr_prune_mask(P, lo.data_ptr(), ls.data_ptr(), cols, float(opacity_thresh),
                                              -1.0 if big_thresh is None else float(big_thresh), out.data_ptr(), _stream(dev)), "fr_prune_mask")
     return out
+
+
+def _check_window(window_size):
+    if window_size != 11:
+        raise NotImplementedError(f"calc_ssim: only window_size == 11 is built (the reference passes no other), got {window_size}")
+
+
+def calc_ssim(img1, img2, window_size=11, size_average=True):
+    """slam_external.py:89-120: the mean SSIM of img1 against img2 ([C,H,W] or [B,C,H,W]; a batch folds into the channels), or
+    with size_average=False the per-batch means [B], from the per-channel sums.  Differentiable w.r.t. img1 (with
+    size_average=False for a single image only; img2 must not require a gradient)."""
+    _check_window(window_size)
+    if size_average:
+        return _il.image_loss(img1, img2, None, 0.0, -1.0, _il.FR_LOSS_L1_SUM, which=_il.OUT_SSIM)[0]
+    B = int(img1.shape[0]) if img1.dim() == 4 else 1
+    if B == 1:
+        return _il.image_loss(img1, img2, None, 0.0, -1.0, _il.FR_LOSS_L1_SUM, which=_il.OUT_SSIM)[0].reshape(1)
+    if img1.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("calc_ssim(size_average=False): the gradient of a batch's per-image means is not built")
+    chan = _il.image_loss(img1.detach(), img2, None, 0.0, -1.0, _il.FR_LOSS_L1_SUM, which=_il.OUT_SSIM, want_channels=True)[1]
+    return chan.reshape(B, -1).mean(1)
+
+
+def calc_ssim_masked(img1, img2, mask, window_size=11):
+    """slam_external.py:144-193: the SSIM map's mean over the channels, weighted by `mask` ([1,H,W] or [H,W], 0 / 1) with
+    clamp_min(1) on its count.  img1, img2: [C,H,W] (or [1,C,H,W]).  Differentiable w.r.t. img1."""
+    _check_window(window_size)
+    if img1.dim() == 4:
+        if img1.shape[0] != 1:
+            raise NotImplementedError("calc_ssim_masked: one image at a time (the reference's callers pass [3,H,W])")
+        img1, img2 = img1[0], img2[0]
+    H, W = int(img1.shape[-2]), int(img1.shape[-1])
+    return _il.image_loss(img1, img2, mask.reshape(1, H, W), 0.0, -1.0, _il.FR_LOSS_L1_SUM, weights_map=True, which=_il.OUT_SSIM)[0]

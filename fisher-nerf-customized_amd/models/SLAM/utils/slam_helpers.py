@@ -1,6 +1,9 @@
-"""Render-variable builders on the hot path (models/SLAM/utils/slam_helpers.py:178-188, 235-252, 268-279)."""
+"""Render-variable builders on the hot path (models/SLAM/utils/slam_helpers.py:178-188, 235-252, 268-279) and the loss terms of the
+training step (slam_helpers.py:5-6, 23-77) on the fused image-loss kernels (fisher_rast/image_loss.py)."""
 import torch
 import torch.nn.functional as F
+
+from fisher_rast import image_loss as _il
 
 
 def _scales3(params):
@@ -51,3 +54,36 @@ def render_rgb_depth_sil(params, cam, w2c, transformed_pts, renderer_cls=None):
         rendervar['means3D'], rendervar['means2D'], rendervar['opacities'], rendervar['colors_precomp'], feats,
         scales=rendervar['scales'], rotations=rendervar['rotations'])
     return im, radius, depth_sil, rendervar
+
+
+def l1_loss_v1(x, y):
+    """slam_helpers.py:5-6: mean |x - y|, differentiable w.r.t. x ([C,H,W] or [B,C,H,W])."""
+    return _il.image_loss(x, y, None, 1.0, 0.0, _il.FR_LOSS_L1_MEAN)[0]
+
+
+def _loss_terms(curr_data, im, depth, mask, color_mask, use_l1, use_sil_for_loss, ignore_outlier_depth_loss, tracking, mask_colour):
+    losses = {}
+    if use_l1:
+        # depth: the masked sum in tracking, the masked mean in mapping
+        losses['depth'] = _il.image_loss(depth, curr_data['depth'], mask.detach(), 1.0, 0.0,
+                                         _il.FR_LOSS_L1_SUM if tracking else _il.FR_LOSS_L1_MASKED_MEAN)[0]
+    if tracking and (use_sil_for_loss or ignore_outlier_depth_loss):
+        losses['im'] = _il.image_loss(im, curr_data['im'], color_mask, 1.0, 0.0, _il.FR_LOSS_L1_SUM)[0]
+    elif tracking:
+        losses['im'] = _il.image_loss(im, curr_data['im'], None, 1.0, 0.0, _il.FR_LOSS_L1_SUM)[0]
+    elif mask_colour:
+        # the masked mean of |.| and the SSIM of the two images times the mask
+        losses['im'] = _il.image_loss(im, curr_data['im'], color_mask, 0.8, 0.2, _il.FR_LOSS_L1_MASKED_MEAN)[0]
+    else:
+        losses['im'] = _il.image_loss(im, curr_data['im'], None, 0.8, 0.2, _il.FR_LOSS_L1_MEAN)[0]
+    return losses
+
+
+def calc_loss(curr_data, im, depth, mask, color_mask, use_l1, use_sil_for_loss, ignore_outlier_depth_loss, tracking):
+    """slam_helpers.py:23-44: {'depth': .., 'im': ..}, each entry one forward launch pair and one backward launch."""
+    return _loss_terms(curr_data, im, depth, mask, color_mask, use_l1, use_sil_for_loss, ignore_outlier_depth_loss, tracking, False)
+
+
+def calc_loss_mask(curr_data, im, depth, mask, color_mask, use_l1, use_sil_for_loss, ignore_outlier_depth_loss, tracking):
+    """slam_helpers.py:46-77: calc_loss with the mapping colour term taken over `color_mask` only."""
+    return _loss_terms(curr_data, im, depth, mask, color_mask, use_l1, use_sil_for_loss, ignore_outlier_depth_loss, tracking, True)

@@ -37,6 +37,8 @@
  *                           (tester_gaussians_navigation.py:2147-2178, models/SLAM/gaussian_object.py:1705-1719)
  *   fr_densify_stats / fr_densify_masks / fr_prune_mask <- the statistics of get_loss / densify / prune_gaussians
  *                           models/SLAM/gaussian.py:289-291, models/SLAM/utils/slam_external.py:196-200, 345-465
+ *   fr_image_loss_forward / fr_image_loss_backward <- calc_loss / calc_loss_mask / calc_ssim / calc_ssim_masked,
+ *                           models/SLAM/utils/slam_helpers.py:23-77, models/SLAM/utils/slam_external.py:77-193
  *   fr_knn_dist2         <- simple_knn._C.distCUDA2 (thirdparty/simple-knn, un-vendored submodule)
  *
  * The pybind module `_C` of the reference (RAST/ext.cpp:14-18) is re-created in Python on top of
@@ -401,6 +403,41 @@ int fr_densify_masks(int32_t P, const float* means2D_gradient_accum, const float
  * OR (big_thresh >= 0 AND max_k exp(log_scales) > big_thresh).  uint8 [P]. */
 int fr_prune_mask(int32_t P, const float* logit_opacities, const float* log_scales, int32_t scale_cols,
                   float opacity_thresh, float big_thresh, uint8_t* to_remove, fr_stream_t stream);
+
+/* ---- fused image loss of the training step: L1 + SSIM, forward and backward ------------------------------------------
+ * In place of calc_loss / calc_loss_mask / calc_ssim / calc_ssim_masked (models/SLAM/utils/slam_helpers.py:23-77,
+ * slam_external.py:77-193): per term two launches forward and one backward, no host synchronisation, no atomics (the same call
+ * gives the same bits).  The 11 x 11 window (gaussian(11, 1.5); no other size) is applied as its two 11-tap passes, zero padded.
+ *   loss = w_l1 * (sum |img - gt| / denominator) + w_ssim * (1 - sum ssim_map / normaliser)       (a term whose weight is 0 is left out)
+ *   denominator: 1 (FR_LOSS_L1_SUM), C H W (FR_LOSS_L1_MEAN) or the number of mask bytes set (FR_LOSS_L1_MASKED_MEAN; an empty mask
+ *                gives NaN, as torch's mean of nothing does);   normaliser: C H W
+ * mask: device bytes (0 / 1), [C,H,W] (mask_channels = C) or [1,H,W] shared by the channels (mask_channels = 1), or null
+ * (mask_channels = 0).  It selects the pixels of the L1 sum, and both images are multiplied by it before the SSIM (calc_loss_mask).
+ * With mask_weights_ssim_map = 1 it does neither: it weights the SSIM map instead, and the normaliser is max(bytes set, C) -- for a
+ * [1,H,W] mask the mean over the channels, weighted by the mask with clamp_min(1) on its count (calc_ssim_masked).
+ * w_ssim == 0 is the L1-only form (depth term, tracking terms): no SSIM pass, and the SSIM outputs must be null. */
+enum { FR_LOSS_L1_SUM = 0, FR_LOSS_L1_MEAN = 1, FR_LOSS_L1_MASKED_MEAN = 2 };
+typedef struct {
+	int32_t C, H, W;
+	float w_l1, w_ssim;
+	int32_t l1_denom;                 /* FR_LOSS_L1_* */
+	int32_t mask_channels;            /* 0 (no mask), 1 or C */
+	int32_t mask_weights_ssim_map;    /* 0 / 1, see above */
+} fr_image_loss_cfg;
+
+/* Host-only query (0 for a bad argument): the fp64 per-workgroup partials and their per-channel sums. */
+size_t fr_image_loss_workspace_bytes(int32_t C, int32_t H, int32_t W);
+/* out4 = {loss, L1 term (sum / denominator), SSIM mean, mask bytes set (C H W without a mask)}; out_channel_ssim [C] (or null):
+ * the channels' SSIM means; out_ssim_map [C,H,W] (or null): the per-pixel map.  saved: (w_ssim != 0 ? 3 C H W : 0) + 4 floats that
+ * fr_image_loss_backward reads -- the three partial maps of the SSIM term w.r.t. the window moments of img (mean, E[x x], E[x y], taken about 0.5) and the two factors w_l1 / denominator,
+ * w_ssim / normaliser.  workspace: fr_image_loss_workspace_bytes, 8-byte aligned. */
+int fr_image_loss_forward(const fr_image_loss_cfg* cfg, const float* img, const float* gt, const uint8_t* mask,
+                          float* out4, float* out_channel_ssim, float* out_ssim_map, float* saved,
+                          void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* dL_dimg [C,H,W] = upstream[0] * d loss / d img, every element written once; exactly 0 where the mask is 0 (also under an empty
+ * mask).  upstream: DEVICE float (autograd's 0-dim gradient), read by the kernel.  cfg, img, gt, mask, saved as in the forward. */
+int fr_image_loss_backward(const fr_image_loss_cfg* cfg, const float* img, const float* gt, const uint8_t* mask,
+                           const float* saved, const float* upstream, float* dL_dimg, fr_stream_t stream);
 
 /* ---- simple-knn ---------------------------------------------------------------------------------- */
 
