@@ -100,6 +100,28 @@ class ImageLossCfg(ctypes.Structure):
     ]
 
 
+FR_INGEST_NONPRESENCE, FR_INGEST_MASK = 0, 1
+FR_INGEST_STATUS_WORDS = 5
+FR_INGEST_WS_INDEX_OFFSET = 8192
+
+
+class FrameIngestCfg(ctypes.Structure):
+    """fr_frame_ingest_cfg (include/fisher_rast.h)"""
+    _fields_ = [
+        ("H", ctypes.c_int32),
+        ("W", ctypes.c_int32),
+        ("downsample", ctypes.c_int32),
+        ("mode", ctypes.c_int32),
+        ("sil_thres", ctypes.c_float),
+        ("depth_error_ratio", ctypes.c_float),
+        ("transform_pts", ctypes.c_int32),
+        ("scale_cols", ctypes.c_int32),
+        ("means_stride", ctypes.c_int32),
+        ("colors_stride", ctypes.c_int32),
+        ("intrinsics", _f32p),
+    ]
+
+
 # every symbol include/fisher_rast.h and include/fisher_occ.h declare
 EXPORTS = (
     "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
@@ -109,6 +131,7 @@ EXPORTS = (
     "fr_fisher_point_workspace_bytes", "fr_fisher_point_workspace_layout", "fr_fisher_point_views",
     "fr_popgs_diag_criterion_workspace_bytes", "fr_popgs_diag_criterion",
     "fr_image_loss_workspace_bytes", "fr_image_loss_forward", "fr_image_loss_backward",
+    "fr_frame_ingest_workspace_bytes", "fr_frame_ingest_select", "fr_frame_ingest_emit",
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
@@ -118,7 +141,8 @@ _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_math.h", "fr_loss_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_math.h", "fr_loss_math.h",
+                                                  "fr_ingest_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -260,6 +284,15 @@ def load():
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         lib.fr_image_loss_backward.restype = ctypes.c_int
         lib.fr_image_loss_backward.argtypes = [ctypes.POINTER(ImageLossCfg), _f32p, _f32p, ctypes.c_void_p, _f32p, _f32p, _f32p, ctypes.c_void_p]
+    if hasattr(lib, "fr_frame_ingest_select"):
+        lib.fr_frame_ingest_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_frame_ingest_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+        lib.fr_frame_ingest_select.restype = ctypes.c_int
+        lib.fr_frame_ingest_select.argtypes = [ctypes.POINTER(FrameIngestCfg), _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_frame_ingest_emit.restype = ctypes.c_int
+        lib.fr_frame_ingest_emit.argtypes = [ctypes.POINTER(FrameIngestCfg), _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_int32,
+                                             ctypes.c_int64] + [_f32p] * 6 + [ctypes.c_void_p]
     lib.fr_densify_stats.restype = ctypes.c_int
     lib.fr_densify_stats.argtypes = [ctypes.c_int32, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]
     lib.fr_densify_masks.restype = ctypes.c_int

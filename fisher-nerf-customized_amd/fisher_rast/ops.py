@@ -10,6 +10,8 @@ Four groups of entry points:
   * `knn_dist2` -- simple_knn._C.distCUDA2.
   * `popgs_diag_criterion` -- the POp-GS T-opt / D-opt score of a batch of views from their probe rows, and the priors of the
     path evaluation updated in the same pass (tester_gaussians_navigation.py:2147-2178).
+  * `frame_ingest_select` / `frame_ingest_emit` -- which cells of an RGB-D frame become new Gaussians, and their parameter rows
+    (models/SLAM/gaussian.py:320-414, 75-143, 299-318).
 """
 import ctypes
 from typing import Optional
@@ -17,7 +19,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import FisherRastError, RasterCfg, Gaussians, FisherCfg
+from ._lib import FisherRastError, RasterCfg, Gaussians, FisherCfg, FrameIngestCfg
 
 
 def _need_gpu(t: torch.Tensor, name: str):
@@ -826,3 +828,121 @@ def popgs_diag_criterion(rows: torch.Tensor, prior_in: torch.Tensor, lam: float 
                                                workspace.numel() * workspace.element_size(), _stream(dev)),
                    "fr_popgs_diag_criterion")
     return scores
+
+
+def _small_f32(t, dev, rows, cols, name):
+    """a [rows, cols] matrix (tensor on any device, array or nested list) as contiguous fp32 on `dev`, without a host
+    synchronisation: a device tensor is used where it is; host values are staged in pinned memory and sent with a non-blocking
+    copy (the host allocator keeps a pinned block until the copies issued from it have run, so dropping the staging tensor on
+    return is safe)"""
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t, dtype=torch.float32)
+    if t.dim() != 2 or t.shape[0] < rows or t.shape[1] < cols:
+        raise FisherRastError(f"{name} must be at least [{rows},{cols}], got {tuple(t.shape)}")
+    t = t[:rows, :cols]
+    if t.device != dev:
+        if t.is_cuda:
+            return t.to(dev).float().contiguous()
+        t = t.float().contiguous().pin_memory().to(dev, non_blocking=True)
+    return t.float().contiguous()
+
+
+def _ingest_plain(t, name, dev, dtype, shape):
+    _need_gpu(t, name)
+    if t.device != dev or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise FisherRastError(f"{name} must be a contiguous {dtype} tensor of {tuple(shape)} on {dev}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def frame_ingest_workspace(H, W, downsample, dev):
+    need = int(_lib.load().fr_frame_ingest_workspace_bytes(int(H), int(W), int(downsample)))
+    if need == 0:
+        raise FisherRastError(f"frame ingest: downsample {downsample} must be positive and divide H = {H} and W = {W}")
+    return torch.empty(((need + 7) // 8,), dtype=torch.int64, device=dev)
+
+
+def _mask_bytes_hw(mask, H, W, name):
+    """a [H,W] mask (bool / uint8, or anything compared with 0) as contiguous bytes; bool is reinterpreted, not copied"""
+    _need_gpu(mask, name)
+    if mask.numel() != H * W:
+        raise FisherRastError(f"frame ingest: {name} of {tuple(mask.shape)} does not fit a frame of {H} x {W}")
+    m = mask if mask.dtype in (torch.bool, torch.uint8) else (mask != 0)
+    m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def frame_ingest_select(depth_sil=None, gt_depth=None, mask=None, *, and_mask=None, downsample=1, sil_thres=0.5, depth_error_ratio=50.0,
+                        workspace=None, status=None):
+    """fr_frame_ingest_select.  With `mask` (bool / uint8, H W elements, given together with its [*,H,W] shaped `gt_depth` or
+    `depth_sil` for the size, or itself [H,W]) the caller's mask is pooled and compacted; without, the non-presence mask is built
+    from depth_sil [3,H,W] (depth, silhouette, ..) and gt_depth [1,H,W], ANDed with `and_mask` (H W elements; the object
+    mask of the object-aware SLAM class) where one is given.  Returns (status, workspace): status int32
+    [FR_INGEST_STATUS_WORDS] on the device = {count, median is NaN, 0, 0, median bits} -- reading it is the caller's one host
+    synchronisation -- and the workspace that holds the index list for `frame_ingest_emit`.  No host synchronisation in here."""
+    ref = gt_depth if gt_depth is not None else (depth_sil if depth_sil is not None else mask)
+    if ref is None:
+        raise FisherRastError("frame ingest: nothing to select from")
+    _need_gpu(ref, "frame ingest input")
+    dev = ref.device
+    H, W = int(ref.shape[-2]), int(ref.shape[-1])
+    cfg = FrameIngestCfg(H, W, int(downsample), _lib.FR_INGEST_NONPRESENCE if mask is None else _lib.FR_INGEST_MASK,
+                         float(sil_thres), float(depth_error_ratio), 1, 3, 3, 3, None)
+    if mask is None:
+        _ingest_plain(depth_sil, "depth_sil", dev, torch.float32, (3, H, W))
+        _ingest_plain(gt_depth, "gt_depth", dev, torch.float32, (1, H, W))
+        m = None if and_mask is None else _mask_bytes_hw(and_mask, H, W, "and_mask")
+    else:
+        if and_mask is not None:
+            raise FisherRastError("frame ingest: and_mask goes with the non-presence mask, not with a caller's mask")
+        m = _mask_bytes_hw(mask, H, W, "mask")
+    if workspace is None:
+        workspace = frame_ingest_workspace(H, W, downsample, dev)
+    if status is None:
+        status = torch.empty((_lib.FR_INGEST_STATUS_WORDS,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().fr_frame_ingest_select(ctypes.byref(cfg), _ptr(depth_sil if mask is None else None),
+                                                      _ptr(gt_depth if mask is None else None), _ptr(m), _ptr(status), _ptr(workspace),
+                                                      workspace.numel() * workspace.element_size(), _stream(dev)),
+                   "fr_frame_ingest_select")
+    return status, workspace
+
+
+def frame_ingest_emit(color, gt_depth, intrinsics, w2c, workspace, count, *, downsample=1, transform_pts=True, row_offset=0,
+                      means3D=None, rgb_colors=None, unnorm_rotations=None, logit_opacities=None, log_scales=None, mean3_sq_dist=None,
+                      point_cld=None):
+    """fr_frame_ingest_emit: rows [row_offset, row_offset + count) of every destination given (contiguous fp32 on the device of
+    `color`; `point_cld` [N,6] takes the point and the colour of a row side by side, in place of means3D and rgb_colors).
+    workspace None with count == (H/d)(W/d): every cell.  intrinsics [3,3] and w2c [4,4] may live anywhere; on the device they are
+    read where they are.  No host synchronisation."""
+    _need_gpu(color, "color")
+    dev = color.device
+    H, W = int(color.shape[-2]), int(color.shape[-1])
+    _ingest_plain(color, "color", dev, torch.float32, (3, H, W))
+    _ingest_plain(gt_depth, "gt_depth", dev, torch.float32, (1, H, W))
+    count, row_offset = int(count), int(row_offset)
+    rows = row_offset + count
+    K = _small_f32(intrinsics, dev, 3, 3, "intrinsics")
+    pose = _small_f32(w2c, dev, 4, 4, "w2c") if transform_pts else None
+    means_ptr, rgb_ptr, stride = _ptr(means3D), _ptr(rgb_colors), 3
+    if point_cld is not None:
+        if means3D is not None or rgb_colors is not None:
+            raise FisherRastError("frame ingest: point_cld takes the place of means3D and rgb_colors")
+        _ingest_plain(point_cld, "point_cld", dev, torch.float32, (point_cld.shape[0], 6))
+        means_ptr, rgb_ptr, stride = ctypes.c_void_p(point_cld.data_ptr()), ctypes.c_void_p(point_cld.data_ptr() + 12), 6
+    scale_cols = 3
+    for t, name, cols in ((means3D, "means3D", 3), (rgb_colors, "rgb_colors", 3), (unnorm_rotations, "unnorm_rotations", 4),
+                          (logit_opacities, "logit_opacities", 1), (log_scales, "log_scales", None), (mean3_sq_dist, "mean3_sq_dist", 0),
+                          (point_cld, "point_cld", 6)):
+        if t is None:
+            continue
+        if name == "log_scales":
+            cols = scale_cols = int(t.shape[1]) if t.dim() == 2 else -1
+        _ingest_plain(t, name, dev, torch.float32, (t.shape[0], cols) if cols else (t.shape[0],))
+        if t.shape[0] < rows:
+            raise FisherRastError(f"frame ingest: {name} has {t.shape[0]} rows, {rows} are written")
+    cfg = FrameIngestCfg(H, W, int(downsample), 0, 0.0, 0.0, int(bool(transform_pts)), scale_cols, stride, stride, K.data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().fr_frame_ingest_emit(ctypes.byref(cfg), _ptr(color), _ptr(gt_depth), _ptr(pose), _ptr(workspace), count, row_offset,
+                                                    means_ptr, rgb_ptr, _ptr(unnorm_rotations), _ptr(logit_opacities), _ptr(log_scales),
+                                                    _ptr(mean3_sq_dist), _stream(dev)),
+                   "fr_frame_ingest_emit")

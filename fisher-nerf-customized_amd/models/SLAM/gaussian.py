@@ -7,6 +7,8 @@ In scope (same names, arguments and return conventions as the reference):
     render_at_poses (new: render_at_pose for a batch of poses in one call, RenderOps)
     pose_eval_points (new: the candidate scan of global_planning, 1285-1316 -- per-Gaussian scores and their running maximum, PointScoreOps)
     pause / resume / color_refinement / stop (1600-1614)
+    get_pointcloud / initialize_params / initialize_new_params / add_new_gaussians (75-182, 299-414: module-level functions; the
+        frame ingest, FrameIngestOps)
 The SLAM loop itself (init, track_rgbd, densify, keyframe selection ...) is NOT rebuilt: it is reference
 Python that stays as it is.  `FisherOps.install(cls)` grafts the accelerated methods onto the reference class
 so that tester_gaussians_navigation.py keeps calling `slam.pose_eval(...)` unchanged; `GaussianSLAM` below is
@@ -24,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from diff_gaussian_rasterization import GaussianRasterizer as Renderer
+from fisher_rast import ops as _ops
 from fisher_rast.ops import FisherScorer
 from models.SLAM.utils.common_utils import checkpoint_time_idx, load_params_ckpt, save_params, save_params_ckpt
 from models.SLAM.utils.recon_helpers import setup_camera
@@ -76,6 +79,187 @@ def make_get_loss(transform_to_frame, calc_loss):
         weighted['loss'] = total
         return total, variables, weighted
     return get_loss
+
+
+# ---- frame ingest: new Gaussians from an RGB-D frame (the reference's gaussian.py:75-182, 299-414) ---------------------------------
+
+def _frame_f32(t, name):
+    """a frame tensor as the kernels read it: contiguous float32 on its GPU"""
+    if not t.is_cuda:
+        raise _ops.FisherRastError(f"{name} must live on the GPU (there is no CPU fallback for this path)")
+    t = t.detach()
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def get_pointcloud(color, depth, intrinsics, w2c, transform_pts=True, downsample=1,
+                   mask=None, compute_mean_sq_dist=False, mean_sq_dist_method="projective"):
+    """The reference's get_pointcloud (gaussian.py:75-143), same arguments and returns: the pixels of an RGB-D frame taken at one in
+    `downsample`, back-projected -- point_cld [N,6] (xyz + rgb) and, with `compute_mean_sq_dist`, mean3_sq_dist [N].  One launch
+    without a mask (no host synchronisation); with one, the mask is max-pooled and compacted on the device and the row count is read
+    once (the reference's `sum() > 0`).  Kept from the reference: depth and colour are those of a block's top-left pixel while the
+    mask is the block's maximum, and a mask that selects nothing returns every point with a warning.  `downsample` must divide the
+    image size (the reference's own shapes disagree otherwise)."""
+    if compute_mean_sq_dist and mean_sq_dist_method != "projective":
+        raise ValueError(f"Unknown mean_sq_dist_method {mean_sq_dist_method}")
+    color, depth = _frame_f32(color, "color"), _frame_f32(depth, "depth")
+    H, W = int(color.shape[1]), int(color.shape[2])
+    depth = depth.reshape(1, H, W)
+    workspace = _ops.frame_ingest_workspace(H, W, downsample, color.device) if mask is not None else None
+    count = (H // downsample) * (W // downsample)
+    if mask is not None:
+        status, _ = _ops.frame_ingest_select(gt_depth=depth, mask=mask.reshape(H, W), downsample=downsample, workspace=workspace)
+        selected = int(status[0])                       # the one host read
+        if selected > 0:
+            count = selected
+        else:
+            print("[WARN] Mask become all zero after downsampling")
+            workspace = None
+    point_cld = torch.empty((count, 6), dtype=torch.float32, device=color.device)
+    mean3_sq_dist = torch.empty((count,), dtype=torch.float32, device=color.device) if compute_mean_sq_dist else None
+    _ops.frame_ingest_emit(color, depth, intrinsics, w2c, workspace, count, downsample=downsample, transform_pts=transform_pts,
+                           point_cld=point_cld, mean3_sq_dist=mean3_sq_dist)
+    return (point_cld, mean3_sq_dist) if compute_mean_sq_dist else point_cld
+
+
+def _as_parameters(tensors):
+    return {k: torch.nn.Parameter(v.detach().float().contiguous().requires_grad_(True)) for k, v in tensors.items()}
+
+
+def _gaussian_rows(pt_cld, mean3_sq_dist, isotropic):
+    """the five per-Gaussian tensors of a point cloud [N,6]: identity rotations, logit opacity 0, log scale log(sqrt(mean3_sq_dist))"""
+    n, dev = int(pt_cld.shape[0]), pt_cld.device
+    rots = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+    rots[:, 0] = 1.0
+    return {
+        'means3D': pt_cld[:, :3],
+        'rgb_colors': pt_cld[:, 3:6],
+        'unnorm_rotations': rots,
+        'logit_opacities': torch.zeros((n, 1), dtype=torch.float32, device=dev),
+        'log_scales': torch.log(torch.sqrt(mean3_sq_dist))[:, None].repeat(1, 1 if isotropic else 3),
+    }
+
+
+def initialize_params(init_pt_cld, num_frames, mean3_sq_dist, w2c=None, isotropic=False):
+    """The reference's initialize_params (gaussian.py:145-182): (params, variables) of a first map -- the Gaussians of a point cloud
+    and one camera trajectory of `num_frames` identity poses."""
+    dev = init_pt_cld.device
+    tensors = _gaussian_rows(init_pt_cld, mean3_sq_dist, isotropic)
+    cam_rots = torch.zeros((1, 4, num_frames), dtype=torch.float32, device=dev)
+    cam_rots[:, 0] = 1.0
+    tensors['cam_unnorm_rots'] = cam_rots
+    tensors['cam_trans'] = torch.zeros((1, 3, num_frames), dtype=torch.float32, device=dev)
+    params = _as_parameters(tensors)
+    n = int(params['means3D'].shape[0])
+    variables = {k: torch.zeros(n, dtype=torch.float32, device=dev) for k in ('max_2D_radius', 'means2D_gradient_accum', 'denom', 'timestep')}
+    return params, variables
+
+
+def initialize_new_params(new_pt_cld, mean3_sq_dist, isotropic=False):
+    """The reference's initialize_new_params (gaussian.py:299-318)."""
+    return _as_parameters(_gaussian_rows(new_pt_cld, mean3_sq_dist, isotropic))
+
+
+def frame_w2c(params, time_idx):
+    """[4,4] world->camera pose of frame `time_idx` from the camera trajectory in `params` (gaussian.py:347-351), on the device"""
+    q = F.normalize(params['cam_unnorm_rots'][..., time_idx].detach())[0]
+    r, x, y, z = q[0], q[1], q[2], q[3]
+    rot = torch.stack((1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                       2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                       2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y))).reshape(3, 3)
+    w2c = torch.eye(4, dtype=torch.float32, device=rot.device)
+    w2c[:3, :3] = rot
+    w2c[:3, 3] = params['cam_trans'][..., time_idx].detach()[0]
+    return w2c
+
+
+def _transform_to_frame(params, time_idx, gaussians_grad, camera_grad):
+    """The Gaussians' centres in the frame of camera `time_idx`, for the module-level add_new_gaussians (which needs no gradient);
+    `FrameIngestOps.install` hands the patched module's own transform_to_frame to `make_add_new_gaussians` instead."""
+    pts = params['means3D'].detach()
+    w2c = frame_w2c(params, time_idx)
+    return pts @ w2c[:3, :3].T + w2c[:3, 3]
+
+
+def _random_gaussians(params, new_means):
+    """gaussian.py:365-397: up to 200 random points in the outer shell of the bounding box of the map and the frame's new points, at
+    the robot's height, with random colours and mean3_sq_dist 0.5.  Plain torch, as in the reference (`.item()` and the boolean
+    indexing synchronise the host); off in every shipped config.  Returns (point_cld [M,6], mean3_sq_dist [M])."""
+    dev = new_means.device
+    num_pts = int(min(params["means3D"].shape[0], 1e2))
+    hi = torch.maximum(params["means3D"].detach().max(dim=0)[0], new_means.max(dim=0)[0])
+    lo = torch.minimum(params["means3D"].detach().min(dim=0)[0], new_means.min(dim=0)[0])
+    extent, center = (hi - lo) / 2, (hi + lo) / 2
+    center[1] = params["cam_trans"][0, 1, 0].item()
+    extent[1] = 1.0
+    seed = torch.rand((num_pts * 2, 3), device=dev) * 2 - 1
+    inside = (seed[:, 0].abs() <= 0.8) & (seed[:, 2].abs() <= 0.8)
+    seed = seed[~inside]
+    seed[:, 1] = torch.rand((len(seed),), device=dev) - 0.5
+    cld = torch.cat([seed * extent + center, torch.rand((len(seed), 3), device=dev)], dim=-1)
+    return cld, torch.ones((len(seed),), device=dev) * .5
+
+
+def make_add_new_gaussians(transform_to_frame, renderer_cls=None, object_mask=False):
+    """Drop-in for the module-level `add_new_gaussians` of the reference (models/SLAM/gaussian.py:320-414): same signature, same
+    return `(params, variables)`.  The depth / silhouette render is the caller's (`transform_to_frame` and the rasteriser class are
+    handed in, as `make_get_loss` takes its pieces); everything behind it -- depth error, its median, the non-presence mask, the
+    max-pool, the selection, the inverse pose, the back-projection and the new parameter rows -- is fr_frame_ingest_select and
+    fr_frame_ingest_emit with ONE host read between them (the row count, which sizes the new tensors).  A frame that the map
+    explains returns `params` and `variables` as they came.  Otherwise every per-Gaussian parameter is allocated once at its new
+    size, the old rows are copied and the kernel writes the new rows in place (no point cloud, no cat of temporaries).
+    `add_rand_gaussians` (the signature's default, off in every shipped config) appends the reference's random shell points behind
+    the frame's rows in plain torch; it is not accelerated.  The reference's print of the scale range (two more host reads) is left out.
+    `object_mask=True` is the function of the object-aware module (models/SLAM/gaussian_object.py:431-525), which differs in one
+    step: the non-presence mask is ANDed with `curr_data['obj_mask_2d']` [H,W] before the depth filter (447-460), so new Gaussians
+    appear inside the object mask only.  The mask goes to the select kernel as bytes.  (An entry that is missing or None means no
+    mask here; the reference fails on it.)"""
+    def add_new_gaussians(config, params, variables, curr_data, sil_thres,
+                          time_idx, mean_sq_dist_method, densify_dict,
+                          add_rand_gaussians=True, downsample_pcd=1):
+        if mean_sq_dist_method != "projective":
+            raise ValueError(f"Unknown mean_sq_dist_method {mean_sq_dist_method}")
+        renderer = renderer_cls or Renderer
+        pts = transform_to_frame(params, time_idx, gaussians_grad=False, camera_grad=False)
+        rendervar = transformed_params2depthplussilhouette(params, curr_data['w2c'], pts)
+        depth_sil, _, _ = renderer(raster_settings=curr_data['cam'])(**rendervar)
+        depth_sil, gt_depth = _frame_f32(depth_sil, "the depth / silhouette render"), _frame_f32(curr_data['depth'], "curr_data['depth']")
+        obj_mask = curr_data.get('obj_mask_2d', None) if object_mask else None
+        status, workspace = _ops.frame_ingest_select(depth_sil, gt_depth, and_mask=obj_mask, downsample=downsample_pcd, sil_thres=sil_thres,
+                                                     depth_error_ratio=densify_dict["depth_error_ratio"])
+        count = int(status[0])                          # the one host read
+        if count == 0:
+            return params, variables
+        isotropic = bool(config["isotropic"])
+        old = {k: params[k].detach() for k in ('means3D', 'rgb_colors', 'unnorm_rotations', 'logit_opacities', 'log_scales')}
+        P, dev = int(old['means3D'].shape[0]), depth_sil.device
+        extra = None
+        if add_rand_gaussians:
+            # the shell needs the frame's new points first: emit them on their own, then lay everything out once
+            frame_means = torch.empty((count, 3), dtype=torch.float32, device=dev)
+            _ops.frame_ingest_emit(_frame_f32(curr_data['im'], "curr_data['im']"), gt_depth, curr_data['intrinsics'], frame_w2c(params, time_idx),
+                                   workspace, count, downsample=downsample_pcd, means3D=frame_means)
+            extra = initialize_new_params(*_random_gaussians(params, frame_means), isotropic=isotropic)
+        n_extra = 0 if extra is None else int(extra['means3D'].shape[0])
+        total = P + count + n_extra
+        new = {k: torch.empty((total,) + tuple(v.shape[1:]), dtype=torch.float32, device=dev) for k, v in old.items()}
+        if new['log_scales'].shape[1] != (1 if isotropic else 3):
+            raise ValueError(f"add_new_gaussians: log_scales has {new['log_scales'].shape[1]} columns, config['isotropic'] is {isotropic}")
+        for k, v in old.items():
+            new[k][:P] = v
+            if extra is not None:
+                new[k][P + count:] = extra[k].detach()
+        _ops.frame_ingest_emit(_frame_f32(curr_data['im'], "curr_data['im']"), gt_depth, curr_data['intrinsics'], frame_w2c(params, time_idx),
+                               workspace, count, downsample=downsample_pcd, row_offset=P, **new)
+        for k, v in new.items():
+            params[k] = torch.nn.Parameter(v.requires_grad_(True))
+        for k in ('means2D_gradient_accum', 'denom', 'max_2D_radius'):
+            variables[k] = torch.zeros(total, dtype=torch.float32, device=dev)
+        variables['timestep'] = torch.cat((variables['timestep'], torch.full((count + n_extra,), float(time_idx), dtype=torch.float32, device=dev)), dim=0)
+        return params, variables
+    return add_new_gaussians
+
+
+add_new_gaussians = make_add_new_gaussians(_transform_to_frame)
 
 
 class FisherOps:
@@ -347,6 +531,42 @@ class PointScoreOps:
         """Graft the method onto the reference's class (after FisherOps.install / ObjectFisherOps.install)."""
         for name in ("pose_eval_points",):
             setattr(target_cls, name, getattr(cls, name))
+        return target_cls
+
+
+class FrameIngestOps:
+    """The frame ingest of the mapping loop (fr_frame_ingest_select / fr_frame_ingest_emit, include/fisher_rast.h) for the reference's
+    modules: `install(target_cls)` replaces the four module-level functions `get_pointcloud`, `initialize_params`,
+    `initialize_new_params` and `add_new_gaussians` of the module `target_cls` lives in (models/SLAM/gaussian.py for GaussianSLAM,
+    models/SLAM/gaussian_object.py for GaussianObjectSLAM -- their `init` and `track_rgbd` look these names up in the module), and
+    nothing on the class itself.  `add_new_gaussians` renders with that module's own `transform_to_frame` and `Renderer`, and keeps
+    the one difference between the two modules' functions: the object module's ANDs `curr_data['obj_mask_2d']` into the mask."""
+
+    INGEST_NAMES = ("get_pointcloud", "initialize_params", "initialize_new_params", "add_new_gaussians")
+
+    @staticmethod
+    def _reads_object_mask(fn):
+        """whether a module's add_new_gaussians looks at curr_data['obj_mask_2d'] (gaussian_object.py's does, gaussian.py's does not)"""
+        if hasattr(fn, "object_mask"):                  # one of ours, installed before
+            return bool(fn.object_mask)
+        code = getattr(fn, "__code__", None)
+        return code is not None and "obj_mask_2d" in code.co_consts
+
+    @classmethod
+    def install(cls, target_cls, object_mask=None):
+        """`object_mask`: whether the installed add_new_gaussians ANDs `curr_data['obj_mask_2d']` into the non-presence mask, as the
+        object-aware module's own function does.  None (default) follows the function being replaced: on when it reads that entry."""
+        import sys
+        mod = sys.modules.get(target_cls.__module__)
+        if mod is None or not all(hasattr(mod, n) for n in cls.INGEST_NAMES + ("transform_to_frame",)):
+            raise ValueError(f"FrameIngestOps.install: the module of {target_cls.__name__} does not define {cls.INGEST_NAMES} and transform_to_frame")
+        if object_mask is None:
+            object_mask = cls._reads_object_mask(mod.add_new_gaussians)
+        mod.get_pointcloud = get_pointcloud
+        mod.initialize_params = initialize_params
+        mod.initialize_new_params = initialize_new_params
+        mod.add_new_gaussians = make_add_new_gaussians(mod.transform_to_frame, getattr(mod, "Renderer", None), object_mask=bool(object_mask))
+        mod.add_new_gaussians.object_mask = bool(object_mask)
         return target_cls
 
 

@@ -39,6 +39,8 @@
  *                           models/SLAM/gaussian.py:289-291, models/SLAM/utils/slam_external.py:196-200, 345-465
  *   fr_image_loss_forward / fr_image_loss_backward <- calc_loss / calc_loss_mask / calc_ssim / calc_ssim_masked,
  *                           models/SLAM/utils/slam_helpers.py:23-77, models/SLAM/utils/slam_external.py:77-193
+ *   fr_frame_ingest_select / fr_frame_ingest_emit <- add_new_gaussians / get_pointcloud / initialize_new_params,
+ *                           models/SLAM/gaussian.py:320-414, 75-143, 299-318
  *   fr_knn_dist2         <- simple_knn._C.distCUDA2 (thirdparty/simple-knn, un-vendored submodule)
  *
  * The pybind module `_C` of the reference (RAST/ext.cpp:14-18) is re-created in Python on top of
@@ -438,6 +440,54 @@ int fr_image_loss_forward(const fr_image_loss_cfg* cfg, const float* img, const 
  * mask).  upstream: DEVICE float (autograd's 0-dim gradient), read by the kernel.  cfg, img, gt, mask, saved as in the forward. */
 int fr_image_loss_backward(const fr_image_loss_cfg* cfg, const float* img, const float* gt, const uint8_t* mask,
                            const float* saved, const float* upstream, float* dL_dimg, fr_stream_t stream);
+
+/* ---- frame ingest: new Gaussians from an RGB-D frame ------------------------------------------------------------------
+ * In place of add_new_gaussians / get_pointcloud / initialize_new_params (models/SLAM/gaussian.py:320-414, 75-143, 299-318): which
+ * cells of the H/d x W/d grid of a frame become Gaussians, as an ascending index list, and their parameter rows.  Two calls, since
+ * the row count has to reach the host once to size the new tensors; no other host read, no atomics on floats (the same call
+ * gives the same bits), nothing allocated inside.
+ *   FR_INGEST_NONPRESENCE: a pixel is selected when the map does not explain it --
+ *       err = |gt - render| * (gt > 0);  np = (sil < sil_thres) | ((render > gt) & (err > depth_error_ratio * median(err)));
+ *       np &= mask_in (where one is given: the obj_mask_2d of models/SLAM/gaussian_object.py:447-460);  np &= gt > 0.01
+ *     with the exact lower median of the H W errors (element (n - 1) / 2 of the sorted values; NaN as soon as one error is NaN,
+ *     which switches the depth term off everywhere), found by a radix select.
+ *   FR_INGEST_MASK: the caller's bytes [H,W] (non-zero = selected).
+ * A cell is selected when any pixel of its d x d block is (max_pool2d); depth and colour of its row are those of the block's
+ * TOP-LEFT pixel (x, y) = (gx d, gy d), as in the reference, so a selected block whose top-left depth is 0 gives a point at the
+ * camera centre with log scale -inf.  downsample must divide H and W (FR_EINVAL otherwise: the reference's own shapes disagree then).
+ * intrinsics ([3,3]) and w2c ([4,4]) are DEVICE float32, row-major, read by the kernels. */
+enum { FR_INGEST_NONPRESENCE = 0, FR_INGEST_MASK = 1 };
+#define FR_INGEST_STATUS_WORDS 5
+#define FR_INGEST_WS_INDEX_OFFSET 8192   /* byte offset of the int32 index list in the workspace; the pooled mask, one byte per cell, follows it at + 4 (H/d)(W/d) */
+typedef struct {
+	int32_t H, W, downsample;
+	int32_t mode;                     /* FR_INGEST_*  (select) */
+	float sil_thres;                  /* select, FR_INGEST_NONPRESENCE */
+	float depth_error_ratio;          /* select, FR_INGEST_NONPRESENCE: densify_dict["depth_error_ratio"] */
+	int32_t transform_pts;            /* emit: 1 = world points through the inverse of w2c, 0 = camera-frame points */
+	int32_t scale_cols;               /* emit: columns of log_scales, 1 (isotropic) or 3 */
+	int32_t means_stride;             /* emit: floats between rows of means3D (3; 6 writes into an [N,6] xyz+rgb cloud) */
+	int32_t colors_stride;            /* emit: the same for rgb_colors */
+	const float* intrinsics;          /* emit: device [3,3] */
+} fr_frame_ingest_cfg;
+
+/* Host-only query (0 for a bad argument, a downsample that does not divide H and W included). */
+size_t fr_frame_ingest_workspace_bytes(int32_t H, int32_t W, int32_t downsample);
+/* depth_sil: [3,H,W], channel 0 the rendered depth, channel 1 the silhouette; gt_depth: [1,H,W] (both FR_INGEST_NONPRESENCE only);
+ * mask_in: bytes [H,W] -- the mask itself in FR_INGEST_MASK; in FR_INGEST_NONPRESENCE optional (null: none), ANDed into the predicate.  status: FR_INGEST_STATUS_WORDS device int32 = {count, median is NaN, 0, 0, the
+ * median's bits (0x7fc00000 when NaN; 0 in FR_INGEST_MASK)}.  The index list (count ascending row-major cell indices) is left in
+ * the workspace (fr_frame_ingest_workspace_bytes, 8-byte aligned) for the emit call. */
+int fr_frame_ingest_select(const fr_frame_ingest_cfg* cfg, const float* depth_sil, const float* gt_depth, const uint8_t* mask_in,
+                           int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* One row per selected cell, written to rows [row_offset, row_offset + count) of every destination that is not null: means3D
+ * [*,3] the back-projected point ((m0 X + m1 Y) + m2 Z) + m3 per row of c2w = the affine inverse of w2c; rgb_colors [*,3] the
+ * pixel's colour, bits copied; unnorm_rotations [*,4] = (1,0,0,0); logit_opacities [*,1] = 0; log_scales [*,scale_cols] =
+ * log(sqrt(mean3_sq_dist)); mean3_sq_dist [*] = (d z / ((fx + fy) / 2))^2.  color: [3,H,W]; count: status[0] as the host read it.
+ * workspace null with count == (H/d)(W/d): every cell (mask=None), no select call needed.  count == 0 launches and writes nothing. */
+int fr_frame_ingest_emit(const fr_frame_ingest_cfg* cfg, const float* color, const float* gt_depth, const float* w2c,
+                         const void* workspace, int32_t count, int64_t row_offset,
+                         float* means3D, float* rgb_colors, float* unnorm_rotations, float* logit_opacities,
+                         float* log_scales, float* mean3_sq_dist, fr_stream_t stream);
 
 /* ---- simple-knn ---------------------------------------------------------------------------------- */
 
