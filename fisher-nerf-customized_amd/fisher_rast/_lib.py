@@ -122,6 +122,27 @@ class FrameIngestCfg(ctypes.Structure):
     ]
 
 
+FR_EDIT_COPY, FR_EDIT_ZERO = 0, 1
+FR_EDIT_STATUS_WORDS = 4
+FR_EDIT_MAX_ARRAYS = 32
+FR_EDIT_MAX_COLS = 16
+
+
+def edit_ws_list_stride(P):
+    """FR_EDIT_WS_LIST_STRIDE (include/fisher_rast.h): list k of the map-edit workspace begins at byte k * this"""
+    return (int(P) * 4 + 15) & ~15
+
+
+class MapEditArray(ctypes.Structure):
+    """fr_map_edit_array (include/fisher_rast.h)"""
+    _fields_ = [
+        ("src", ctypes.c_void_p),
+        ("dst", ctypes.c_void_p),
+        ("cols", ctypes.c_int32),
+        ("appended", ctypes.c_int32),
+    ]
+
+
 # every symbol include/fisher_rast.h and include/fisher_occ.h declare
 EXPORTS = (
     "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
@@ -132,6 +153,7 @@ EXPORTS = (
     "fr_popgs_diag_criterion_workspace_bytes", "fr_popgs_diag_criterion",
     "fr_image_loss_workspace_bytes", "fr_image_loss_forward", "fr_image_loss_backward",
     "fr_frame_ingest_workspace_bytes", "fr_frame_ingest_select", "fr_frame_ingest_emit",
+    "fr_map_edit_workspace_bytes", "fr_map_edit_plan", "fr_map_edit_apply", "fr_map_edit_split_children",
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
@@ -141,8 +163,8 @@ _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_math.h", "fr_loss_math.h",
-                                                  "fr_ingest_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_math.h", "fr_loss_math.h",
+                                                  "fr_ingest_math.h", "fr_mapedit_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -293,6 +315,15 @@ def load():
         lib.fr_frame_ingest_emit.restype = ctypes.c_int
         lib.fr_frame_ingest_emit.argtypes = [ctypes.POINTER(FrameIngestCfg), _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_int32,
                                              ctypes.c_int64] + [_f32p] * 6 + [ctypes.c_void_p]
+    if hasattr(lib, "fr_map_edit_plan"):
+        lib.fr_map_edit_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_map_edit_workspace_bytes.argtypes = [ctypes.c_int32]
+        lib.fr_map_edit_plan.restype = ctypes.c_int
+        lib.fr_map_edit_plan.argtypes = [ctypes.c_int32] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_map_edit_apply.restype = ctypes.c_int
+        lib.fr_map_edit_apply.argtypes = [ctypes.POINTER(MapEditArray)] + [ctypes.c_int32] * 6 + [ctypes.c_void_p, ctypes.c_void_p]
+        lib.fr_map_edit_split_children.restype = ctypes.c_int
+        lib.fr_map_edit_split_children.argtypes = [ctypes.c_int32] * 3 + [_f32p] * 4 + [ctypes.c_void_p]
     lib.fr_densify_stats.restype = ctypes.c_int
     lib.fr_densify_stats.argtypes = [ctypes.c_int32, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]
     lib.fr_densify_masks.restype = ctypes.c_int

@@ -9,7 +9,8 @@ In scope (same names, arguments and return conventions as the reference):
     pause / resume / color_refinement / stop (1600-1614)
     get_pointcloud / initialize_params / initialize_new_params / add_new_gaussians (75-182, 299-414: module-level functions; the
         frame ingest, FrameIngestOps)
-The SLAM loop itself (init, track_rgbd, densify, keyframe selection ...) is NOT rebuilt: it is reference
+    prune_gaussians / densify / remove_points (models/SLAM/utils/slam_external.py 235-262, 345-463: the map edit, MapEditOps)
+The SLAM loop itself (init, track_rgbd, keyframe selection, the optimizer step ...) is NOT rebuilt: it is reference
 Python that stays as it is.  `FisherOps.install(cls)` grafts the accelerated methods onto the reference class
 so that tester_gaussians_navigation.py keeps calling `slam.pose_eval(...)` unchanged; `GaussianSLAM` below is
 the same operator surface as a standalone object built from a parameter dict (a `params{t}.npz` checkpoint
@@ -567,6 +568,29 @@ class FrameIngestOps:
         mod.initialize_new_params = initialize_new_params
         mod.add_new_gaussians = make_add_new_gaussians(mod.transform_to_frame, getattr(mod, "Renderer", None), object_mask=bool(object_mask))
         mod.add_new_gaussians.object_mask = bool(object_mask)
+        return target_cls
+
+
+class MapEditOps:
+    """The map edit of the mapping loop (fr_map_edit_plan / fr_map_edit_apply / fr_map_edit_split_children, include/fisher_rast.h)
+    for the reference's modules: `install(target_cls)` replaces the module-level functions `prune_gaussians`, `densify` and
+    `remove_points` of the module `target_cls` lives in (their `track_rgbd` and `prune_invisible` look these names up in the module),
+    and nothing on the class itself.  The object-aware branch of `prune_gaussians` asks that module's own
+    `get_gaussians_outside_mask` for the outside mask.  Opt-in: nothing is installed by default."""
+
+    EDIT_NAMES = ("prune_gaussians", "densify", "remove_points")
+
+    @classmethod
+    def install(cls, target_cls):
+        import sys
+        from models.SLAM.utils import slam_external as se
+        mod = sys.modules.get(target_cls.__module__)
+        if mod is None or not all(hasattr(mod, n) for n in cls.EDIT_NAMES):
+            raise ValueError(f"MapEditOps.install: the module of {target_cls.__name__} does not define {cls.EDIT_NAMES}")
+        edit = se.MapEdit(se.HipMapEditBackend(), outside_mask_fn=getattr(mod, "get_gaussians_outside_mask", None))
+        mod.prune_gaussians = edit.prune_gaussians
+        mod.densify = edit.densify
+        mod.remove_points = edit.remove_points
         return target_cls
 
 

@@ -41,6 +41,8 @@
  *                           models/SLAM/utils/slam_helpers.py:23-77, models/SLAM/utils/slam_external.py:77-193
  *   fr_frame_ingest_select / fr_frame_ingest_emit <- add_new_gaussians / get_pointcloud / initialize_new_params,
  *                           models/SLAM/gaussian.py:320-414, 75-143, 299-318
+ *   fr_map_edit_plan / fr_map_edit_apply / fr_map_edit_split_children <- remove_points / cat_params_to_optimizer and the split
+ *                           children of densify, models/SLAM/utils/slam_external.py:218-262, 411-463 over 25-42
  *   fr_knn_dist2         <- simple_knn._C.distCUDA2 (thirdparty/simple-knn, un-vendored submodule)
  *
  * The pybind module `_C` of the reference (RAST/ext.cpp:14-18) is re-created in Python on top of
@@ -488,6 +490,47 @@ int fr_frame_ingest_emit(const fr_frame_ingest_cfg* cfg, const float* color, con
                          const void* workspace, int32_t count, int64_t row_offset,
                          float* means3D, float* rgb_colors, float* unnorm_rotations, float* logit_opacities,
                          float* log_scales, float* mean3_sq_dist, fr_stream_t stream);
+
+/* ---- map edit: a prune or densify mask applied to the map, its Adam state and its statistics --------------------------
+ * In place of remove_points / cat_params_to_optimizer and the clone / split of densify (models/SLAM/utils/slam_external.py:218-262,
+ * 411-463): a row's destination depends on the masks alone, so one ordered compaction of the masks (plan) and one gather over a
+ * table of arrays (apply) do the work of the reference's boolean indexings and cats, with one host read of the three counts between
+ * them to size the new tensors.  Nothing is allocated inside; integer sums only (the same call gives the same lists). */
+enum { FR_EDIT_COPY = 0, FR_EDIT_ZERO = 1 };
+#define FR_EDIT_STATUS_WORDS 4
+#define FR_EDIT_MAX_ARRAYS 32
+#define FR_EDIT_MAX_COLS 16
+/* the ascending int32 list k (0 kept rows, 1 cloned rows, 2 split rows) begins at byte k * FR_EDIT_WS_LIST_STRIDE(P) of the workspace */
+#define FR_EDIT_WS_LIST_STRIDE(P) ((((size_t)(P)) * 4 + 15) & ~(size_t)15)
+typedef struct {
+	const void* src;                  /* device [P, cols] 4-byte words */
+	void* dst;                        /* device [n_keep + n_clone + n_into n_split, cols]; overlaps no source and no other destination */
+	int32_t cols;                     /* 1 .. FR_EDIT_MAX_COLS */
+	int32_t appended;                 /* FR_EDIT_COPY: clones and children carry their source row (parameters);
+	                                     FR_EDIT_ZERO: the appended rows are zero (Adam moments, timestep) */
+} fr_map_edit_array;
+
+/* Host-only query (0 for a negative P). */
+size_t fr_map_edit_workspace_bytes(int32_t P);
+/* keep, clone, split: byte masks over the P source rows (non-zero = selected); any may be null -- a null keep keeps every row, a
+ * null clone / split selects none.  Leaves the three ascending index lists in the workspace (fr_map_edit_workspace_bytes, 8-byte
+ * aligned; FR_ENOSPACE when short) and status = {n_keep, n_clone, n_split, 0} (FR_EDIT_STATUS_WORDS device int32).  Three launches:
+ * count, a one-workgroup scan, scatter.  P == 0 launches nothing and writes zeros to status. */
+int fr_map_edit_plan(int32_t P, const uint8_t* keep, const uint8_t* clone, const uint8_t* split, int32_t* status,
+                     void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* One launch for the whole table (HOST array of n_arrays <= FR_EDIT_MAX_ARRAYS entries, passed in the kernel arguments).  Rows are
+ * copied as bits.  The destination's rows are: the kept rows in ascending source order; the clones in ascending source order; the
+ * children copy-major (every split row for copy 0, then for copy 1, ... n_into copies) -- the order of
+ * cat((v[keep], v[to_clone], v[to_split].repeat(n_into, 1))).  n_keep, n_clone, n_split: the status as the host read it; the
+ * workspace is the one the plan call wrote for this P.  FR_EINVAL for src == dst, a destination that overlaps a source or another
+ * destination, cols outside 1 .. FR_EDIT_MAX_COLS or more than FR_EDIT_MAX_ARRAYS arrays.  A destination of zero rows launches nothing. */
+int fr_map_edit_apply(const fr_map_edit_array* table, int32_t n_arrays, int32_t P, int32_t n_keep, int32_t n_clone, int32_t n_split,
+                      int32_t n_into, const void* workspace, fr_stream_t stream);
+/* The split children of densify, in place on the n_into n_split child rows of the destination (pointers already offset to the first
+ * child): reads each child's copied unnorm_rotations [*,4] and log_scales [*,scale_cols] (1 or 3) and its normal sample z [*,3], and
+ * writes means += R (z exp(log_scales)), log_scales = log(exp(log_scales) / (0.8 n_into)) -- csrc/fr_mapedit_math.h. */
+int fr_map_edit_split_children(int32_t n_split, int32_t n_into, int32_t scale_cols, const float* z, float* means,
+                               const float* unnorm_rotations, float* log_scales, fr_stream_t stream);
 
 /* ---- simple-knn ---------------------------------------------------------------------------------- */
 

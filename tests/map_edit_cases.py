@@ -1,0 +1,477 @@
+"""Inputs, a binary32 NumPy restatement, a NumPy backend and the golden-case plumbing for the map edit (fr_map_edit_plan / _apply /
+_split_children, csrc/fr_mapedit.hip; remove_points / prune_gaussians / densify of models/SLAM/utils/slam_external.py).
+
+`np_rotation` / `np_split` restate csrc/fr_mapedit_math.h in NumPy binary32 with the header's operand order: every operation is one
+of + - x / sqrt, each correctly rounded in both, and exp is the oracle's orc_expf (the fixed IEEE sequence of fr_expf, held to it bit
+for bit by tests/test_kernel_math_cpu.py) -- so they reproduce the header bit for bit, all but logf.  `NumpyBackend` is the CPU
+stand-in for slam_external.HipMapEditBackend: np.flatnonzero plans, fancy indexing applies, the restatements of oracle/densify_stats.py
+give the masks; the bookkeeping Python above it (slam_external.MapEdit) is the product's own.  The reference's outputs are
+tests/golden/reference_map_edit.npz (tests/golden/make_reference_map_edit_vectors.py); `build_inputs` rebuilds a case's parameters,
+Adam state and statistics from the recorded arrays on any device, `snapshot` reads them back."""
+import os
+
+import numpy as np
+
+F = np.float32
+MAP_KEYS = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales")
+CAM_KEYS = ("cam_unnorm_rots", "cam_trans")
+STAT_KEYS = ("means2D_gradient_accum", "denom", "max_2D_radius")
+STATELESS = "rgb_colors"                      # the group that never saw a gradient: it has no Adam state
+ADAM_STEP = 3.0
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_map_edit.npz")
+
+# child means: |got - binary64 chain| <= K 2^-24 (|mean_r| + sum_j |z_j std_j|).  Needed on the CPU over quaternion norms from 1e-3 to
+# 50 and scales from 0.003 to 0.3 (printed by tests/test_map_edit_cpu.py, which fails when the measurement moves away from the figure
+# recorded here and in DESIGN.md section 2); K used is twice that, under the cap of 16.
+K_NEEDED_CPU = 5.32
+K_CHILD = min(16.0, round(2 * K_NEEDED_CPU, 1))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+def log_scale_ok(got, want64):
+    import ingest_cases
+    return ingest_cases.log_scale_ok(got, want64)
+
+
+# ---- inputs ----------------------------------------------------------------------------------------------------------------------
+
+def make_state(P, cols, seed, quantum=2.0 ** -7):
+    """raw float32 arrays of a map of P rows: 'p/<key>' parameters (camera ones included), 'm/<key>' / 'v/<key>' Adam moments,
+    'var/<key>' statistics, 'grad2d' the gradient of means2D, 'z' normal samples [4 P, 3].  The first rows sit on the thresholds:
+    exp(log_scale) == 0.05 / 0.1 and sigmoid(logit) == 0.005 as nearly as float32 allows, as tests/test_gpu_densify_stats.py has them.
+    Values are multiples of `quantum` where nothing depends on their low bits (the file compresses)."""
+    rng = np.random.default_rng([P, cols, seed, 20250601])
+    q = lambda a: (np.round(np.asarray(a) / quantum) * quantum).astype(F)
+    st = {}
+    st["p/means3D"] = q(rng.uniform(-2, 2, (P, 3)))
+    st["p/rgb_colors"] = q(rng.uniform(0, 1, (P, 3)))
+    rot = q(rng.normal(0, 1, (P, 4)))
+    rot[np.abs(rot).sum(1) == 0] = 1.0
+    rot[: P // 3] *= F(0.125)                                                   # unnormalised: norms well away from 1
+    rot[P // 3: P // 2] *= F(8.0)
+    st["p/unnorm_rotations"] = rot.astype(F)
+    ls = q(rng.normal(np.log(0.025), 0.7, (P, cols)))
+    lo = q(rng.normal(0.0, 3.0, (P, 1)))
+    t = min(P // 4, 3)
+    ls[:t] = F(np.log(0.05)); ls[t:2 * t] = np.nextafter(F(np.log(0.05)), F(1)); ls[2 * t:3 * t] = F(np.log(0.1))
+    ls[3 * t:4 * t] = np.nextafter(F(np.log(0.1)), F(1))
+    lo[:t, 0] = F(np.log(0.005 / 0.995)); lo[t:2 * t, 0] = np.nextafter(lo[0, 0], F(-10))
+    lo[2 * t:4 * t, 0] = F(3.0)                                                 # the big-scale rows survive the opacity test
+    st["p/log_scales"], st["p/logit_opacities"] = ls, lo
+    st["p/cam_unnorm_rots"] = q(rng.normal(0, 1, (1, 4, 2)))
+    st["p/cam_trans"] = q(rng.normal(0, 1, (1, 3, 2)))
+    for k in MAP_KEYS + CAM_KEYS:
+        st["m/" + k] = q(rng.normal(0, 1, st["p/" + k].shape))
+        st["v/" + k] = q(rng.uniform(0, 1, st["p/" + k].shape))
+    acc = q(rng.uniform(0, 0.5, P))
+    den = rng.integers(0, 4, P).astype(F)
+    acc[den == 0] = 0
+    st["var/means2D_gradient_accum"], st["var/denom"] = acc, den
+    st["var/max_2D_radius"] = q(rng.uniform(0, 40, P))
+    st["var/timestep"] = rng.integers(0, 9, P).astype(F)
+    st["var/seen"] = rng.uniform(size=P) < 0.6
+    st["var/scene_radius"] = np.array(1.7, F)
+    g = q(rng.normal(0, 0.25, (P, 3)))
+    g[:, 2] = 0
+    st["grad2d"] = g
+    st["z"] = q(rng.normal(0, 1, (4 * P, 3)))
+    return st
+
+
+def build_inputs(st, device, optimizer=True, state=True, timestep=True):
+    """(params, variables, optimizer or None) of a case on `device`.  With `state`, a real torch.optim.Adam takes one step (every
+    group but STATELESS has a gradient, so that one ends up without state), then parameters, moments and step hold the recorded values."""
+    import torch
+    t = lambda a: torch.from_numpy(np.array(a, copy=True)).to(device)          # never the caller's memory
+    params = {k: torch.nn.Parameter(t(st["p/" + k]).requires_grad_(True)) for k in MAP_KEYS + CAM_KEYS}
+    opt = None
+    if optimizer:
+        opt = torch.optim.Adam([dict(params=[v], name=k, lr=1e-3) for k, v in params.items()])
+        if state:
+            for k, v in params.items():
+                v.grad = None if k == STATELESS else torch.ones_like(v)
+            opt.step()
+            for k, v in params.items():
+                v.grad = None
+                with torch.no_grad():
+                    v.copy_(t(st["p/" + k]))
+                    if k != STATELESS:
+                        s = opt.state[v]
+                        s["exp_avg"].copy_(t(st["m/" + k]))
+                        s["exp_avg_sq"].copy_(t(st["v/" + k]))
+                        s["step"].fill_(ADAM_STEP)
+    variables = {k: t(st["var/" + k]) for k in STAT_KEYS}
+    if timestep:
+        variables["timestep"] = t(st["var/timestep"])
+    variables["seen"] = t(st["var/seen"])
+    variables["scene_radius"] = t(st["var/scene_radius"])
+    m2d = torch.zeros(st["grad2d"].shape, device=device, requires_grad=True)
+    m2d.grad = t(st["grad2d"])
+    variables["means2D"] = m2d
+    return params, variables, opt
+
+
+def snapshot(params, variables, optimizer=None):
+    """numpy copies: 'p/<key>', and with state 'm/<key>', 'v/<key>', 'step/<key>'; 'var/<key>' for the statistics and timestep;
+    'len/seen', 'len/means2D'"""
+    out = {}
+    for k in MAP_KEYS + CAM_KEYS:
+        out["p/" + k] = params[k].detach().cpu().numpy().copy()
+        if optimizer is not None:
+            group = [g for g in optimizer.param_groups if g["name"] == k][0]
+            s = optimizer.state.get(group["params"][0], None)
+            if s:
+                out["m/" + k], out["v/" + k] = s["exp_avg"].cpu().numpy().copy(), s["exp_avg_sq"].cpu().numpy().copy()
+                out["step/" + k] = np.array(float(s["step"]), F)
+    for k in STAT_KEYS + ("timestep",):
+        if k in variables:
+            out["var/" + k] = variables[k].detach().cpu().numpy().copy()
+    out["len/seen"] = np.array(variables["seen"].shape[0], np.int32)
+    out["len/means2D"] = np.array(variables["means2D"].shape[0], np.int32)
+    return out
+
+
+def check_bookkeeping(params, variables, optimizer, before):
+    """what the reference's bookkeeping guarantees beside the values: `before` = (params, optimizer state dicts by name) from
+    `remember` before the call"""
+    old_params, old_states, cam = before
+    for k in CAM_KEYS:
+        assert params[k] is cam[k], f"{k} was replaced"
+    if optimizer is None:
+        return
+    for k in MAP_KEYS:
+        group = [g for g in optimizer.param_groups if g["name"] == k][0]
+        p = group["params"][0]
+        assert params[k] is p and p.grad is None and p.requires_grad and p.is_leaf
+        if old_states[k] is not None:
+            assert optimizer.state[p] is old_states[k], f"{k}: the state dict did not move to the new parameter"
+            assert p is old_params[k] or old_params[k] not in optimizer.state
+            assert float(old_states[k]["step"]) == ADAM_STEP
+            assert optimizer.state[p]["exp_avg"].shape == p.shape == optimizer.state[p]["exp_avg_sq"].shape
+        else:
+            assert p not in optimizer.state or not optimizer.state[p]
+
+
+def remember(params, optimizer):
+    states = {k: None for k in MAP_KEYS}
+    if optimizer is not None:
+        for k in MAP_KEYS:
+            group = [g for g in optimizer.param_groups if g["name"] == k][0]
+            states[k] = optimizer.state.get(group["params"][0], None) or None
+    return dict(params), states, {k: params[k] for k in CAM_KEYS}
+
+
+# ---- the golden cases ------------------------------------------------------------------------------------------------------------
+
+PRUNE = dict(start_after=0, remove_big_after=100, stop_after=40, prune_every=10, removal_opacity_threshold=0.005,
+             final_removal_opacity_threshold=0.005, reset_opacities=False, reset_opacities_every=500)
+DENSIFY = dict(start_after=0, remove_big_after=3000, stop_after=5000, densify_every=10, grad_thresh=0.2, num_to_split_into=2,
+               removal_opacity_threshold=0.005, final_removal_opacity_threshold=0.005, reset_opacities=False, reset_opacities_every=3000)
+P_GOLDEN = 37
+# name -> (function, state key, keyword arguments); "state" 3 / 1: the columns of log_scales
+CASES = {
+    "remove/optimizer": dict(fn="remove_points", cols=3, optimizer=True, state=True, timestep=True),
+    "remove/no-optimizer": dict(fn="remove_points", cols=3, optimizer=False, state=False, timestep=False),
+    "cat/state": dict(fn="cat", cols=3, optimizer=True, state=True, timestep=True),
+    "cat/no-state": dict(fn="cat", cols=3, optimizer=True, state=False, timestep=True),
+    "prune/before-stop": dict(fn="prune", cols=3, iter=20, cfg=PRUNE),
+    "prune/at-stop": dict(fn="prune", cols=3, iter=40, cfg=dict(PRUNE, final_removal_opacity_threshold=0.3)),
+    "prune/big": dict(fn="prune", cols=3, iter=20, cfg=dict(PRUNE, remove_big_after=20)),
+    "prune/off-beat-reset": dict(fn="prune", cols=1, iter=15, cfg=dict(PRUNE, reset_opacities=True, reset_opacities_every=15)),
+    "densify/n2": dict(fn="densify", cols=3, iter=20, cfg=DENSIFY),
+    "densify/n3-big": dict(fn="densify", cols=3, iter=20, cfg=dict(DENSIFY, num_to_split_into=3, remove_big_after=20)),
+    "densify/n2-iso": dict(fn="densify", cols=1, iter=20, cfg=dict(DENSIFY, remove_big_after=10)),
+    "densify/n3-iso-stop": dict(fn="densify", cols=1, iter=5000, cfg=dict(DENSIFY, num_to_split_into=3, final_removal_opacity_threshold=0.2)),
+}
+for _c in CASES.values():
+    _c.setdefault("optimizer", True); _c.setdefault("state", True); _c.setdefault("timestep", True)
+
+
+def state_of(case, gold=None):
+    """the recorded inputs of a case (the generator passes no file and makes them)"""
+    cols = CASES[case]["cols"]
+    if gold is None:
+        return make_state(P_GOLDEN, cols, 11)
+    pre = f"state{cols}/"
+    return {k[len(pre):]: v for k, v in gold.items() if k.startswith(pre)}
+
+
+def removal_mask(P):
+    rng = np.random.default_rng([P, 77])
+    m = rng.uniform(size=P) < 0.55
+    m[0], m[-1] = True, False
+    return m
+
+
+def new_rows(st, n=5):
+    """the rows `cat` appends: the first n of every map parameter, negated"""
+    return {k: -st["p/" + k][:n] for k in MAP_KEYS}
+
+
+def run_case(case, fns, st, device):
+    """Runs a golden case's call through `fns` (an object with the five functions) on inputs built on `device`; returns
+    (snapshot, params, variables, optimizer, what `remember` saw before).  The caller sees to it that densify's normal samples
+    are st["z"]."""
+    import torch
+    c = CASES[case]
+    params, variables, opt = build_inputs(st, device, c["optimizer"], c["state"], c["timestep"])
+    before = remember(params, opt)
+    if c["fn"] == "remove_points":
+        m = torch.from_numpy(removal_mask(P_GOLDEN)).to(device)
+        params, variables = fns.remove_points(m, params, variables, opt) if opt is not None else fns.remove_points(m, params, variables)
+    elif c["fn"] == "cat":
+        new = {k: torch.from_numpy(v).to(device) for k, v in new_rows(st).items()}
+        params = fns.cat_params_to_optimizer(new, params, opt)
+    elif c["fn"] == "prune":
+        params, variables = fns.prune_gaussians(params, variables, opt, c["iter"], dict(c["cfg"]))
+    else:
+        params, variables = fns.densify(params, variables, opt, c["iter"], dict(c["cfg"]))
+    return snapshot(params, variables, opt), params, variables, opt, before
+
+
+def pack(arrays):
+    """(one uint32 blob, its layout as a JSON string) of a dict of float32 / int32 / bool arrays: a zip member per array would cost
+    more than the arrays"""
+    import json
+    words, layout = [], []
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.int32, np.bool_), (k, a.dtype)
+        w = a.astype(np.int32).reshape(-1).view(np.uint32) if a.dtype == np.bool_ else np.ascontiguousarray(a).reshape(-1).view(np.uint32)
+        layout.append([k, a.dtype.name, list(a.shape)])
+        words.append(w)
+    return np.concatenate(words) if words else np.zeros(0, np.uint32), json.dumps(layout)
+
+
+def unpack(blob, layout):
+    import json
+    out, o = {}, 0
+    for k, dtype, shape in json.loads(str(layout)):
+        n = int(np.prod(shape, dtype=np.int64))
+        w = blob[o:o + n]
+        o += n
+        out[k] = (w.view(np.int32) != 0).reshape(shape) if dtype == "bool" else w.view(np.dtype(dtype)).reshape(shape).copy()
+    assert o == blob.size
+    return out
+
+
+def load_golden():
+    """{"<group>/<key>": array} for the groups "state3", "state1" and every case"""
+    out = {}
+    with np.load(GOLDEN) as z:
+        for g in z["groups"]:
+            for k, v in unpack(z[f"{g}:data"], z[f"{g}:layout"]).items():
+                out[f"{g}/{k}"] = v
+    return out
+
+
+def golden_of(gold, case):
+    pre = case + "/"
+    return {k[len(pre):]: v for k, v in gold.items() if k.startswith(pre)}
+
+
+def child_chain64(st, case, gold_case):
+    """(rows, means64 [n,3], scale [n], log_scales64 [n,cols]): for the child rows of a densify case's final map, the reference
+    chain in binary64 from the binary32 inputs -- mean + R (z exp(log_scales)), log(exp(log_scales) / (0.8 n)) -- and the scale of
+    the K rule, |mean_r| + sum_j |z_j std_j| per component [n,3]"""
+    ci, src = gold_case["child_index"], gold_case["child_src"]
+    rows = np.flatnonzero(ci >= 0)
+    n_into = CASES[case]["cfg"]["num_to_split_into"]
+    s, j = src[rows], ci[rows]
+    q = st["p/unnorm_rotations"][s].astype(np.float64)
+    R = rotation64(q)
+    ls = st["p/log_scales"][s].astype(np.float64)
+    std = np.exp(ls) * np.ones((1, 3))
+    zs = st["z"][j].astype(np.float64) * std
+    mean = st["p/means3D"][s].astype(np.float64)
+    means64 = mean + np.einsum("nij,nj->ni", R, zs)
+    scale = np.abs(mean) + np.abs(zs).sum(1, keepdims=True)
+    logs64 = np.log(np.exp(ls) / np.float64(F(0.8 * n_into)))
+    return rows, means64, scale, logs64
+
+
+def rotation64(q):
+    q = q / np.sqrt((q * q).sum(1, keepdims=True))
+    r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    return np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                     2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                     2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
+
+
+def k_need(got, want64, scale):
+    """max over rows and components of |got - want64| / (2^-24 scale): the K the rule would have to hold"""
+    dev = np.abs(np.asarray(got, np.float64) - want64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        need = np.where(dev == 0, 0.0, dev / (2.0 ** -24 * scale))
+    return float(need.max()) if need.size else 0.0
+
+
+def compare_with_golden(case, st, got, want):
+    """every array of the two snapshots: bit for bit, except the children of a densify case (means by the K rule, log scales by
+    log_scale_ok, both against the binary64 chain -- the golden's own values are held to the same rules).  No row is left out."""
+    assert set(got) == set(k for k in want if not k.startswith("child_")), (sorted(got), sorted(want))
+    child = np.zeros(0, bool)
+    if "child_index" in want:
+        child = want["child_index"] >= 0
+        rows, means64, scale, logs64 = child_chain64(st, case, want)
+    for k, w in want.items():
+        if k.startswith("child_"):
+            continue
+        g = got[k]
+        assert g.shape == w.shape and g.dtype == w.dtype, (case, k, g.shape, w.shape, g.dtype, w.dtype)
+        if child.any() and k in ("p/means3D", "p/log_scales"):
+            assert np.array_equal(bits(g)[~child], bits(w)[~child]), (case, k)
+            for which, a in (("ours", g), ("reference", w)):
+                if k == "p/means3D":
+                    need = k_need(a[rows], means64, scale)
+                    assert need <= K_CHILD, (case, which, "child means: K needed", need)
+                else:
+                    assert log_scale_ok(a[rows], logs64), (case, which, "child log scales")
+        elif w.dtype == np.float32:
+            assert np.array_equal(bits(g), bits(w)), (case, k)
+        else:
+            assert np.array_equal(g, w), (case, k)
+
+
+# ---- the binary32 restatement of csrc/fr_mapedit_math.h -------------------------------------------------------------------------
+
+def np_rotation(q):
+    q = np.asarray(q, F)
+    norm = np.sqrt(((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3])
+    r, x, y, z = q[:, 0] / norm, q[:, 1] / norm, q[:, 2] / norm, q[:, 3] / norm
+    one, two = F(1), F(2)
+    return np.stack([one - two * (y * y + z * z), two * (x * y - r * z), two * (x * z + r * y),
+                     two * (x * y + r * z), one - two * (x * x + z * z), two * (y * z - r * x),
+                     two * (x * z - r * y), two * (y * z + r * x), one - two * (x * x + y * y)], 1).astype(F)
+
+
+def np_split(expf, z, means, rot, logs, n_into):
+    """(means' [n,3] float32, the binary32 argument of logf [n,cols]) for n children; expf: oracle.ref.expf"""
+    z, means, logs = np.asarray(z, F), np.asarray(means, F), np.asarray(logs, F)
+    cols = logs.shape[1]
+    R = np_rotation(rot)
+    std = expf(logs).astype(F)
+    s = np.stack([z[:, c] * std[:, min(c, cols - 1)] for c in range(3)], 1)
+    off = np.stack([(R[:, 3 * r] * s[:, 0] + R[:, 3 * r + 1] * s[:, 1]) + R[:, 3 * r + 2] * s[:, 2] for r in range(3)], 1)
+    return (means + off).astype(F), (std / F(0.8 * n_into)).astype(F)
+
+
+# ---- the NumPy backend of slam_external.MapEdit -----------------------------------------------------------------------------------
+
+class NumpyBackend:
+    """CPU stand-in for slam_external.HipMapEditBackend: the same five operations on CPU tensors.  Masks come from
+    oracle/densify_stats.py (the kernels' arithmetic); the children from the g++ harness over the header."""
+
+    def __init__(self, harness, z=None):
+        self.h, self.z = harness, z
+        self.plans = self.applies = 0
+
+    @staticmethod
+    def _np(t):
+        return t.detach().cpu().numpy()
+
+    def prune_mask(self, params, opacity_thresh, big_thresh=None):
+        import torch
+        from oracle import densify_stats as ods
+        return torch.from_numpy(ods.prune_mask(self._np(params["logit_opacities"]), self._np(params["log_scales"]), opacity_thresh, big_thresh))
+
+    def densify_masks(self, params, variables, grad_thresh):
+        import torch
+        from oracle import densify_stats as ods
+        c, s = ods.densify_masks(self._np(variables["means2D_gradient_accum"]), self._np(variables["denom"]), self._np(params["log_scales"]), grad_thresh)
+        return torch.from_numpy(c), torch.from_numpy(s)
+
+    def accumulate(self, variables):
+        import torch
+        from oracle import densify_stats as ods
+        a, d = ods.accumulate_mean2d_gradient(self._np(variables["means2D"].grad), self._np(variables["seen"]),
+                                              self._np(variables["means2D_gradient_accum"]), self._np(variables["denom"]))
+        variables["means2D_gradient_accum"], variables["denom"] = torch.from_numpy(a), torch.from_numpy(d)
+        return variables
+
+    def plan(self, P, keep, clone, split, n_into, device, read_with=None):
+        from models.SLAM.utils.slam_external import MapEditPlan
+        self.plans += 1
+        lists = [np.arange(P) if keep is None else np.flatnonzero(self._np(keep))]
+        lists += [np.zeros(0, np.int64) if m is None else np.flatnonzero(self._np(m)) for m in (clone, split)]
+        extra = read_with.detach().cpu() if hasattr(read_with, "detach") else read_with
+        return MapEditPlan(P, len(lists[0]), len(lists[1]), len(lists[2]), n_into, lists), extra
+
+    def apply(self, plan, table):
+        import torch
+        self.applies += 1
+        keep, clone, split = plan.handle
+        out = []
+        for src, mode in table:
+            a = self._np(src)
+            assert a.shape[0] == plan.P
+            tail = np.concatenate([a[clone]] + [a[split]] * plan.n_into)
+            if mode == 1:
+                tail = np.zeros_like(tail)
+            out.append(torch.from_numpy(np.concatenate([a[keep], tail]).copy()))
+        return out
+
+    def randn(self, rows, like, generator=None):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(self.z[:rows])) if self.z is not None else torch.randn((rows, 3), generator=generator)
+
+    def split_children(self, plan, z, means, rots, logs):
+        c = plan.first_child
+        m, l = self._np(means)[c:], self._np(logs)[c:]               # views of the tensors' memory: written in place
+        harness_split(self.h, plan.n_into, self._np(z), m, np.ascontiguousarray(self._np(rots)[c:]), l)
+
+
+# ---- the g++ harness over csrc/fr_mapedit_math.h (tests/harness/fr_mapedit_harness.cpp) ------------------------------------------
+
+def build_harness():
+    import ctypes
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdir = os.path.join(root, "tests", "harness")
+    so = os.path.join(hdir, "libfr_mapedit_harness.so")
+    csrc = os.path.join(root, "fisher-nerf-customized_amd", "csrc")
+    srcs = [os.path.join(hdir, "fr_mapedit_harness.cpp"), os.path.join(csrc, "fr_mapedit_math.h"), os.path.join(csrc, "fr_math.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
+    h = ctypes.CDLL(so)
+    vp = ctypes.c_void_p
+    h.frm_rotations.argtypes = [ctypes.c_int, vp, vp]
+    h.frm_rotations.restype = None
+    h.frm_divisor.argtypes = [ctypes.c_int]
+    h.frm_divisor.restype = ctypes.c_float
+    h.frm_split.argtypes = [ctypes.c_int] * 3 + [vp] * 4
+    h.frm_split.restype = None
+    return h
+
+
+def harness_rotations(h, q):
+    q = np.ascontiguousarray(q, F)
+    R = np.zeros((q.shape[0], 9), F)
+    h.frm_rotations(q.shape[0], q.ctypes.data, R.ctypes.data)
+    return R
+
+
+def harness_split(h, n_into, z, means, rot, logs):
+    """in place on means [n,3] and logs [n,cols] (C-contiguous float32)"""
+    n = means.shape[0]
+    cols = logs.shape[1] if logs.ndim == 2 else 1
+    for a in (z, means, rot, logs):
+        assert a.dtype == F and a.flags["C_CONTIGUOUS"]
+    assert z.shape[0] >= n and rot.shape[0] == n
+    if n:
+        h.frm_split(n, n_into, cols, z.ctypes.data, means.ctypes.data, rot.ctypes.data, logs.ctypes.data)
+
+
+def sweep(n=4096, seed=5):
+    """children over quaternion norms from 1e-3 to 50 and scales from 0.003 to 0.3: (z, means, rot, logs [n,3]) float32"""
+    rng = np.random.default_rng(seed)
+    q = rng.normal(size=(n, 4))
+    q *= (np.exp(rng.uniform(np.log(1e-3), np.log(50.0), n)) / np.linalg.norm(q, axis=1))[:, None]
+    logs = np.log(np.exp(rng.uniform(np.log(0.003), np.log(0.3), (n, 3))))
+    means = rng.uniform(-3, 3, (n, 3))
+    means[: n // 8] *= 0.01                                     # means small against the offsets, too
+    z = rng.normal(size=(n, 3))
+    return z.astype(F), means.astype(F), q.astype(F), logs.astype(F)
