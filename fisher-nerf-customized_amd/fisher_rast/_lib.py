@@ -143,6 +143,27 @@ class MapEditArray(ctypes.Structure):
     ]
 
 
+FR_ADAM_MAX_ARRAYS = 16
+
+
+class AdamArray(ctypes.Structure):
+    """fr_adam_array (include/fisher_rast.h)"""
+    _fields_ = [
+        ("param", ctypes.c_void_p),
+        ("grad", ctypes.c_void_p),
+        ("exp_avg", ctypes.c_void_p),
+        ("exp_avg_sq", ctypes.c_void_p),
+        ("n", ctypes.c_int64),
+        ("w1", ctypes.c_float),
+        ("beta2", ctypes.c_float),
+        ("c2", ctypes.c_float),
+        ("bc2_sqrt", ctypes.c_float),
+        ("eps", ctypes.c_float),
+        ("neg_step_size", ctypes.c_float),
+        ("fresh", ctypes.c_int32),
+    ]
+
+
 # every symbol include/fisher_rast.h and include/fisher_occ.h declare
 EXPORTS = (
     "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
@@ -153,7 +174,7 @@ EXPORTS = (
     "fr_popgs_diag_criterion_workspace_bytes", "fr_popgs_diag_criterion",
     "fr_image_loss_workspace_bytes", "fr_image_loss_forward", "fr_image_loss_backward",
     "fr_frame_ingest_workspace_bytes", "fr_frame_ingest_select", "fr_frame_ingest_emit",
-    "fr_map_edit_workspace_bytes", "fr_map_edit_plan", "fr_map_edit_apply", "fr_map_edit_split_children",
+    "fr_map_edit_workspace_bytes", "fr_map_edit_plan", "fr_map_edit_apply", "fr_map_edit_split_children", "fr_adam_step",
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
@@ -163,8 +184,8 @@ _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_math.h", "fr_loss_math.h",
-                                                  "fr_ingest_math.h", "fr_mapedit_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_math.h",
+                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -324,6 +345,9 @@ def load():
         lib.fr_map_edit_apply.argtypes = [ctypes.POINTER(MapEditArray)] + [ctypes.c_int32] * 6 + [ctypes.c_void_p, ctypes.c_void_p]
         lib.fr_map_edit_split_children.restype = ctypes.c_int
         lib.fr_map_edit_split_children.argtypes = [ctypes.c_int32] * 3 + [_f32p] * 4 + [ctypes.c_void_p]
+    if hasattr(lib, "fr_adam_step"):
+        lib.fr_adam_step.restype = ctypes.c_int
+        lib.fr_adam_step.argtypes = [ctypes.POINTER(AdamArray), ctypes.c_int32, ctypes.c_void_p]
     lib.fr_densify_stats.restype = ctypes.c_int
     lib.fr_densify_stats.argtypes = [ctypes.c_int32, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]
     lib.fr_densify_masks.restype = ctypes.c_int

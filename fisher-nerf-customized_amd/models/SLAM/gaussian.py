@@ -594,6 +594,29 @@ class MapEditOps:
         return target_cls
 
 
+class OptimizerOps:
+    """The optimizer step of the tracking and mapping loops (fr_adam_step, include/fisher_rast.h) for the reference's classes:
+    `install(target_cls)` replaces the method `get_optimizer(self, tracking)` (models/SLAM/gaussian.py:1458-1469 and
+    models/SLAM/gaussian_object.py:1815-1826, which are identical) by one that builds the same seven groups of one tensor, with the
+    same names, learning rates (`self.config[...]["lrs"]`) and eps, and returns a fisher_rast.optim.FusedAdam.  `skip_frozen=True`
+    additionally leaves the lr == 0 groups -- the whole map, in tracking -- out of the step (see FusedAdam for what that changes).
+    Opt-in: nothing is installed by default."""
+
+    @classmethod
+    def install(cls, target_cls, skip_frozen=False):
+        from fisher_rast.optim import FusedAdam
+
+        def get_optimizer(self, tracking):
+            lrs_dict = self.config["tracking"]["lrs"] if tracking else self.config["mapping"]["lrs"]
+            param_groups = [{'params': [v], 'name': k, 'lr': lrs_dict[k]} for k, v in self.params.items()]
+            if tracking:
+                return FusedAdam(param_groups, skip_frozen=skip_frozen)
+            return FusedAdam(param_groups, lr=0.0, eps=1e-15, skip_frozen=skip_frozen)
+
+        target_cls.get_optimizer = get_optimizer
+        return target_cls
+
+
 class GaussianSLAM(FisherOps, PoseFisherOps, RenderOps, PointScoreOps):
     """Standalone carrier of the operator surface: a Gaussian map (param dict), a camera and keyframes."""
 

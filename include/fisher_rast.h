@@ -43,6 +43,8 @@
  *                           models/SLAM/gaussian.py:320-414, 75-143, 299-318
  *   fr_map_edit_plan / fr_map_edit_apply / fr_map_edit_split_children <- remove_points / cat_params_to_optimizer and the split
  *                           children of densify, models/SLAM/utils/slam_external.py:218-262, 411-463 over 25-42
+ *   fr_adam_step         <- optimizer.step() of the torch.optim.Adam that get_optimizer builds (seven groups of one tensor),
+ *                           models/SLAM/gaussian.py:1458-1469, models/SLAM/gaussian_object.py:1815-1826
  *   fr_knn_dist2         <- simple_knn._C.distCUDA2 (thirdparty/simple-knn, un-vendored submodule)
  *
  * The pybind module `_C` of the reference (RAST/ext.cpp:14-18) is re-created in Python on top of
@@ -531,6 +533,26 @@ int fr_map_edit_apply(const fr_map_edit_array* table, int32_t n_arrays, int32_t 
  * writes means += R (z exp(log_scales)), log_scales = log(exp(log_scales) / (0.8 n_into)) -- csrc/fr_mapedit_math.h. */
 int fr_map_edit_split_children(int32_t n_split, int32_t n_into, int32_t scale_cols, const float* z, float* means,
                                const float* unnorm_rotations, float* log_scales, fr_stream_t stream);
+
+/* ---- fused Adam step: one launch over a table of parameter arrays ------------------------------------------------------
+ * In place of optimizer.step() of the reference's torch.optim.Adam (amsgrad, maximize and weight decay off): per element, in binary32
+ * and in this operand order (csrc/fr_adam_math.h; no contraction, IEEE divide and sqrt, so a g++ build of that header gives the same bits)
+ *   m' = |w1| < 0.5 ? m + w1 (g - m) : g - (g - m)(1 - w1);   v' = v beta2 + (c2 g) g;   p' = p + neg_step_size (m' / (sqrt(v') / bc2_sqrt + eps))
+ * The caller computes the coefficients as torch/optim/adam.py does, in doubles, and rounds each once: w1 = 1 - beta1, c2 = 1 - beta2,
+ * bc2_sqrt = (1 - beta2^t)^0.5, neg_step_size = -lr / (1 - beta1^t).  lr == 0 goes through the same arithmetic. */
+#define FR_ADAM_MAX_ARRAYS 16
+typedef struct {
+	float* param; const float* grad; float* exp_avg; float* exp_avg_sq;   /* device, n floats each, 4-byte aligned */
+	int64_t n;
+	float w1, beta2, c2, bc2_sqrt, eps, neg_step_size;
+	int32_t fresh;    /* 1: first step of this array -- exp_avg / exp_avg_sq are NOT read (taken as zero), only written */
+} fr_adam_array;
+/* One launch for the whole table (HOST array of n_arrays <= FR_ADAM_MAX_ARRAYS entries, passed in the kernel arguments); no
+ * workspace, no atomics, no host read.  An array whose four pointers are 16-byte aligned moves as 16-byte words, any other as 4-byte
+ * words.  Nothing is launched when every n is 0.  FR_EINVAL for a null pointer with n > 0, n < 0, fresh outside 0 / 1, n_arrays outside
+ * 0 .. FR_ADAM_MAX_ARRAYS, or a param, exp_avg or exp_avg_sq range that overlaps any other range of the table (gradients, which are
+ * only read, may share memory with each other). */
+int fr_adam_step(const fr_adam_array* table, int32_t n_arrays, fr_stream_t stream);
 
 /* ---- simple-knn ---------------------------------------------------------------------------------- */
 
