@@ -946,3 +946,87 @@ def frame_ingest_emit(color, gt_depth, intrinsics, w2c, workspace, count, *, dow
                                                     means_ptr, rgb_ptr, _ptr(unnorm_rotations), _ptr(logit_opacities), _ptr(log_scales),
                                                     _ptr(mean3_sq_dist), _stream(dev)),
                    "fr_frame_ingest_emit")
+
+
+# ---- fused render-variable build (fr_rendervar_forward / fr_rendervar_backward) -------------------------------------------------------
+
+class RenderVarUnsupported(FisherRastError):
+    """the inputs are outside what the render-variable kernels take (not float32, not contiguous, not on one HIP device, log_scales not
+    1 or 3 wide): raised before anything is launched, so a caller may take the torch route for this call instead"""
+
+
+RENDERVAR_INPUTS = ("cam_unnorm_rots", "cam_trans", "first_frame_w2c", "means3D", "unnorm_rotations", "logit_opacities", "log_scales")
+_RENDERVAR_COLS = {"means3D": 3, "unnorm_rotations": 4, "logit_opacities": 1}
+
+
+def rendervar_check(tensors, time_idx, need_cuda=True):
+    """(P, scale_cols, n_frames) of the inputs in `tensors` (name -> tensor or None), or RenderVarUnsupported"""
+    present = {k: v for k, v in tensors.items() if v is not None}
+    dev = None
+    for k, v in present.items():
+        if v.dtype != torch.float32 or not v.is_contiguous():
+            raise RenderVarUnsupported(f"rendervar: {k} must be contiguous float32 (got {v.dtype}, contiguous={v.is_contiguous()})")
+        if need_cuda and not v.is_cuda:
+            raise RenderVarUnsupported(f"rendervar: {k} must live on a HIP device")
+        if dev is not None and v.device != dev:
+            raise RenderVarUnsupported(f"rendervar: {k} is on {v.device}, other inputs on {dev}")
+        dev = v.device
+    rows = {int(v.shape[0]) for k, v in present.items() if k in _RENDERVAR_COLS or k == "log_scales"}
+    for k, cols in _RENDERVAR_COLS.items():
+        if k in present and (present[k].dim() != 2 or int(present[k].shape[1]) != cols):
+            raise RenderVarUnsupported(f"rendervar: {k} must be [P,{cols}] (got {tuple(present[k].shape)})")
+    scale_cols = 3
+    if "log_scales" in present:
+        ls = present["log_scales"]
+        if ls.dim() != 2 or int(ls.shape[1]) not in (1, 3):
+            raise RenderVarUnsupported(f"rendervar: log_scales must be [P,1] or [P,3] (got {tuple(ls.shape)})")
+        scale_cols = int(ls.shape[1])
+    if len(rows) > 1:
+        raise RenderVarUnsupported(f"rendervar: the per-Gaussian inputs disagree on P ({sorted(rows)})")
+    n_frames = 1
+    if "cam_unnorm_rots" in present or "cam_trans" in present:
+        cr, ct = present.get("cam_unnorm_rots"), present.get("cam_trans")
+        if cr is None or ct is None or cr.dim() != 3 or ct.dim() != 3 or tuple(cr.shape[:2]) != (1, 4) or tuple(ct.shape[:2]) != (1, 3) or cr.shape[2] != ct.shape[2]:
+            raise RenderVarUnsupported("rendervar: the camera arrays must be [1,4,T] and [1,3,T]")
+        n_frames = int(cr.shape[2])
+        if not 0 <= int(time_idx) < n_frames:
+            raise RenderVarUnsupported(f"rendervar: time_idx {time_idx} is outside [0, {n_frames})")
+    if "first_frame_w2c" in present and tuple(present["first_frame_w2c"].shape) != (4, 4):
+        raise RenderVarUnsupported("rendervar: first_frame_w2c must be [4,4]")
+    return (rows.pop() if rows else 0), scale_cols, n_frames
+
+
+def rendervar_cfg(P, scale_cols, time_idx, n_frames, tensors):
+    """fr_rendervar_cfg over `tensors` (field name -> tensor or None; a missing field is a null pointer)"""
+    cfg = _lib.RenderVarCfg(int(P), int(scale_cols), int(time_idx), int(n_frames))
+    for name, t in tensors.items():
+        setattr(cfg, name, None if t is None else t.data_ptr())
+    return cfg
+
+
+def rendervar_forward(P, scale_cols, time_idx, n_frames, tensors):
+    """one fr_rendervar_forward call on the current stream of the tensors' device"""
+    dev = next(t for t in tensors.values() if t is not None).device
+    cfg = rendervar_cfg(P, scale_cols, time_idx, n_frames, tensors)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().fr_rendervar_forward(ctypes.byref(cfg), _stream(dev)), "fr_rendervar_forward")
+
+
+_rendervar_ws = {}
+
+
+def rendervar_backward(P, scale_cols, time_idx, n_frames, tensors):
+    """one fr_rendervar_backward call; the camera sums' workspace is kept per (device, stream) and only ever grown"""
+    dev = next(t for t in tensors.values() if t is not None).device
+    lib = _lib.load()
+    cfg = rendervar_cfg(P, scale_cols, time_idx, n_frames, tensors)
+    ws, nbytes = None, 0
+    if tensors.get("g_cam_unnorm_rots") is not None or tensors.get("g_cam_trans") is not None:
+        nbytes = int(lib.fr_rendervar_workspace_bytes(int(P)))
+        key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(dev).cuda_stream))
+        ws = _rendervar_ws.get(key)
+        if ws is None or ws.numel() * 4 < nbytes:
+            ws = _rendervar_ws[key] = torch.empty((max(nbytes // 4, 12 * 2048),), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.fr_rendervar_backward(ctypes.byref(cfg), None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, _stream(dev)),
+                   "fr_rendervar_backward")

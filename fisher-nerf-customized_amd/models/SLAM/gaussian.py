@@ -32,7 +32,7 @@ from fisher_rast.ops import FisherScorer
 from models.SLAM.utils.common_utils import checkpoint_time_idx, load_params_ckpt, save_params, save_params_ckpt
 from models.SLAM.utils.recon_helpers import setup_camera
 from models.SLAM.utils.slam_helpers import (transformed_params2rendervar, transformed_params2depthplussilhouette,
-                                            render_rgb_depth_sil)
+                                            render_rgb_depth_sil, frame_render_vars)
 from models.SLAM.utils.slam_external import update_seen_and_radius
 
 
@@ -53,7 +53,7 @@ def _loss_pixel_mask(depth_sil, gt_depth, sil_thres, reject_outliers, need_prese
     return rendered, keep.detach()
 
 
-def make_get_loss(transform_to_frame, calc_loss):
+def make_get_loss(transform_to_frame, calc_loss, fused_rendervar=False):
     """Drop-in for the module-level `get_loss` of the reference (models/SLAM/gaussian.py:184-297): same signature, same return
     `(loss, variables, weighted_losses)`.  What changes: the two rasteriser calls of 205-211 (RGB, then depth / silhouette /
     depth^2 on the same Gaussians) are ONE projection / binning / sort with two compositing passes and one fused backward
@@ -61,7 +61,11 @@ def make_get_loss(transform_to_frame, calc_loss):
     kernel pass (fr_densify_stats).  The loss terms are the reference's own `calc_loss` and the pose / point transform its own
     `transform_to_frame` (models/SLAM/utils/slam_helpers.py:23-44, 282-317), handed in by the caller; the pixel mask is
     `_loss_pixel_mask`.  The matplotlib dump of 240-284 is not reproduced (visualize_tracking_loss is accepted and ignored).
-    Opt-in: `FisherOps.install(cls, patch_get_loss=True)` puts it into the reference module."""
+    Opt-in: `FisherOps.install(cls, patch_get_loss=True)` puts it into the reference module.  With `fused_rendervar=True` the
+    stretch between `params` and the rasteriser -- transform_to_frame, the depth / silhouette features and the activations -- is one
+    launch forward and one backward, two with the camera's gradient (`frame_render_vars`, fr_rendervar_forward / _backward), instead
+    of the torch chain; a call whose parameters the kernels do not take (not float32, not contiguous, not on one HIP device) goes
+    the torch route, that call only."""
     @torch.enable_grad()
     def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_for_loss,
                  sil_thres, use_l1, ignore_outlier_depth_loss, tracking=False,
@@ -69,8 +73,18 @@ def make_get_loss(transform_to_frame, calc_loss):
         if not (tracking or mapping):
             raise ValueError("get_loss: one of tracking / mapping must be set")     # (the reference fails with a NameError here)
         # tracking: only the camera pose takes a gradient; mapping: only the Gaussians (gaussian.py:189-199)
-        pts = transform_to_frame(params, iter_time_idx, gaussians_grad=not tracking, camera_grad=bool(tracking))
-        im, radius, depth_sil, rendervar = render_rgb_depth_sil(params, curr_data['cam'], curr_data['w2c'], pts)
+        rendervar = feats = None
+        if fused_rendervar:
+            try:
+                rendervar, feats = frame_render_vars(params, iter_time_idx, curr_data['w2c'], gaussians_grad=not tracking, camera_grad=bool(tracking))
+            except _ops.RenderVarUnsupported:
+                pass
+        if rendervar is None:
+            pts = transform_to_frame(params, iter_time_idx, gaussians_grad=not tracking, camera_grad=bool(tracking))
+            im, radius, depth_sil, rendervar = render_rgb_depth_sil(params, curr_data['cam'], curr_data['w2c'], pts)
+        else:
+            im, radius, depth_sil, rendervar = render_rgb_depth_sil(params, curr_data['cam'], curr_data['w2c'], rendervar['means3D'],
+                                                                    rendervar=rendervar, feats=feats)
         variables['means2D'] = rendervar['means2D']      # densification reads the colour render's screen-space gradient (gaussian.py:207)
         depth, mask = _loss_pixel_mask(depth_sil, curr_data['depth'], sil_thres, ignore_outlier_depth_loss, tracking and use_sil_for_loss)
         terms = calc_loss(curr_data, im, depth, mask, mask.repeat(3, 1, 1), use_l1, use_sil_for_loss, ignore_outlier_depth_loss, tracking)
@@ -426,12 +440,13 @@ class FisherOps:
         return scorer.run(self._as_w2c(w2cs), H_inv=H_inv_per_view, H_inv_per_view=True)["scores"]
 
     @classmethod
-    def install(cls, target_cls, patch_get_loss=False, fused_loss=False):
+    def install(cls, target_cls, patch_get_loss=False, fused_loss=False, fused_rendervar=False):
         """Graft the accelerated methods onto the reference's class.  `patch_get_loss=True` also replaces the
         module-level `get_loss` of the module `target_cls` lives in by the fused-render form (`make_get_loss`); off by default --
         a caller that only wants the Fisher scorer keeps the reference's training step untouched.  With `fused_loss=True` as well,
         that get_loss takes its loss terms from this package's `calc_loss` (`calc_loss_mask` where the module has one: the object
-        class) -- the fused L1 + SSIM kernels, no host synchronisation -- instead of the reference module's own; off by default."""
+        class) -- the fused L1 + SSIM kernels, no host synchronisation -- instead of the reference module's own; off by default.  With `fused_rendervar=True`
+        as well, it builds the render variables with the fused kernels (`make_get_loss(..., fused_rendervar=True)`); off by default."""
         for name in ("_device", "_as_w2c", "_stack_poses", "_scorer", "_scorer_key", "_keyframe_key", "_same_keyframes", "_PARAM_KEYS", "compute_Hessian", "compute_H_train",
                      "pose_eval", "path_scores"):
             setattr(target_cls, name, getattr(cls, name))
@@ -444,7 +459,8 @@ class FisherOps:
             if fused_loss:
                 from models.SLAM.utils import slam_helpers as _sh
                 loss_fn = _sh.calc_loss_mask if hasattr(mod, "calc_loss_mask") else _sh.calc_loss
-            mod.get_loss = make_get_loss(mod.transform_to_frame, loss_fn)
+            # the keyword only when it is set: a make_get_loss wrapped by a caller with the two-argument signature keeps working
+            mod.get_loss = make_get_loss(mod.transform_to_frame, loss_fn, **(dict(fused_rendervar=True) if fused_rendervar else {}))
         if not hasattr(target_cls, "FISHER_COLUMNS"):
             target_cls.FISHER_COLUMNS = cls.FISHER_COLUMNS
         target_cls.H_TRAIN_REG = cls.H_TRAIN_REG

@@ -1,9 +1,11 @@
-"""Render-variable builders on the hot path (models/SLAM/utils/slam_helpers.py:178-188, 235-252, 268-279) and the loss terms of the
-training step (slam_helpers.py:5-6, 23-77) on the fused image-loss kernels (fisher_rast/image_loss.py)."""
+"""Render-variable builders on the hot path (models/SLAM/utils/slam_helpers.py:178-188, 235-252, 268-279), their fused form on the
+render-variable kernels (fisher_rast/rendervar.py: frame_render_vars, transform_to_frame) and the loss terms of the training step
+(slam_helpers.py:5-6, 23-77) on the fused image-loss kernels (fisher_rast/image_loss.py)."""
 import torch
 import torch.nn.functional as F
 
 from fisher_rast import image_loss as _il
+from fisher_rast import rendervar as _rv
 
 
 def _scales3(params):
@@ -40,16 +42,45 @@ def transformed_params2depthplussilhouette(params, w2c, transformed_pts):
     }
 
 
-def render_rgb_depth_sil(params, cam, w2c, transformed_pts, renderer_cls=None):
+def frame_render_vars(params, time_idx, w2c, gaussians_grad, camera_grad):
+    """transform_to_frame (slam_helpers.py:282-317), transformed_params2rendervar and get_depth_and_silhouette in one launch
+    (`FrameRenderVars`): (rendervar, feats), `rendervar` with the keys of transformed_params2rendervar ('means2D' the torch leaf it
+    is there) and `feats` the (z, 1, z^2) features of the depth / silhouette render under the first frame's `w2c`.  Raises
+    `RenderVarUnsupported` on inputs the kernels do not take (not float32, not contiguous, not on one HIP device, log_scales not 1 or 3
+    wide)."""
+    pts, feats, rotations, opacities, scales = _rv.FrameRenderVars.apply(
+        params['means3D'], params['unnorm_rotations'], params['logit_opacities'], params['log_scales'],
+        params['cam_unnorm_rots'], params['cam_trans'], time_idx, w2c, gaussians_grad, camera_grad)
+    rendervar = {
+        'means3D': pts,
+        'colors_precomp': params['rgb_colors'],
+        'rotations': rotations,
+        'opacities': opacities,
+        'scales': scales,
+        'means2D': torch.zeros_like(params['means3D'], requires_grad=True) + 0,
+    }
+    return rendervar, feats
+
+
+def transform_to_frame(params, time_idx, gaussians_grad, camera_grad):
+    """Drop-in for the reference's transform_to_frame (slam_helpers.py:282-317) on the same kernel, with only the points asked for."""
+    return _rv.FrameRenderVars.apply(params['means3D'], None, None, None, params['cam_unnorm_rots'], params['cam_trans'], time_idx, None,
+                                     gaussians_grad, camera_grad)[0]
+
+
+def render_rgb_depth_sil(params, cam, w2c, transformed_pts, renderer_cls=None, rendervar=None, feats=None):
     """The two renders of the reference's get_loss (models/SLAM/gaussian.py:199-211) -- RGB, then (depth, silhouette, depth^2)
     on the same Gaussians -- as one call on one projection / binning / sort (`GaussianRasterizer.forward_pair`).
     Returns (im [3,H,W], radius [P], depth_sil [3,H,W], rendervar); `rendervar['means2D']` keeps the colour render's
-    screen-space gradient, the statistic the densifier accumulates (gaussian.py:207)."""
+    screen-space gradient, the statistic the densifier accumulates (gaussian.py:207).  `rendervar` / `feats` prebuilt
+    (`frame_render_vars`) are taken as they are instead of being built here."""
     if renderer_cls is None:
         from diff_gaussian_rasterization import GaussianRasterizer as renderer_cls
-    rendervar = transformed_params2rendervar(params, transformed_pts)
+    if rendervar is None:
+        rendervar = transformed_params2rendervar(params, transformed_pts)
     rendervar['means2D'].retain_grad()
-    feats = get_depth_and_silhouette(transformed_pts, w2c)
+    if feats is None:
+        feats = get_depth_and_silhouette(transformed_pts, w2c)
     im, radius, _, depth_sil = renderer_cls(raster_settings=cam).forward_pair(
         rendervar['means3D'], rendervar['means2D'], rendervar['opacities'], rendervar['colors_precomp'], feats,
         scales=rendervar['scales'], rotations=rendervar['rotations'])

@@ -45,6 +45,8 @@
  *                           children of densify, models/SLAM/utils/slam_external.py:218-262, 411-463 over 25-42
  *   fr_adam_step         <- optimizer.step() of the torch.optim.Adam that get_optimizer builds (seven groups of one tensor),
  *                           models/SLAM/gaussian.py:1458-1469, models/SLAM/gaussian_object.py:1815-1826
+ *   fr_rendervar_forward / fr_rendervar_backward <- transform_to_frame, get_depth_and_silhouette, transformed_params2rendervar and
+ *                           their autograd, models/SLAM/utils/slam_helpers.py:178-188, 235-252, 268-317 over slam_external.py:25-42
  *   fr_knn_dist2         <- simple_knn._C.distCUDA2 (thirdparty/simple-knn, un-vendored submodule)
  *
  * The pybind module `_C` of the reference (RAST/ext.cpp:14-18) is re-created in Python on top of
@@ -553,6 +555,54 @@ typedef struct {
  * 0 .. FR_ADAM_MAX_ARRAYS, or a param, exp_avg or exp_avg_sq range that overlaps any other range of the table (gradients, which are
  * only read, may share memory with each other). */
 int fr_adam_step(const fr_adam_array* table, int32_t n_arrays, fr_stream_t stream);
+
+/* ---- fused render-variable build: frame transform and activations ---------------------------------------------------------
+ * Everything between `params` and the rasteriser of a tracking / mapping iteration, one launch forward and one backward (two with a
+ * camera gradient), in binary32 and in the operand order of csrc/fr_rendervar_math.h:
+ *   q = normalize(normalize(cq)),  R = build_rotation(q),  pts = R m + ct,  zc = w2c[2,:3] . pts + w2c[2,3],  feats = (zc, 1, zc^2),
+ *   rotations = q_g / max(|q_g|, 1e-12),  opacities = 1 / (1 + exp(-logit)),  scales = exp(log_scales) (one column broadcast to three)
+ * All pointers are device pointers, 4-byte aligned (rows of 12 bytes: nothing more is assumed).  The camera arrays are the
+ * reference's [1,4,T] / [1,3,T] tensors themselves: element c of frame time_idx is base[c * n_frames + time_idx].
+ * Every output and every incoming gradient is nullable: a null output is a part that is not computed, a null incoming gradient is
+ * not read and counts as zero (an output gradient that depends on it alone is then written as zeros). */
+typedef struct {
+	int32_t P, scale_cols;                 /* scale_cols: 1 (isotropic, broadcast to three) or 3 */
+	int32_t time_idx, n_frames;
+	const float* cam_unnorm_rots;          /* [4, n_frames] */
+	const float* cam_trans;                /* [3, n_frames] */
+	const float* first_frame_w2c;          /* [4,4] row-major; needed for feats / g_feats only */
+	const float* means3D;                  /* [P,3] */
+	const float* unnorm_rotations;         /* [P,4] */
+	const float* logit_opacities;          /* [P,1] */
+	const float* log_scales;               /* [P,scale_cols] */
+	/* forward outputs */
+	float* pts;                            /* [P,3] */
+	float* feats;                          /* [P,3] */
+	float* rotations;                      /* [P,4] */
+	float* opacities;                      /* [P,1] */
+	float* scales;                         /* [P,3] */
+	float* rel_w2c;                        /* [4,4] row-major: the frame's pose as a matrix */
+	/* backward: incoming gradients of the five outputs */
+	const float* g_pts; const float* g_feats; const float* g_rotations; const float* g_opacities; const float* g_scales;
+	/* backward outputs */
+	float* g_means3D;                      /* [P,3] */
+	float* g_unnorm_rotations;             /* [P,4] */
+	float* g_logit_opacities;              /* [P,1] */
+	float* g_log_scales;                   /* [P,scale_cols] */
+	float* g_cam_unnorm_rots;              /* [4, n_frames]: written whole, zero outside time_idx */
+	float* g_cam_trans;                    /* [3, n_frames]: written whole, zero outside time_idx */
+} fr_rendervar_cfg;
+/* bytes of the backward's workspace when a camera gradient is asked for: one row of twelve partial sums per workgroup */
+size_t fr_rendervar_workspace_bytes(int32_t P);
+/* One launch.  Reads the inputs an asked-for output needs (FR_EINVAL when one of them is null), writes the non-null outputs. */
+int fr_rendervar_forward(const fr_rendervar_cfg* cfg, fr_stream_t stream);
+/* One launch for the non-null per-Gaussian gradients; with g_cam_unnorm_rots or g_cam_trans set, the same launch leaves one row of
+ * partial sums per workgroup in the workspace (plain stores, no atomics) and a second, one-workgroup launch adds the rows in a fixed
+ * order and runs the pose's way back: the same bits on every call.  The workspace is the caller's (needed only with a camera
+ * gradient); nothing is allocated, read back or synchronised.  P == 0 launches nothing: the camera gradients are set to zero.
+ * FR_EINVAL for P < 0, scale_cols not 1 or 3, time_idx outside [0, n_frames), a null input that an asked-for gradient needs; FR_ENOSPACE for a workspace
+ * that is too small. */
+int fr_rendervar_backward(const fr_rendervar_cfg* cfg, void* workspace, size_t workspace_bytes, fr_stream_t stream);
 
 /* ---- simple-knn ---------------------------------------------------------------------------------- */
 
