@@ -174,6 +174,16 @@ class RenderVarCfg(ctypes.Structure):
                    "g_means3D", "g_unnorm_rotations", "g_logit_opacities", "g_log_scales", "g_cam_unnorm_rots", "g_cam_trans")]
 
 
+FR_KEYFRAME_STATUS_WORDS = 4
+FR_KEYFRAME_MAX_POINTS = 4096
+
+
+class KeyframeCfg(ctypes.Structure):
+    """fr_keyframe_cfg (include/fisher_rast.h)"""
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("n", ctypes.c_int32), ("K", ctypes.c_int32), ("edge", ctypes.c_int32),
+                ("n_valid_idx", ctypes.c_int32), ("intrinsics", _f32p), ("w2c", _f32p)]
+
+
 # every symbol include/fisher_rast.h and include/fisher_occ.h declare
 EXPORTS = (
     "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
@@ -186,6 +196,7 @@ EXPORTS = (
     "fr_frame_ingest_workspace_bytes", "fr_frame_ingest_select", "fr_frame_ingest_emit",
     "fr_map_edit_workspace_bytes", "fr_map_edit_plan", "fr_map_edit_apply", "fr_map_edit_split_children", "fr_adam_step",
     "fr_rendervar_workspace_bytes", "fr_rendervar_forward", "fr_rendervar_backward",
+    "fr_keyframe_valid_pixels_workspace_bytes", "fr_keyframe_overlap_workspace_bytes", "fr_keyframe_valid_pixels", "fr_keyframe_overlap",
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
@@ -195,8 +206,8 @@ _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_math.h",
-                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_math.h",
+                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -366,6 +377,18 @@ def load():
         lib.fr_rendervar_forward.argtypes = [ctypes.POINTER(RenderVarCfg), ctypes.c_void_p]
         lib.fr_rendervar_backward.restype = ctypes.c_int
         lib.fr_rendervar_backward.argtypes = [ctypes.POINTER(RenderVarCfg), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    if hasattr(lib, "fr_keyframe_overlap"):
+        lib.fr_keyframe_valid_pixels_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_keyframe_valid_pixels_workspace_bytes.argtypes = [ctypes.c_int32] * 2
+        lib.fr_keyframe_overlap_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_keyframe_overlap_workspace_bytes.argtypes = [ctypes.c_int32]
+        lib.fr_keyframe_valid_pixels.restype = ctypes.c_int
+        lib.fr_keyframe_valid_pixels.argtypes = [ctypes.c_int32, ctypes.c_int32, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_keyframe_overlap.restype = ctypes.c_int
+        lib.fr_keyframe_overlap.argtypes = [ctypes.POINTER(KeyframeCfg), _f32p, ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                            ctypes.c_void_p]
     lib.fr_densify_stats.restype = ctypes.c_int
     lib.fr_densify_stats.argtypes = [ctypes.c_int32, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]
     lib.fr_densify_masks.restype = ctypes.c_int

@@ -12,6 +12,8 @@ Four groups of entry points:
     path evaluation updated in the same pass (tester_gaussians_navigation.py:2147-2178).
   * `frame_ingest_select` / `frame_ingest_emit` -- which cells of an RGB-D frame become new Gaussians, and their parameter rows
     (models/SLAM/gaussian.py:320-414, 75-143, 299-318).
+  * `keyframe_valid_pixels` / `keyframe_overlap` -- the pixels of a frame with a measured depth, and how many of the points drawn from
+    them each keyframe sees (models/SLAM/utils/keyframe_selection.py:10-37, 40-134).
 """
 import ctypes
 from typing import Optional
@@ -19,7 +21,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import FisherRastError, RasterCfg, Gaussians, FisherCfg, FrameIngestCfg
+from ._lib import FisherRastError, RasterCfg, Gaussians, FisherCfg, FrameIngestCfg, KeyframeCfg
 
 
 def _need_gpu(t: torch.Tensor, name: str):
@@ -946,6 +948,107 @@ def frame_ingest_emit(color, gt_depth, intrinsics, w2c, workspace, count, *, dow
                                                     means_ptr, rgb_ptr, _ptr(unnorm_rotations), _ptr(logit_opacities), _ptr(log_scales),
                                                     _ptr(mean3_sq_dist), _stream(dev)),
                    "fr_frame_ingest_emit")
+
+
+# ---- keyframe overlap (fr_keyframe_valid_pixels / fr_keyframe_overlap) ----------------------------------------------------------------
+
+_keyframe_ws = {}
+
+
+def _keyframe_workspace(kind, shape, dev, nbytes):
+    """the workspace of one of the two keyframe calls, kept per device and shape: calls on one stream follow each other"""
+    key = (kind, dev, shape)
+    ws = _keyframe_ws.get(key)
+    if ws is None:
+        if nbytes == 0:
+            raise FisherRastError(f"keyframe overlap: bad size {shape}")
+        ws = _keyframe_ws[key] = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+    return ws
+
+
+def _host_i64_to(values, dev):
+    """int64 values (a host tensor or a list) on `dev` without a host synchronisation: staged in pinned memory (see _small_f32);
+    a tensor already on the device is used where it is"""
+    t = values if isinstance(values, torch.Tensor) else torch.tensor(values, dtype=torch.int64)
+    if t.dtype != torch.int64:
+        t = t.long()
+    if t.device == dev:
+        return t.contiguous()
+    if t.is_cuda:
+        return t.to(dev).contiguous()
+    return t.contiguous().pin_memory().to(dev, non_blocking=True)
+
+
+def _depth_hw(depth):
+    _need_gpu(depth, "depth")
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    if depth.dtype != torch.float32 or not depth.is_contiguous() or depth.numel() != H * W:
+        raise FisherRastError(f"keyframe overlap: depth must be a contiguous float32 [H,W] or [1,H,W] tensor, got {depth.dtype} {tuple(depth.shape)}")
+    return H, W
+
+
+def keyframe_valid_pixels(depth, mask=None, *, idx=None, status=None):
+    """fr_keyframe_valid_pixels: (idx, status) -- idx int32 [H W] on the device, whose first status[0] entries are the ascending flat
+    indices of depth > 0 (and mask != 0 where a mask of H W elements is given): the rows of torch.where in order.  status int32
+    [FR_KEYFRAME_STATUS_WORDS] = {count, 0, 0, 0}; reading it is the caller's host synchronisation, there is none in here."""
+    H, W = _depth_hw(depth)
+    dev = depth.device
+    m = None if mask is None else _mask_bytes_hw(mask, H, W, "mask")
+    lib = _lib.load()
+    ws = _keyframe_workspace("pixels", (H, W), dev, int(lib.fr_keyframe_valid_pixels_workspace_bytes(H, W)))
+    if idx is None:
+        idx = torch.empty((H * W,), dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty((_lib.FR_KEYFRAME_STATUS_WORDS,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.fr_keyframe_valid_pixels(H, W, _ptr(depth), _ptr(m), _ptr(idx), _ptr(status), _ptr(ws),
+                                                ws.numel() * ws.element_size(), _stream(dev)), "fr_keyframe_valid_pixels")
+    return idx, status
+
+
+def keyframe_overlap(depth, intrinsics, w2c, draws, kf_w2c, *, valid_idx=None, n_valid_idx=None, kf_masks=None, edge=20,
+                     want_valid=True, want_pts=False):
+    """fr_keyframe_overlap: dict(counts int32 [K], status int32 [4] = {valid points, out-of-range draws, 0, 0}, valid uint8 [n] or
+    None, pts float32 [n,3] or None), all on the device of `depth`.  draws: int64 [n] (host or device) into valid_idx -- the list
+    `keyframe_valid_pixels` wrote, with n_valid_idx its count as the host read it -- or, without valid_idx, flat pixel indices.
+    kf_w2c: [K,4,4] float32 on the device (K may be 0).  kf_masks: None, or one entry per keyframe, each None or a [H,W] mask on the
+    device (bool / uint8; anything else is compared with 0).  intrinsics [3,3] and w2c [4,4] may live anywhere.  No host read and no
+    host synchronisation in here; the number of launches does not depend on K."""
+    H, W = _depth_hw(depth)
+    dev = depth.device
+    d = _host_i64_to(draws, dev).reshape(-1)
+    n = int(d.numel())
+    kf = kf_w2c if isinstance(kf_w2c, torch.Tensor) else torch.as_tensor(kf_w2c, dtype=torch.float32)
+    K = int(kf.shape[0]) if kf.dim() == 3 else (0 if kf.numel() == 0 else -1)
+    if K < 0 or (K > 0 and tuple(kf.shape[1:]) != (4, 4)):
+        raise FisherRastError(f"keyframe overlap: kf_w2c must be [K,4,4], got {tuple(kf.shape)}")
+    kf = _prep(kf, dev)
+    Kmat, pose = _small_f32(intrinsics, dev, 3, 3, "intrinsics"), _small_f32(w2c, dev, 4, 4, "w2c")
+    if valid_idx is not None:
+        if valid_idx.device != dev or valid_idx.dtype != torch.int32 or not valid_idx.is_contiguous():
+            raise FisherRastError("keyframe overlap: valid_idx must be a contiguous int32 tensor on the device of depth")
+        n_valid_idx = int(valid_idx.numel() if n_valid_idx is None else n_valid_idx)
+        if not 0 <= n_valid_idx <= valid_idx.numel():
+            raise FisherRastError(f"keyframe overlap: n_valid_idx {n_valid_idx} outside valid_idx of {valid_idx.numel()}")
+    keep, table = [], None
+    if kf_masks is not None and any(m is not None for m in kf_masks):
+        if len(kf_masks) != K:
+            raise FisherRastError(f"keyframe overlap: {len(kf_masks)} masks for {K} keyframes")
+        keep = [None if m is None else _mask_bytes_hw(m if m.device == dev else m.to(dev), H, W, "keyframe mask") for m in kf_masks]
+        table = _host_i64_to([0 if m is None else m.data_ptr() for m in keep], dev)
+    lib = _lib.load()
+    ws = _keyframe_workspace("overlap", (n,), dev, int(lib.fr_keyframe_overlap_workspace_bytes(n)))
+    counts = torch.empty((K,), dtype=torch.int32, device=dev)
+    status = torch.empty((_lib.FR_KEYFRAME_STATUS_WORDS,), dtype=torch.int32, device=dev)
+    valid = torch.empty((n,), dtype=torch.uint8, device=dev) if want_valid else None
+    pts = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_pts else None
+    cfg = KeyframeCfg(H, W, n, K, int(edge), int(n_valid_idx or 0), Kmat.data_ptr(), pose.data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(lib.fr_keyframe_overlap(ctypes.byref(cfg), _ptr(depth), _ptr(valid_idx), _ptr(d), _ptr(kf), _ptr(table),
+                                           _ptr(counts) if K else None, _ptr(valid), _ptr(pts), _ptr(status), _ptr(ws),
+                                           ws.numel() * ws.element_size(), _stream(dev)), "fr_keyframe_overlap")
+    del keep                                                   # alive until the launches were issued; the stream orders the rest
+    return dict(counts=counts, status=status, valid=valid, pts=pts)
 
 
 # ---- fused render-variable build (fr_rendervar_forward / fr_rendervar_backward) -------------------------------------------------------

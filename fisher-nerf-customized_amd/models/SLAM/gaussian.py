@@ -10,7 +10,8 @@ In scope (same names, arguments and return conventions as the reference):
     get_pointcloud / initialize_params / initialize_new_params / add_new_gaussians (75-182, 299-414: module-level functions; the
         frame ingest, FrameIngestOps)
     prune_gaussians / densify / remove_points (models/SLAM/utils/slam_external.py 235-262, 345-463: the map edit, MapEditOps)
-The SLAM loop itself (init, track_rgbd, keyframe selection, the optimizer step ...) is NOT rebuilt: it is reference
+    keyframe_selection_overlap (models/SLAM/utils/keyframe_selection.py 40-134: the mapping window, KeyframeSelectOps)
+The SLAM loop itself (init, track_rgbd ...) is NOT rebuilt: it is reference
 Python that stays as it is.  `FisherOps.install(cls)` grafts the accelerated methods onto the reference class
 so that tester_gaussians_navigation.py keeps calling `slam.pose_eval(...)` unchanged; `GaussianSLAM` below is
 the same operator surface as a standalone object built from a parameter dict (a `params{t}.npz` checkpoint
@@ -607,6 +608,25 @@ class MapEditOps:
         mod.prune_gaussians = edit.prune_gaussians
         mod.densify = edit.densify
         mod.remove_points = edit.remove_points
+        return target_cls
+
+
+class KeyframeSelectOps:
+    """The keyframe selection of the mapping loop (fr_keyframe_valid_pixels / fr_keyframe_overlap, include/fisher_rast.h) for the
+    reference's modules: `install(target_cls)` replaces the module-level name `keyframe_selection_overlap` of the module `target_cls`
+    lives in (models/SLAM/gaussian.py and models/SLAM/gaussian_object.py import it by name, and their `track_rgbd` looks it up there
+    every `map_every` frames), and nothing on the class itself.  Opt-in: nothing is installed by default."""
+
+    NAME = "keyframe_selection_overlap"
+
+    @classmethod
+    def install(cls, target_cls):
+        import sys
+        from models.SLAM.utils.keyframe_selection import keyframe_selection_overlap
+        mod = sys.modules.get(target_cls.__module__)
+        if mod is None or not hasattr(mod, cls.NAME):
+            raise ValueError(f"KeyframeSelectOps.install: the module of {target_cls.__name__} does not define {cls.NAME}")
+        setattr(mod, cls.NAME, keyframe_selection_overlap)
         return target_cls
 
 

@@ -45,6 +45,8 @@
  *                           children of densify, models/SLAM/utils/slam_external.py:218-262, 411-463 over 25-42
  *   fr_adam_step         <- optimizer.step() of the torch.optim.Adam that get_optimizer builds (seven groups of one tensor),
  *                           models/SLAM/gaussian.py:1458-1469, models/SLAM/gaussian_object.py:1815-1826
+ *   fr_keyframe_valid_pixels / fr_keyframe_overlap <- the device work of keyframe_selection_overlap / get_pointcloud,
+ *                           models/SLAM/utils/keyframe_selection.py:40-134, 10-37
  *   fr_rendervar_forward / fr_rendervar_backward <- transform_to_frame, get_depth_and_silhouette, transformed_params2rendervar and
  *                           their autograd, models/SLAM/utils/slam_helpers.py:178-188, 235-252, 268-317 over slam_external.py:25-42
  *   fr_knn_dist2         <- simple_knn._C.distCUDA2 (thirdparty/simple-knn, un-vendored submodule)
@@ -603,6 +605,50 @@ int fr_rendervar_forward(const fr_rendervar_cfg* cfg, fr_stream_t stream);
  * FR_EINVAL for P < 0, scale_cols not 1 or 3, time_idx outside [0, n_frames), a null input that an asked-for gradient needs; FR_ENOSPACE for a workspace
  * that is too small. */
 int fr_rendervar_backward(const fr_rendervar_cfg* cfg, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+
+/* ---- keyframe overlap: which keyframes see the current frame -----------------------------------------------------------
+ * In place of the device work of keyframe_selection_overlap / get_pointcloud (models/SLAM/utils/keyframe_selection.py:10-37, 40-134):
+ * the list of pixels with a measured depth, then -- for n of them the caller drew -- their world points, which of those the
+ * reference's duplicate filter keeps, and how many of the kept ones each of K keyframes sees.  Two calls, with the one host read of
+ * the pixel count between them (the draw needs it); arithmetic in csrc/fr_keyframe_math.h.  Nothing allocated, no host read inside,
+ * integer sums only (the same call gives the same numbers whatever the launch geometry).
+ *   key(c)  = |nearbyint(c * 1e4) / 1e4| per coordinate;  a point is INVALID when its three keys equal those of any other drawn
+ *             point or (0,0,0): both copies of a pixel drawn twice go, and so do mirror images (x,y,z) / (-x,y,z) -- the reference's
+ *             unique() / isin() filter, kept as it is.
+ *   inside  = (u < W - edge) & (u > edge) & (v < H - edge) & (v > edge) & (z > 0), with (u, v) = p2.xy / z, z = p2.z + 1e-5,
+ *             p2 = K (est_w2c p), and, where a keyframe has a mask, mask[clamp(nearbyint(v))][clamp(nearbyint(u))] != 0. */
+#define FR_KEYFRAME_STATUS_WORDS 4
+#define FR_KEYFRAME_MAX_POINTS 4096      /* the most points one overlap call takes (the reference draws 1600) */
+typedef struct {
+	int32_t H, W;                     /* the frame; H W at most 2^30 */
+	int32_t n;                        /* drawn points, 1 .. FR_KEYFRAME_MAX_POINTS */
+	int32_t K;                        /* keyframes, 0 or more */
+	int32_t edge;                     /* margin in pixels, 0 or more (the reference uses 20) */
+	int32_t n_valid_idx;              /* entries of valid_idx (the first call's count as the host read it); ignored without valid_idx */
+	const float* intrinsics;          /* device [3,3] row-major */
+	const float* w2c;                 /* device [4,4] row-major: the current frame */
+} fr_keyframe_cfg;
+
+/* Host-only queries (0 for a bad argument). */
+size_t fr_keyframe_valid_pixels_workspace_bytes(int32_t H, int32_t W);
+size_t fr_keyframe_overlap_workspace_bytes(int32_t n);
+/* idx_out [H W] int32: the ascending flat indices of depth > 0 (& mask != 0 where mask, bytes [H,W], is not null) -- the row-major
+ * order torch.where gives; status: FR_KEYFRAME_STATUS_WORDS device int32 = {count, 0, 0, 0}.  Three launches: per-workgroup counts by
+ * ballot / popcount, a one-workgroup scan, a scatter; workgroups never wait for each other.  workspace: 8-byte aligned; FR_EINVAL
+ * when it is short, as for a null pointer, a bad size or a misaligned depth / idx_out / status. */
+int fr_keyframe_valid_pixels(int32_t H, int32_t W, const float* depth, const uint8_t* mask, int32_t* idx_out, int32_t* status,
+                             void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* Point i is the back-projection of pixel valid_idx[draws[i]] (valid_idx null: of pixel draws[i]) of depth [H,W] through the inverse
+ * of cfg->w2c.  draws: int64 [n].  kf_w2c: [K,16] row-major est_w2c of the keyframes.  kf_mask_table: device uint64 [K] of addresses of
+ * byte masks [H,W] (0: that keyframe has none), or null: no keyframe has one.  out_counts [K] int32: valid & inside points per
+ * keyframe.  out_valid [n] bytes and out_pts [n,3] (every drawn point, kept or not; zeros for an out-of-range draw) may be null.
+ * status = {valid points, out-of-range draws, 0, 0}: a draw outside [0, n_valid_idx) (or [0, H W) without valid_idx) or a valid_idx
+ * entry outside [0, H W) makes its point invalid and is counted; nothing is read through it.  K == 0 writes status, out_valid and
+ * out_pts only.  FR_EINVAL for a null required pointer, sizes outside the limits above, a float pointer not 4-byte or an int64 /
+ * table pointer not 8-byte aligned, and a short workspace (fr_keyframe_overlap_workspace_bytes, 8-byte aligned). */
+int fr_keyframe_overlap(const fr_keyframe_cfg* cfg, const float* depth, const int32_t* valid_idx, const int64_t* draws,
+                        const float* kf_w2c, const uint64_t* kf_mask_table, int32_t* out_counts, uint8_t* out_valid, float* out_pts,
+                        int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream);
 
 /* ---- simple-knn ---------------------------------------------------------------------------------- */
 
