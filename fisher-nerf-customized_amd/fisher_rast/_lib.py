@@ -184,6 +184,11 @@ class KeyframeCfg(ctypes.Structure):
                 ("n_valid_idx", ctypes.c_int32), ("intrinsics", _f32p), ("w2c", _f32p)]
 
 
+FR_PLAN_STATUS_WORDS = 4
+FR_PLAN_TILE = 64
+FR_PLAN_UNREACHED = 0xFFFFFFFFFFFFFFFF
+
+
 # every symbol include/fisher_rast.h and include/fisher_occ.h declare
 EXPORTS = (
     "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
@@ -200,14 +205,15 @@ EXPORTS = (
     "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
+    "fr_plan_workspace_bytes", "fr_plan_round_cap", "fr_plan_grid", "fr_plan_tiers", "fr_plan_field", "fr_plan_paths",
 )
 
 _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_math.h",
-                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_math.h",
+                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -432,6 +438,22 @@ def load():
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.fr_occ_cells_of.restype = ctypes.c_int
     lib.fr_occ_cells_of.argtypes = [occp, _f32p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    if hasattr(lib, "fr_plan_field"):
+        lib.fr_plan_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_plan_workspace_bytes.argtypes = [occp]
+        lib.fr_plan_round_cap.restype = ctypes.c_int32
+        lib.fr_plan_round_cap.argtypes = [occp]
+        lib.fr_plan_grid.restype = ctypes.c_int
+        lib.fr_plan_grid.argtypes = [occp, _f32p, _f32p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_plan_tiers.restype = ctypes.c_int
+        lib.fr_plan_tiers.argtypes = [occp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.fr_plan_field.restype = ctypes.c_int
+        lib.fr_plan_field.argtypes = [occp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.POINTER(ctypes.c_int32 * 2), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_plan_paths.restype = ctypes.c_int
+        lib.fr_plan_paths.argtypes = [occp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                      ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     _lib = lib
     return lib
 

@@ -4,8 +4,9 @@ In scope (same names, arguments and return conventions as the reference):
     init (66-103)                      update_occ_map (202-301)        build_connected_freespace (401-447)
     build_frontiers (540-683)          generate_candidate (1406-1430)  generate_candidate_object (1432-1469)
     the free-space filter of the candidate loop (1383-1401)            sample_random_candidate (782-837)
-The A* search, path shortcutting, visualisation and the VLM frontier selection are NOT rebuilt: they are reference
-Python that stays as it is.  `OccupancyOps.install(cls)` grafts the accelerated methods onto the reference class;
+    setup_start + planning (449-538, 1591-1777): `PathPlanOps`, one cost field from the start, paths to all goals
+Visualisation, the RRT planner and the VLM frontier selection are NOT rebuilt: they are reference Python that stays as it
+is.  `OccupancyOps.install(cls)` / `PathPlanOps.install(cls)` graft the accelerated methods onto the reference class;
 `AstarPlanner` below is the same operator surface as a standalone object for tests and benchmarks.
 
 What changes underneath: the reference bins the depth samples with torch ops and then walks every occupied cell in a
@@ -33,7 +34,15 @@ class OccupancyOps:
 
     # -- internals -----------------------------------------------------------------------------------------------
     def _occ_cfg(self):
-        mc = self.map_center.detach().cpu().numpy() if isinstance(self.map_center, torch.Tensor) else np.asarray(self.map_center)
+        mc = self.map_center
+        if isinstance(mc, torch.Tensor):
+            # the host copy is kept until the tensor is replaced or written: one device read, not one per call
+            held = getattr(self, "_occ_mc_held", None)
+            if held is None or held[0] is not mc or held[1] != mc._version:
+                held = self._occ_mc_held = (mc, mc._version, mc.detach().cpu().numpy())
+            mc = held[2]
+        else:
+            mc = np.asarray(mc)
         return _lib.OccCfg(int(self.grid_dim[0]), int(self.grid_dim[1]), float(self.cell_size), float(np.float32(mc[0])),
                            float(np.float32(mc[1])), float(self.height_lower), float(self.height_upper), float(self.pcd_far_distance))
 
@@ -285,7 +294,154 @@ class OccupancyOps:
         return planner_cls
 
 
-class AstarPlanner(OccupancyOps):
+class PathPlanOps:
+    """Mixin with the action-planning stage: `setup_start` + `planning` (astar.py:449-538, 1591-1777) and the batched `plan_paths`.
+
+    The reference searches best-first on the host, once per goal.  Here `setup_start` builds ONE cost field from the start on the
+    device (fisher_occ.h: fr_plan_grid, fr_occ_freespace, fr_plan_tiers, fr_plan_field) and every goal's path is read off it
+    (fr_plan_paths): the minimum of the reference's own cost, distance + collision, with no expansion cap -- never above what the
+    reference's search pays for the same cell.  Needs OccupancyOps' internals and the attributes
+    occ_map, cam_height, grid_dim; `shortcut_path` defaults to True.  The reference's `planning_direction` array is not maintained
+    (`plan_field()` gives cost and parent), and no PNG is written."""
+
+    PLAN_MAX_LEN = 1024            # path points per goal of the first fr_plan_paths call; a longer path repeats the call
+
+    @staticmethod
+    def _localization_error(cls):
+        """the LocalizationError of the module that defines `cls` (defined there when the module has none)"""
+        import sys
+        mod = sys.modules.get(cls.__module__)
+        err = getattr(mod, "LocalizationError", None)
+        if err is None:
+            err = type("LocalizationError", (Exception,), {"__module__": cls.__module__})
+            if mod is not None:
+                mod.LocalizationError = err
+        return err
+
+    def _plan_cell(self, cell):
+        return int(cell[0]), int(cell[1])
+
+    # -- astar.py:449-538 --------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def setup_start(self, start, gaussian_points=None, frame_idx=0):
+        """ Setup the start point for the planner: the planning grid, the free space, and the cost field from `start` = (row, col).
+            This function should be called before the planning """
+        lib = _lib.load()
+        dev = self.occ_map.device
+        cfg = self._occ_cfg()
+        gh, gw = int(self.grid_dim[1]), int(self.grid_dim[0])
+        need = lib.fr_plan_workspace_bytes(ctypes.byref(cfg))
+        ws = getattr(self, "_plan_ws", None)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+            self._plan_ws = ws
+        sy, sx = self._plan_cell(start)
+        pts, n = None, 0
+        if gaussian_points is not None:
+            pts_t = gaussian_points.detach().to(dev).float().contiguous()
+            pts, n = pts_t.data_ptr(), int(pts_t.shape[0])
+        occ_plan = torch.empty((gh, gw), dtype=torch.uint8, device=dev)
+        tiers = torch.empty((gh, gw), dtype=torch.uint8, device=dev)
+        field = torch.empty((gh, gw), dtype=torch.int64, device=dev)
+        status = torch.empty((_lib.FR_PLAN_STATUS_WORDS,), dtype=torch.int32, device=dev)
+        _lib.check(lib.fr_plan_grid(ctypes.byref(cfg), self.occ_map.data_ptr(), pts, n, float(self.cam_height), sy, sx, occ_plan.data_ptr(),
+                                    status.data_ptr(), ws.data_ptr(), need, self._stream()), "fr_plan_grid")
+        free = self.build_connected_freespace(gaussian_points, as_tensor=True)
+        _lib.check(lib.fr_plan_tiers(ctypes.byref(cfg), free.data_ptr(), tiers.data_ptr(), self._stream()), "fr_plan_tiers")
+        counts = (ctypes.c_int32 * 2)()
+        _lib.check(lib.fr_plan_field(ctypes.byref(cfg), tiers.data_ptr(), sy, sx, field.data_ptr(), status.data_ptr(), ctypes.byref(counts),
+                                     ws.data_ptr(), need, self._stream()), "fr_plan_field")
+        self.start = start
+        self._plan = dict(cfg=cfg, start=(sy, sx), occ_plan=occ_plan, free=free, tiers=tiers, field=field)
+        self._plan_np = {}
+        st = self._plan_read(status)                               # the one host read of the step beyond the convergence checks
+        self.plan_stats = dict(ring=int(st[0]), gaussians_binned=int(st[1]), start_in_free_space=bool(st[2]), rounds=int(st[3]),
+                               rounds_launched=int(counts[0]), convergence_reads=int(counts[1]))
+        if st[0] >= 8:
+            raise self._localization_error(type(self))("The start point is not in free space")
+
+    @staticmethod
+    def _plan_read(t):
+        """every device-to-host copy of the stage goes through here"""
+        return t.cpu().numpy()
+
+    @property
+    def occ_map_np(self):
+        """the planning grid (uint8 [H, W]), copied down on first access"""
+        if "occ" not in self._plan_np:
+            self._plan_np["occ"] = self._plan_read(self._plan["occ_plan"])
+        return self._plan_np["occ"]
+
+    @occ_map_np.setter
+    def occ_map_np(self, value):
+        self.__dict__.setdefault("_plan_np", {})["occ"] = value
+
+    @property
+    def free_space_np(self):
+        if "free" not in self._plan_np:
+            self._plan_np["free"] = self._plan_read(self._plan["free"])
+        return self._plan_np["free"]
+
+    @free_space_np.setter
+    def free_space_np(self, value):
+        self.__dict__.setdefault("_plan_np", {})["free"] = value
+
+    # -- astar.py:1591-1777 ------------------------------------------------------------------------------------------
+    def plan_paths(self, goals):
+        """[G, 2] goals (row, col) -> a list of G paths, each an (M, 2) int array in x-z order or np.array([]): one kernel call and
+        one host read (a path longer than PLAN_MAX_LEN points repeats both once with room for any path)."""
+        lib = _lib.load()
+        plan = self._plan
+        dev = plan["field"].device
+        g = torch.as_tensor(np.asarray(goals, dtype=np.int64).reshape(-1, 2)).to(torch.int32)
+        G = int(g.shape[0])
+        if G == 0:
+            return []
+        g = g.to(dev).contiguous()
+        shortcut = 1 if getattr(self, "shortcut_path", True) else 0
+        max_len = int(self.PLAN_MAX_LEN)
+        while True:
+            out = torch.empty((G * (2 * max_len + 1),), dtype=torch.int32, device=dev)       # the lengths, then the paths: one copy down
+            lengths, paths = out[:G], out[G:]
+            _lib.check(lib.fr_plan_paths(ctypes.byref(plan["cfg"]), plan["field"].data_ptr(), plan["occ_plan"].data_ptr(), plan["start"][0],
+                                         plan["start"][1], g.data_ptr(), G, shortcut, paths.data_ptr(), max_len, lengths.data_ptr(),
+                                         self._stream()), "fr_plan_paths")
+            host = self._plan_read(out)
+            lens, pts = host[:G], host[G:].reshape(G, max_len, 2)
+            if (lens >= 0).all():
+                break
+            max_len = int(self.grid_dim[0]) * int(self.grid_dim[1]) + 1
+        return [pts[k, :lens[k]].astype(np.int64) if lens[k] > 0 else np.array([]) for k in range(G)]
+
+    def planning(self, goal):
+        """ the path to one goal (row, col): (M, 2) int array in x-z order, or np.array([]) """
+        return self.plan_paths([self._plan_cell(goal)])[0]
+
+    def plan_field(self):
+        """(cost float32 [H, W], -1 where the start does not reach; parent int32 [H, W, 2] = (row, col), -1 there)"""
+        words = self._plan_read(self._plan["field"]).view(np.uint64)
+        reached = words != np.uint64(_lib.FR_PLAN_UNREACHED)
+        cost = np.where(reached, (words >> np.uint64(32)).astype(np.uint32).view(np.float32), np.float32(-1))
+        idx = (words & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        gw = int(self.grid_dim[0])
+        parent = np.where(reached[..., None], np.stack([idx // gw, idx % gw], axis=-1), -1).astype(np.int32)
+        return cost, parent
+
+    @classmethod
+    def install(cls, planner_cls):
+        """Graft the planning stage onto the reference's AstarPlanner class (after OccupancyOps.install, whose internals it uses)."""
+        for name in ("setup_start", "planning", "plan_paths", "plan_field", "_plan_cell", "_plan_read", "_localization_error", "occ_map_np",
+                     "free_space_np", "PLAN_MAX_LEN"):
+            setattr(planner_cls, name, cls.__dict__[name])
+        cls._localization_error(planner_cls)
+        return planner_cls
+
+
+class LocalizationError(Exception):
+    """raised by setup_start when all 8 neighbours of the start are occupied in the dilated map (astar.py:481-482)"""
+
+
+class AstarPlanner(OccupancyOps, PathPlanOps):
     """Standalone object with the reference constructor's configuration keys (astar.py:23-60)."""
 
     def __init__(self, slam_config=None, eval_dir=None, device=torch.device("cuda:0"), **kw):
@@ -306,3 +462,4 @@ class AstarPlanner(OccupancyOps):
         self.eval_dir = eval_dir
         self.cam_pos = None
         self.frame_idx = 0
+        self.shortcut_path = kw.get("shortcut_path", ex.get("shortcut_path", True))

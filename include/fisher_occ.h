@@ -93,6 +93,48 @@ int fr_occ_free_candidates(const fr_occ_cfg* cfg, const uint8_t* eroded_free, fl
                            float* c2w, int32_t max_out, int32_t* counts, void* workspace, size_t workspace_bytes,
                            fr_stream_t stream);
 
+/* ---- path planning: one cost field from the start, paths to all goals ------------------------------------------------------
+ * Replaces AstarPlanner.setup_start + planning (planning/astar.py:449-538, 1591-1777): the reference runs a best-first search
+ * per goal on the host; these calls build the single-source shortest-path field of the same cost model (csrc/fr_plan_math.h)
+ * on the device and read every goal's path off it.  Cells are (row, col); a cell's raster index is row * grid_w + col.
+ *
+ *   fr_plan_grid    occ_plan uint8 [grid_h][grid_w] = the reference's occ_map_np: arg-max label == 1, plus the cells holding more
+ *                   than 50 of the Gaussians `points` [n_points][3] (or null) with cam_height - 1 <= y <= cam_height (cells by the
+ *                   rule of fr_occ_cells_of; Gaussians outside the grid are ignored), dilated 3 x 3, the start cleared.
+ *                   status int32 [FR_PLAN_STATUS_WORDS] (device) = {occupied cells among the start's 8 neighbours in the dilated
+ *                   map, Gaussians binned, 0, 0}; fr_plan_field then sets words 2 and 3.
+ *   fr_plan_tiers   tiers uint8 [grid_h][grid_w] from free_space (fr_occ_freespace's output): 0 where not free, else
+ *                   1 | tier << 1, tier = 3, 2, 1, 0 for an L1 distance to the nearest non-free cell of <= 5, <= 10, <= 20, more.
+ *   fr_plan_field   field uint64 [grid_h][grid_w]: (bits of the binary32 cost) << 32 | raster index of the parent, all ones where
+ *                   the start does not reach.  status[2] = 1 when the start is in free space, status[3] = the number of rounds
+ *                   that changed something.  The call launches rounds over FR_PLAN_TILE-square tiles and READS ONE DEVICE WORD
+ *                   every few rounds (it synchronises the stream); past fr_plan_round_cap() rounds it returns FR_ENOSPACE.
+ *                   host_counts: HOST int32 [2] or null = {rounds launched, convergence reads}.
+ *   fr_plan_paths   goals int32 [n_goals][2] = (row, col).  paths int32 [n_goals][max_len][2] = (x, z) = (col, row) from the start
+ *                   to the end cell; lengths int32 [n_goals]: 0 = no path (goal occupied in occ_plan or outside the grid, nothing
+ *                   reached within Chebyshev distance 1 of it, or the end cell is the start), -1 = the path as walked, before
+ *                   any shortcut, is longer than max_len (repeat with a larger one; grid_w * grid_h + 1 always suffices).  shortcut != 0 runs the reference's shortcut loop,
+ *                   a segment being clear when no occupied cell's centre lies within 3.5 cells of it.
+ * Workspace: fr_plan_workspace_bytes(), 16-byte aligned, shared by fr_plan_grid and fr_plan_field (not kept between calls). */
+#define FR_PLAN_STATUS_WORDS 4
+#define FR_PLAN_TILE 64
+
+size_t fr_plan_workspace_bytes(const fr_occ_cfg* cfg);
+int32_t fr_plan_round_cap(const fr_occ_cfg* cfg);
+
+int fr_plan_grid(const fr_occ_cfg* cfg, const float* occ_map, const float* points, int32_t n_points, float cam_height,
+                 int32_t start_row, int32_t start_col, uint8_t* occ_plan, int32_t* status,
+                 void* workspace, size_t workspace_bytes, fr_stream_t stream);
+
+int fr_plan_tiers(const fr_occ_cfg* cfg, const uint8_t* free_space, uint8_t* tiers, fr_stream_t stream);
+
+int fr_plan_field(const fr_occ_cfg* cfg, const uint8_t* tiers, int32_t start_row, int32_t start_col, uint64_t* field,
+                  int32_t* status, int32_t* host_counts, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+
+int fr_plan_paths(const fr_occ_cfg* cfg, const uint64_t* field, const uint8_t* occ_plan, int32_t start_row, int32_t start_col,
+                  const int32_t* goals, int32_t n_goals, int32_t shortcut, int32_t* paths, int32_t max_len, int32_t* lengths,
+                  fr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
