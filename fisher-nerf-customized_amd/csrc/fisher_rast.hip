@@ -44,6 +44,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "fr_math.h"
+#include "fr_sortnet.h"
 #include "../../include/fisher_rast.h"
 #include "fr_internal.h"
 
@@ -1645,7 +1646,25 @@ __device__ __forceinline__ void fr_take_rows(uint64_t& key, bool keepmin)
 	key = ((b < a) == keepmin) ? b : a;
 }
 
-template <int K> struct FrLog2 { static constexpr int value = K == 1 ? 0 : K == 2 ? 1 : K == 4 ? 2 : K == 8 ? 3 : 4; };
+// K need not be a power of two (fr_sortnet.h has the plan and the argument): the exchanges between lanes and between waves act per
+// register and only need the two halves of a block to be equally long, which they are for any K down to one lane; what they leave
+// inside a lane -- K unsorted keys at the start, a bitonic sequence of K keys after every merge level -- is finished by a fixed
+// comparator list (FrSnSort<K>, FrSnClean<K>).  A run of n keys is held with K = ceil(n / 64) keys per lane instead of the next
+// power of two: a part of 280 keys sorts 320 positions, not 512.
+// For such K the stage numbers below count LANES: FrLog2<K> = 0, stage S merges blocks of 2^(S-1) lanes, stride T is 2^T lanes,
+// and the in-lane lists stand where the power-of-two forms have their in-lane stages.
+template <int K> struct FrLog2 { static constexpr int value = K == 2 ? 1 : K == 4 ? 2 : K == 8 ? 3 : K == 16 ? 4 : 0; };
+// comparator list L (fr_sortnet.h) on a lane's registers; every register index is a constant
+template <class L, int K, int I = 0>
+__device__ __forceinline__ void fr_lane_net(uint64_t (&key)[K])
+{
+	if constexpr (I < L::N)
+	{
+		constexpr FrSnCmp c = L::at(I);
+		fr_cx(key[c.a], key[c.b]);
+		fr_lane_net<L, K, I + 1>(key);
+	}
+}
 // key <-> the key of lane ^ 2^M
 template <int M>
 __device__ __forceinline__ void fr_take_lane_xor(uint64_t& key, bool keepmin)
@@ -1697,6 +1716,8 @@ __device__ __forceinline__ void fr_wave_flip(uint64_t (&key)[K], int lane)
 				fr_take(key[r], fr_lane_mirror<M>(hi, lane), keepmin);
 				fr_take(key[K - 1 - r], fr_lane_mirror<M>(lo, lane), keepmin);
 			}
+			// odd K: the middle register pairs with itself in the mirror lane
+			if constexpr ((K & 1) != 0) fr_take(key[K / 2], fr_lane_mirror<M>(key[K / 2], lane), keepmin);
 		}
 	}
 }
@@ -1722,20 +1743,35 @@ __device__ __forceinline__ void fr_wave_xor_down(uint64_t (&key)[K], int lane)
 		}
 		fr_wave_xor_down<K, T - 1>(key, lane);
 	}
+	else if constexpr (!fr_sn_pow2(K)) fr_lane_net<FrSnClean<K>>(key);     // below the lane strides: the lane's bitonic K keys
 }
-// stages 2 .. min(n_pad, 2^S) of the network on the wave's own run
+// stages 2 .. min(n_pad, 2^S) of the network on the wave's own run.  K no power of two: levels 0 .. S of fr_sortnet.h's plan, and
+// `n_pad` is n itself (fr_sort_limit), since a level is needed or not by n against K 2^(S-1)
 template <int K, int S>
 __device__ __forceinline__ void fr_wave_stages(uint64_t (&key)[K], uint32_t n_pad, int lane)
 {
 	if constexpr (S >= 1)
 	{
 		fr_wave_stages<K, S - 1>(key, n_pad, lane);
-		if ((1u << S) <= n_pad)
+		bool need;
+		if constexpr (fr_sn_pow2(K)) need = (1u << S) <= n_pad;
+		else need = fr_sn_wave_level(K, S, n_pad);
+		if (need)
 		{
 			fr_wave_flip<K, S>(key, lane);
 			fr_wave_xor_down<K, S - 2>(key, lane);
 		}
 	}
+	else if constexpr (!fr_sn_pow2(K)) fr_lane_net<FrSnSort<K>>(key);
+}
+// what fr_wave_stages / fr_wg_stages decide by: n rounded up to a power of two, or n itself when K is none
+template <int K>
+__device__ __forceinline__ uint32_t fr_sort_limit(uint32_t n)
+{
+	if constexpr (!fr_sn_pow2(K)) return n;
+	uint32_t n_pad = 1;
+	while (n_pad < n) n_pad <<= 1;
+	return n_pad;
 }
 
 // One wave, n <= 64 K keys of a segment in global memory.
@@ -1745,8 +1781,7 @@ __device__ __forceinline__ void fr_sort_wave_segment(uint64_t* __restrict__ gk, 
 	uint64_t key[K];
 #pragma unroll
 	for (int r = 0; r < K; r++) { const uint32_t i = (uint32_t)(lane * K + r); key[r] = i < n ? gk[i] : ~0ull; }
-	uint32_t n_pad = 1;
-	while (n_pad < n) n_pad <<= 1;
+	const uint32_t n_pad = fr_sort_limit<K>(n);
 	fr_wave_stages<K, 6 + FrLog2<K>::value>(key, n_pad, lane);
 #pragma unroll
 	for (int r = 0; r < K; r++) { const uint32_t i = (uint32_t)(lane * K + r); if (i < n) gk[i] = key[r]; }
@@ -1778,7 +1813,10 @@ __device__ __forceinline__ void fr_wg_stages(uint64_t (&key)[K], uint64_t* sk, u
 	{
 		fr_wg_stages<K, NW, SW - 1>(key, sk, n_pad, w, lane);
 		constexpr int RUN = 64 * K, kw = 1 << SW;
-		if (((uint32_t)RUN << SW) <= n_pad)            // uniform over the workgroup
+		bool need;                                     // uniform over the workgroup
+		if constexpr (fr_sn_pow2(K)) need = ((uint32_t)RUN << SW) <= n_pad;
+		else need = fr_sn_wg_level(K, SW, n_pad);      // (n_pad is n: fr_sort_limit)
+		if (need)
 		{
 			// flip across the runs: element (w, r, l) <-> (w ^ (kw - 1), K - 1 - r, 63 - l)
 			const uint32_t base = (uint32_t)(w * RUN);
@@ -1808,16 +1846,44 @@ __device__ __forceinline__ void fr_sort_wg_segment(uint64_t* sk, uint64_t* __res
 	uint64_t key[K];
 #pragma unroll
 	for (int r = 0; r < K; r++) { const uint32_t i = base + (uint32_t)(lane * K + r); key[r] = i < n ? gk[i] : ~0ull; }
-	uint32_t n_pad = 1;
-	while (n_pad < n) n_pad <<= 1;
+	const uint32_t n_pad = fr_sort_limit<K>(n);
 	fr_wave_stages<K, 6 + FrLog2<K>::value>(key, n_pad, lane);
 	fr_wg_stages<K, NW, (NW == 4 ? 2 : 4)>(key, sk, n_pad, w, lane);
 #pragma unroll
 	for (int r = 0; r < K; r++) { const uint32_t i = base + (uint32_t)(lane * K + r); if (i < n) gk[i] = key[r]; }
 }
 
+// One wave, 2 .. 512 keys: the fewest keys per lane that hold them (fr_sn_wave_k: 1 .. 8).  (wave-uniform n)
+__device__ __forceinline__ void fr_sort_wave_any(uint64_t* __restrict__ gk, uint32_t n, int lane)
+{
+	switch (fr_sn_wave_k(n))
+	{
+	case 1: if constexpr (fr_sn_has(FR_SN_WAVE_KS, 1)) fr_sort_wave_segment<1>(gk, n, lane); break;
+	case 2: if constexpr (fr_sn_has(FR_SN_WAVE_KS, 2)) fr_sort_wave_segment<2>(gk, n, lane); break;
+	case 3: if constexpr (fr_sn_has(FR_SN_WAVE_KS, 3)) fr_sort_wave_segment<3>(gk, n, lane); break;
+	case 4: if constexpr (fr_sn_has(FR_SN_WAVE_KS, 4)) fr_sort_wave_segment<4>(gk, n, lane); break;
+	case 5: if constexpr (fr_sn_has(FR_SN_WAVE_KS, 5)) fr_sort_wave_segment<5>(gk, n, lane); break;
+	case 6: if constexpr (fr_sn_has(FR_SN_WAVE_KS, 6)) fr_sort_wave_segment<6>(gk, n, lane); break;
+	case 7: if constexpr (fr_sn_has(FR_SN_WAVE_KS, 7)) fr_sort_wave_segment<7>(gk, n, lane); break;
+	default: fr_sort_wave_segment<8>(gk, n, lane); break;
+	}
+}
+// Four waves, 513 .. 2048 keys: 256 K keys, K = 3 .. 8 (fr_sn_wg4_k).  (workgroup-uniform n; sk = FR_SORT_SMALL_KEYS keys of LDS)
+__device__ __forceinline__ void fr_sort_wg4_any(uint64_t* sk, uint64_t* __restrict__ gk, uint32_t n, int tid)
+{
+	switch (fr_sn_wg4_k(n))
+	{
+	case 3: if constexpr (fr_sn_has(FR_SN_WG4_KS, 3)) fr_sort_wg_segment<3, 4>(sk, gk, n, tid); break;
+	case 4: if constexpr (fr_sn_has(FR_SN_WG4_KS, 4)) fr_sort_wg_segment<4, 4>(sk, gk, n, tid); break;
+	case 5: if constexpr (fr_sn_has(FR_SN_WG4_KS, 5)) fr_sort_wg_segment<5, 4>(sk, gk, n, tid); break;
+	case 6: if constexpr (fr_sn_has(FR_SN_WG4_KS, 6)) fr_sort_wg_segment<6, 4>(sk, gk, n, tid); break;
+	case 7: if constexpr (fr_sn_has(FR_SN_WG4_KS, 7)) fr_sort_wg_segment<7, 4>(sk, gk, n, tid); break;
+	default: fr_sort_wg_segment<8, 4>(sk, gk, n, tid); break;
+	}
+}
+
 // Segments of up to FR_SORT_SMALL_KEYS keys: one workgroup per (tile, view).  Up to 512 keys the first wave sorts alone
-// (no barrier at all; the other three leave at once), beyond that the four waves hold 256 K keys, K = 4 or 8.
+// (no barrier at all; the other three leave at once), beyond that the four waves hold 256 K keys, K = 3 .. 8.
 // `first`: the workgroups in front of the T*V of the tile map (k_sort_split).
 __device__ __forceinline__ void fr_sort_short_list(const FrParams& p, uint64_t* skeys, uint32_t first)
 {
@@ -1841,15 +1907,11 @@ __device__ __forceinline__ void fr_sort_short_list(const FrParams& p, uint64_t* 
 	if (n <= 512u)
 	{
 		if (tid >= 64) return;
-		if (n <= 64u) fr_sort_wave_segment<1>(gk, n, tid);
-		else if (n <= 128u) fr_sort_wave_segment<2>(gk, n, tid);
-		else if (n <= 256u) fr_sort_wave_segment<4>(gk, n, tid);
-		else fr_sort_wave_segment<8>(gk, n, tid);
+		fr_sort_wave_any(gk, n, tid);
 		return;
 	}
 	// (one wave with 16 keys per lane for 513 .. 1024 keys: measured slower, 0.107 against 0.097 ms)
-	if (n <= 1024u) fr_sort_wg_segment<4, 4>(skeys, gk, n, tid);
-	else fr_sort_wg_segment<8, 4>(skeys, gk, n, tid);
+	fr_sort_wg4_any(skeys, gk, n, tid);
 }
 
 __global__ __launch_bounds__(FR_THREADS) void k_sort_tiles(FrParams p)
@@ -1989,6 +2051,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_sort_split(FrParams p, uint32_t 
 			const uint32_t c = s_cnt[q];
 			if (c <= 512u) continue;
 			uint64_t* pk = tmp + s_off[q];
+			// (the power-of-two runs only: K = 3, 5, 6, 7 here as well cost the kernel 73 VGPRs and its seventh wave, and these parts are rare)
 			if (c <= 1024u) fr_sort_wg_segment<4, 4>(skeys, pk, c, tid);
 			else if (c <= (uint32_t)FR_SORT_SMALL_KEYS) fr_sort_wg_segment<8, 4>(skeys, pk, c, tid);
 			else fr_bitonic(pk, c, tid, FR_THREADS);
@@ -2009,10 +2072,10 @@ __global__ __launch_bounds__(FR_THREADS) void k_sort_parts(FrParams p)
 		const uint2 d = parts[i];
 		uint64_t* pk = p.keys + (uint32_t)__builtin_amdgcn_readfirstlane((int)d.x);
 		const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.y);
-		if (c <= 64u) fr_sort_wave_segment<1>(pk, c, lane);
-		else if (c <= 128u) fr_sort_wave_segment<2>(pk, c, lane);
-		else if (c <= 256u) fr_sort_wave_segment<4>(pk, c, lane);
-		else fr_sort_wave_segment<8>(pk, c, lane);
+		// (the lane as this trip's own value: the key offsets lane K + r of every K are otherwise kept in registers across the loop)
+		int ln = lane;
+		asm volatile("" : "+v"(ln));
+		fr_sort_wave_any(pk, c, ln);
 	}
 }
 
