@@ -79,6 +79,7 @@ def workspace_layout(P, W, H, max_rendered):
 
 
 # high-water mark of tile instances per device, so that the binning buffer is normally large enough first time
+# (host integers only, no device memory: shared by every stream and thread -- a stale or lost update costs one re-run of a forward)
 _capacity_hint = {}
 
 
@@ -279,6 +280,11 @@ class FisherScorer:
     workspace.  `run()` scores / accumulates any number of views with no host synchronisation; the caller
     synchronises when it reads the results.  Overflow of the tile-instance buffer is detected from the
     device status word when results are fetched (`fetch`), and the batch is re-run with a larger buffer.
+
+    One scorer, one stream at a time: every call runs on the torch stream that is current when it is made, and the workspaces
+    (`_ws`, one per kind of launch) and the packed static records in them are shared by the calls that follow each other -- they
+    are NOT keyed by stream.  Calls made on different streams must be ordered by the caller (an event, `wait_stream`) exactly as
+    two writers of one tensor would be; callers that want to score on two streams side by side build a scorer per stream.
     """
 
     WORKSPACE_BUDGET = 32 << 30  # bytes of workspace (of the MI355X's 288 GB) before views are processed in chunks: ~580 views at 500k Gaussians
@@ -756,9 +762,9 @@ def knn_dist2(points: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     pts = _prep(points, dev)
     P = int(pts.shape[0]) if pts is not None else 0
-    out = torch.zeros((P,), dtype=torch.float32, device=dev)
     if P == 0:
-        return out
+        return torch.zeros((0,), dtype=torch.float32, device=dev)
+    out = torch.empty((P,), dtype=torch.float32, device=dev)          # k_knn_search writes every element: no fill kernel in front of it
     nbytes = int(lib.fr_knn_workspace_bytes(P))
     ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
@@ -956,8 +962,9 @@ _keyframe_ws = {}
 
 
 def _keyframe_workspace(kind, shape, dev, nbytes):
-    """the workspace of one of the two keyframe calls, kept per device and shape: calls on one stream follow each other"""
-    key = (kind, dev, shape)
+    """the workspace of one of the two keyframe calls, kept per (device, stream) and shape, as `_backward_scratch` is: calls on one
+    stream follow each other, calls on two streams may run side by side and get a workspace each"""
+    key = (kind, dev, int(torch.cuda.current_stream(dev).cuda_stream), shape)
     ws = _keyframe_ws.get(key)
     if ws is None:
         if nbytes == 0:

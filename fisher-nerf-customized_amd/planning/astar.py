@@ -30,7 +30,11 @@ _METHODS = {"largest": 0, "combined": 1, "closest": 2}
 
 class OccupancyOps:
     """Mixin with the accelerated occupancy / frontier methods.  Needs the attributes AstarPlanner.__init__ sets:
-    device, cell_size, height_lower, height_upper, pcd_far_distance, frontier_select_method, K, radius, min_range."""
+    device, cell_size, height_lower, height_upper, pcd_far_distance, frontier_select_method, K, radius, min_range.
+
+    One planner, one stream at a time: every method runs on the torch stream that is current when it is called, and the resident
+    map and the workspaces (`_occ_ws`, `_occ_cells`, `_plan_ws`, `_free_space_dev`) belong to the object, not to a stream.  Calls
+    made on different streams must be ordered by the caller, as two writers of `occ_map` would be."""
 
     # -- internals -----------------------------------------------------------------------------------------------
     def _occ_cfg(self):
