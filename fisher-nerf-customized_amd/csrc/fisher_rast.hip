@@ -9085,8 +9085,15 @@ static int fr_morton_sort(int P, const float* points, uint64_t* keys, uint32_t* 
 	if ((rc = fr_check_launch("k_knn_minmax"))) return rc;
 	hipLaunchKernelGGL(k_knn_morton, dim3(nblk), dim3(FR_THREADS), 0, s, P, points, mm, keys);
 	if ((rc = fr_check_launch("k_knn_morton"))) return rc;
-	// bitonic network over the whole array
-	const uint32_t n = (uint32_t)P;
+	return fr_sort_keys64(keys, (uint32_t)P, s);
+}
+
+// ascending sort of n 64-bit keys in place: the bitonic network over the whole array (declared in fr_internal.h: fr_cloud.hip sorts with it too)
+int fr_sort_keys64(uint64_t* keys, uint32_t n, fr_stream_t stream)
+{
+	int rc;
+	hipStream_t s = (hipStream_t)stream;
+	if (n == 0) return FR_OK;
 	uint32_t n_pad = 1;
 	while (n_pad < n) n_pad <<= 1;
 	const uint32_t nchunks = (n + FR_KNN_CHUNK - 1) / FR_KNN_CHUNK;

@@ -184,6 +184,18 @@ class KeyframeCfg(ctypes.Structure):
                 ("n_valid_idx", ctypes.c_int32), ("intrinsics", _f32p), ("w2c", _f32p)]
 
 
+FR_CLOUD_MAX_POINTS = 1 << 27
+FR_CLOUD_STATS_WORDS = 4
+FR_CLOUD_SOURCE_POINTS, FR_CLOUD_SOURCE_DEPTH = 0, 1
+
+
+class CloudQueryCfg(ctypes.Structure):
+    """fr_cloud_query_cfg (include/fisher_rast.h)"""
+    _fields_ = [("source", ctypes.c_int32), ("M", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("flip_z", ctypes.c_int32), ("dist_th", ctypes.c_float)] + \
+               [(n, ctypes.c_void_p) for n in ("queries", "depth", "kinv", "c2w", "out_dist", "out_idx", "out_flag", "out_stats")]
+
+
 FR_PLAN_STATUS_WORDS = 4
 FR_PLAN_TILE = 64
 FR_PLAN_UNREACHED = 0xFFFFFFFFFFFFFFFF
@@ -206,14 +218,15 @@ EXPORTS = (
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
     "fr_plan_workspace_bytes", "fr_plan_round_cap", "fr_plan_grid", "fr_plan_tiers", "fr_plan_field", "fr_plan_paths",
+    "fr_cloud_index_bytes", "fr_cloud_index_workspace_bytes", "fr_cloud_query_workspace_bytes", "fr_cloud_index_build", "fr_cloud_query",
 )
 
 _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_math.h",
-                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_cloud.hip", "fr_math.h",
+                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_cloud_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -454,6 +467,15 @@ def load():
         lib.fr_plan_paths.restype = ctypes.c_int
         lib.fr_plan_paths.argtypes = [occp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                       ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    if hasattr(lib, "fr_cloud_query"):
+        for f in (lib.fr_cloud_index_bytes, lib.fr_cloud_index_workspace_bytes, lib.fr_cloud_query_workspace_bytes):
+            f.restype = ctypes.c_size_t
+            f.argtypes = [ctypes.c_int32]
+        lib.fr_cloud_index_build.restype = ctypes.c_int
+        lib.fr_cloud_index_build.argtypes = [ctypes.c_int32, _f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_cloud_query.restype = ctypes.c_int
+        lib.fr_cloud_query.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.POINTER(CloudQueryCfg), ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.c_void_p]
     _lib = lib
     return lib
 
