@@ -196,6 +196,10 @@ class CloudQueryCfg(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("queries", "depth", "kinv", "c2w", "out_dist", "out_idx", "out_flag", "out_stats")]
 
 
+FR_CLUSTER_MAX_POINTS = 1 << 26
+FR_DBSCAN_STATUS_WORDS = 8
+FR_TARGET_STATUS_WORDS = 16
+
 FR_PLAN_STATUS_WORDS = 4
 FR_PLAN_TILE = 64
 FR_PLAN_UNREACHED = 0xFFFFFFFFFFFFFFFF
@@ -219,14 +223,15 @@ EXPORTS = (
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
     "fr_plan_workspace_bytes", "fr_plan_round_cap", "fr_plan_grid", "fr_plan_tiers", "fr_plan_field", "fr_plan_paths",
     "fr_cloud_index_bytes", "fr_cloud_index_workspace_bytes", "fr_cloud_query_workspace_bytes", "fr_cloud_index_build", "fr_cloud_query",
+    "fr_dbscan_workspace_bytes", "fr_target_select_workspace_bytes", "fr_dbscan", "fr_target_select",
 )
 
 _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_cloud.hip", "fr_math.h",
-                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_cloud_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_math.h",
+                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -476,6 +481,16 @@ def load():
         lib.fr_cloud_query.restype = ctypes.c_int
         lib.fr_cloud_query.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.POINTER(CloudQueryCfg), ctypes.c_void_p, ctypes.c_size_t,
                                        ctypes.c_void_p]
+    if hasattr(lib, "fr_target_select"):
+        for f in (lib.fr_dbscan_workspace_bytes, lib.fr_target_select_workspace_bytes):
+            f.restype = ctypes.c_size_t
+            f.argtypes = [ctypes.c_int32]
+        lib.fr_dbscan.restype = ctypes.c_int
+        lib.fr_dbscan.argtypes = [ctypes.c_int32, _f32p, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_target_select.restype = ctypes.c_int
+        lib.fr_target_select.argtypes = [ctypes.c_int32, _f32p, _f32p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_int32] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
     _lib = lib
     return lib
 

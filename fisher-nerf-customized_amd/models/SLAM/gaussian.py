@@ -6,6 +6,8 @@ In scope (same names, arguments and return conventions as the reference):
     render_at_pose (555-579)      gs_pts_cnt (1350-1352)        gaussian_points / cur_frame_idx (1590-1598)
     render_at_poses (new: render_at_pose for a batch of poses in one call, RenderOps)
     pose_eval_points (new: the candidate scan of global_planning, 1285-1316 -- per-Gaussian scores and their running maximum, PointScoreOps)
+    select_target_points / global_planning (1176-1336: the target selection -- height band, quantile, DBSCAN, best cluster -- and the
+        planning round assembled on the library, TargetSelectOps; opt-in, not on GaussianSLAM by default)
     pause / resume / color_refinement / stop (1600-1614)
     get_pointcloud / initialize_params / initialize_new_params / add_new_gaussians (75-182, 299-414: module-level functions; the
         frame ingest, FrameIngestOps)
@@ -34,7 +36,7 @@ from models.SLAM.utils.common_utils import checkpoint_time_idx, load_params_ckpt
 from models.SLAM.utils.recon_helpers import setup_camera
 from models.SLAM.utils.slam_helpers import (transformed_params2rendervar, transformed_params2depthplussilhouette,
                                             render_rgb_depth_sil, frame_render_vars)
-from models.SLAM.utils.slam_external import update_seen_and_radius
+from models.SLAM.utils.slam_external import update_seen_and_radius, remove_points  # noqa: F401  (remove_points: looked up in this module by global_planning)
 
 
 def _loss_pixel_mask(depth_sil, gt_depth, sil_thres, reject_outliers, need_presence):
@@ -548,6 +550,126 @@ class PointScoreOps:
     def install(cls, target_cls):
         """Graft the method onto the reference's class (after FisherOps.install / ObjectFisherOps.install)."""
         for name in ("pose_eval_points",):
+            setattr(target_cls, name, getattr(cls, name))
+        return target_cls
+
+
+class TargetSelectOps:
+    """Mixin with the target selection of the reference's `global_planning` (fr_target_select, include/fisher_rast.h) and the
+    planning round assembled around it: `install(target_cls)` adds `select_target_points` -- models/SLAM/gaussian.py:1218-1276, the
+    same lines at gaussian_object.py:1419-1479 -- and replaces `global_planning` (1176-1336) by one that runs every stage on the
+    library: `compute_H_train`, `select_target_points`, one `pose_eval_points` over the poses that survive Habitat's navigability
+    filter, and the patched module's `remove_points`.  The class keeps its own `build_frontiers`, `generate_Gaussian_at_frontier`
+    and `generate_candidate`.  Needs FisherOps and PointScoreOps installed.  Opt-in: nothing is installed by default.
+
+    What differs from the reference is listed in INTEGRATION.md section 4: binary32 distances in DBSCAN, a non-finite centre is
+    noise, the `global_planning_iter{frame}.npz` dump only with `dump_labels=True`, the candidates scored in one batch after the
+    navigability loop instead of one by one inside it, no print of the pruned count and no empty_cache()."""
+
+    QUANTILE, DBSCAN_EPS, DBSCAN_MIN_SAMPLES = 0.8, 0.1, 5        # gaussian.py:1226, 1239
+
+    def select_target_points(self, scorePoints, K, dump_labels=False):
+        """(center_point [K,3], or [1,3] when nothing is above the threshold, on the device; selected_points_index int64 or None).
+        Draws np.random.randint(0, n_selected, (K,)) exactly as gaussian.py:1269 does, so a seeded run draws the same rows; the
+        centres are gathered on the device.  When no cluster qualifies, max_label stays -1 and the draw is among the NOISE rows,
+        as `labels == max_count_label` selects them there; with no such row np.random.randint raises, as it does there."""
+        from fisher_rast.cluster import select_target
+        height_range = self.config["explore"]["height_range"]
+        lower_y, upper_y = self.cam_height - height_range, self.cam_height + height_range
+        means = self.params["means3D"].detach()
+        sel = select_target(means, scorePoints.detach(), lower_y, upper_y, q=self.QUANTILE, eps=self.DBSCAN_EPS,
+                            min_samples=self.DBSCAN_MIN_SAMPLES)
+        self._last_target_selection = sel
+        if sel.n_above == 0:
+            return means[sel.argmax].unsqueeze(0), None                                       # gaussian.py:1274-1276
+        if dump_labels:
+            # the reference's dump (1259-1264), the only path that copies labels to the host
+            segmentated_labels = np.ones((int(scorePoints.shape[0]),)) * -1
+            segmentated_labels[sel.points_index.cpu().numpy()] = sel.labels.cpu().numpy()
+            points_index_range_np = sel.points_index_range.cpu().numpy().astype(np.int64)
+            np.savez(os.path.join(self.eval_dir, f"global_planning_iter{self.frame_idx}.npz"),
+                     segmentated_labels=segmentated_labels[points_index_range_np], max_label=sel.max_label,
+                     points_index_range=points_index_range_np)
+        selected_points_index = sel.selected_points_index.long()
+        draws = np.random.randint(0, sel.n_selected, (K,))
+        center_point = means[selected_points_index[torch.from_numpy(draws).to(means.device)]]
+        return center_point, selected_points_index
+
+    def global_planning(self, follower, agent_pose):
+        """The reference's global_planning (gaussian.py:1176-1336): same arguments, returns (scores cpu [V'], stack of the navigable
+        c2w [V',4,4]) or (None, None) when no candidate is navigable."""
+        import sys
+        for name in ("compute_H_train", "pose_eval_points", "_scorer", "_keyframe_key"):
+            if not hasattr(self, name):
+                raise RuntimeError(f"TargetSelectOps.global_planning needs FisherOps and PointScoreOps installed on {type(self).__name__} ({name} is missing)")
+        # the module whose remove_points MapEditOps.install replaces: that of the class, or of the base a subclass took it from
+        mod = next((m for m in (sys.modules.get(c.__module__) for c in type(self).__mro__) if m is not None and hasattr(m, "remove_points")), None)
+        frontier = self.build_frontiers()
+        self.generate_Gaussian_at_frontier()
+        use_frontier = frontier is not None and self.selection < 2
+
+        agent_pos = agent_pose[:3, 3]
+        H_train = self.compute_H_train()
+        if H_train is None:
+            raise RuntimeError("global_planning: no keyframe to take H_train from")
+        H_train_inv = torch.reciprocal(H_train + self.H_TRAIN_REG)
+        scorePoints = torch.sum(H_train_inv, dim=1)
+        kkey = self._keyframe_key()
+        if kkey is not None:
+            self._h_inv_cache = (self._scorer(None), kkey, H_train_inv)                      # pose_eval_points below reuses it
+
+        with torch.no_grad():
+            K = self.config["explore"]["sample_view_num"]
+            dev = scorePoints.device
+            if use_frontier:
+                frontier_height = np.ones((frontier.shape[0], )) * self.cam_height
+                frontier = np.stack([frontier[:, 0], frontier_height, frontier[:, 1]], axis=1)
+                frontier = torch.from_numpy(frontier).to(dev)
+                frontier_rand_index = torch.randint(0, frontier.shape[0], (K, ))
+                center_point = frontier[frontier_rand_index.to(dev)]
+                selected_points_index = None
+            else:
+                center_point, selected_points_index = self.select_target_points(scorePoints, K)
+
+            c2ws = self.generate_candidate(center_point)
+            positions = torch.stack([c2w[:3, 3] for c2w in c2ws]).cpu().numpy() if len(c2ws) else np.zeros((0, 3))
+            navigable_c2w = []
+            for c2w, target_pos in zip(c2ws, positions):
+                target_pos = target_pos.copy()
+                target_pos[1] = agent_pos[1]
+                if follower.pathfinder.is_navigable(target_pos):
+                    try:
+                        follower.reset()
+                        len(list(follower.find_path(target_pos)))
+                    except Exception:
+                        # Some time the follower throws an exception even if it's navigable
+                        print(f"[WARN] Exception found when finding action lens for {target_pos}")
+                        continue
+                    navigable_c2w.append(c2w)
+
+            scores = None
+            max_points_score = torch.zeros((scorePoints.shape[0], ), device=dev)
+            if len(navigable_c2w):
+                scores, navigable_c2w, max_points_score = self.pose_eval_points(navigable_c2w)
+
+            # culling invisible
+            if self.config["explore"]["prune_invisible"] and selected_points_index is not None:
+                if mod is None:
+                    raise RuntimeError(f"global_planning: the module of {type(self).__name__} does not define remove_points")
+                low = max_points_score[selected_points_index] < scorePoints[selected_points_index] * 2
+                remove_index = torch.zeros((self.params["means3D"].shape[0], ), dtype=torch.bool, device=dev)
+                remove_index[selected_points_index] = low
+                self.params, self.variables = mod.remove_points(remove_index, self.params, self.variables, None)
+
+            self.selection += 1
+            if scores is None:
+                return None, None
+            return scores, navigable_c2w
+
+    @classmethod
+    def install(cls, target_cls):
+        """Graft the two methods onto the reference's class (after FisherOps.install and PointScoreOps.install)."""
+        for name in ("QUANTILE", "DBSCAN_EPS", "DBSCAN_MIN_SAMPLES", "select_target_points", "global_planning"):
             setattr(target_cls, name, getattr(cls, name))
         return target_cls
 

@@ -709,6 +709,48 @@ int fr_cloud_index_build(int32_t N, const float* points, void* index, size_t ind
 int fr_cloud_query(const void* index, size_t index_bytes, int32_t N, const fr_cloud_query_cfg* cfg, void* workspace,
                    size_t workspace_bytes, fr_stream_t stream);
 
+/* ---- DBSCAN and the target selection of global_planning ---------------------------------------------------------------------
+ * The middle of the reference's global_planning (models/SLAM/gaussian.py:1216-1276; the same lines at gaussian_object.py:1419-1479):
+ * the Gaussians of a height band, torch.quantile of their scores, sklearn.cluster.DBSCAN(eps, min_samples) on the host over those
+ * above it, a Python loop for the cluster with the highest score.  Arithmetic and the labelling rule in csrc/fr_cluster_math.h:
+ * binary32, one rounding per written operation, d2 = (dx*dx + dy*dy) + dz*dz, a neighbour when d2 <= eps*eps (itself included);
+ * core = at least min_samples neighbours; clusters = connected components of the core points, numbered by ascending lowest
+ * original index of their core points; a point that is not core takes the lowest cluster number among its core neighbours, else
+ * -1.  These are sklearn's labels_ wherever no pair lies within rounding of eps.  A point with a non-finite coordinate is noise
+ * and nobody's neighbour (sklearn raises).  Integer atomics only: the same call gives the same bytes.
+ * Nothing is allocated, nothing is read back, no environment variable is read; every launch and memset is on `stream`.
+ * The search grid has 1024 cells per axis of side max(1.125 eps, extent / 1024), per axis: a cloud wider than that (115 m at
+ * eps = 0.1) gets larger cells on that axis, which is slower and never wrong; status reports the three sides. */
+#define FR_CLUSTER_MAX_POINTS (1 << 26)
+#define FR_DBSCAN_STATUS_WORDS 8         /* int32: {clusters, finite points, side x, side y, side z (float bits), 0, 0, 0} */
+#define FR_TARGET_STATUS_WORDS 16        /* int32: {n_band, n_above, n_clusters, max_label, n_selected, argmax, side x, side y, side z
+                                            (float bits), nan flag, threshold (float bits), finite points among those above, 0...} */
+/* Host-only queries, non-decreasing in their argument (0 for an argument outside [0, FR_CLUSTER_MAX_POINTS]). */
+size_t fr_dbscan_workspace_bytes(int32_t N);
+size_t fr_target_select_workspace_bytes(int32_t P);
+/* labels [N] int32 of points [N,3].  status: FR_DBSCAN_STATUS_WORDS int32 on the device.  FR_EINVAL for N outside the limits, an eps
+ * whose square is not a normal binary32 number, min_samples < 1, a null pointer (points and labels may be null when N = 0), a
+ * pointer not 4-byte (workspace: 8-byte) aligned, a short workspace. */
+int fr_dbscan(int32_t N, const float* points, float eps, int32_t min_samples, int32_t* labels, int32_t* status,
+              void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* One call for gaussian.py:1221-1267 over means3D [P,3] and scores [P]; every output stays on the device, each list ascending:
+ *   out_band_idx [P]      the rows with lower_y <= y <= upper_y (points_index_range), n_band of them;
+ *   out_threshold [1]     torch.quantile(scores[band], q): the order statistics floor and ceil of fl(q * fl(n_band - 1)) by radix
+ *                         select, joined by frk_lerp (NaN when the band is empty);
+ *   out_above_idx [P]     the band rows with score > threshold (points_index), n_above of them;
+ *   out_labels [P]        the DBSCAN labels of those rows, in the order of out_above_idx;
+ *   out_selected_idx [P]  the rows of out_above_idx whose label is max_label (selected_points_index), n_selected of them.
+ * max_label follows the reference's loop: from max_score = -1 a cluster wins on strict >, so the lowest label wins a tie; when no
+ * cluster qualifies it stays -1, which selects the NOISE rows, as `labels == max_count_label` does there.  status
+ * (FR_TARGET_STATUS_WORDS int32 on the device, the one thing a caller reads): the counts, max_label, the lowest row that attains
+ * the band's highest score (-1 for an empty band: the reference's `else` branch at 1274), the cell sides, and a flag that is 1
+ * when a band score is NaN -- the threshold is then not torch's, and the caller takes another route.
+ * Only the first n_* entries of a list are written.  FR_EINVAL as fr_dbscan, and for q outside [0, 1]. */
+int fr_target_select(int32_t P, const float* means3D, const float* scores, float lower_y, float upper_y, float q, float eps,
+                     int32_t min_samples, int32_t* out_band_idx, int32_t* out_above_idx, int32_t* out_labels,
+                     int32_t* out_selected_idx, float* out_threshold, int32_t* status, void* workspace, size_t workspace_bytes,
+                     fr_stream_t stream);
+
 /* ---- measurement hooks (not part of the reference surface) ------------------------------------------ */
 
 /* When enabled, every fr_fisher_views call records a pair of HIP events around its dominant kernel
