@@ -200,6 +200,16 @@ FR_CLUSTER_MAX_POINTS = 1 << 26
 FR_DBSCAN_STATUS_WORDS = 8
 FR_TARGET_STATUS_WORDS = 16
 
+FR_EVAL_ROW = 8
+FR_EVAL_GT_F32_CHW, FR_EVAL_GT_U8_HWC = 0, 1
+
+
+class ViewMetricsCfg(ctypes.Structure):
+    """fr_view_metrics_cfg (include/fisher_rast.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("V", "H", "W", "gt_layout", "gt_channels", "clamp_render", "depth_valid_only")] + \
+               [(n, ctypes.c_int64) for n in ("render_view_stride", "depth_view_stride", "gt_depth_view_stride")]
+
+
 FR_PLAN_STATUS_WORDS = 4
 FR_PLAN_TILE = 64
 FR_PLAN_UNREACHED = 0xFFFFFFFFFFFFFFFF
@@ -224,14 +234,15 @@ EXPORTS = (
     "fr_plan_workspace_bytes", "fr_plan_round_cap", "fr_plan_grid", "fr_plan_tiers", "fr_plan_field", "fr_plan_paths",
     "fr_cloud_index_bytes", "fr_cloud_index_workspace_bytes", "fr_cloud_query_workspace_bytes", "fr_cloud_index_build", "fr_cloud_query",
     "fr_dbscan_workspace_bytes", "fr_target_select_workspace_bytes", "fr_dbscan", "fr_target_select",
+    "fr_view_metrics_workspace_bytes", "fr_view_metrics", "fr_view_metrics_summary",
 )
 
 _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_math.h",
-                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_eval.hip", "fr_math.h",
+                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_eval_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -491,6 +502,13 @@ def load():
         lib.fr_target_select.restype = ctypes.c_int
         lib.fr_target_select.argtypes = [ctypes.c_int32, _f32p, _f32p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                          ctypes.c_int32] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
+    if hasattr(lib, "fr_view_metrics"):
+        lib.fr_view_metrics_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_view_metrics_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+        lib.fr_view_metrics.restype = ctypes.c_int
+        lib.fr_view_metrics.argtypes = [ctypes.POINTER(ViewMetricsCfg)] + [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_view_metrics_summary.restype = ctypes.c_int
+        lib.fr_view_metrics_summary.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     _lib = lib
     return lib
 

@@ -14,6 +14,8 @@ Four groups of entry points:
     (models/SLAM/gaussian.py:320-414, 75-143, 299-318).
   * `keyframe_valid_pixels` / `keyframe_overlap` -- the pixels of a frame with a measured depth, and how many of the points drawn from
     them each keyframe sees (models/SLAM/utils/keyframe_selection.py:10-37, 40-134).
+  * `view_metrics` / `view_metrics_summary` -- PSNR, SSIM and depth error of a batch of rendered views against their ground truth
+    (tester_gaussians_navigation.py:1450-1491, models/SLAM/utils/eval_helpers.py:230-257).
 """
 import ctypes
 from typing import Optional
@@ -1140,3 +1142,108 @@ def rendervar_backward(P, scale_cols, time_idx, n_frames, tensors):
     with torch.cuda.device(dev):
         _lib.check(lib.fr_rendervar_backward(ctypes.byref(cfg), None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, _stream(dev)),
                    "fr_rendervar_backward")
+
+
+# ---- render-quality evaluation (fr_view_metrics) --------------------------------------------------------------------------------
+
+_view_metrics_ws = {}
+
+
+def _view_metrics_workspace(dev, nbytes):
+    """the partial sums' workspace, kept per (device, stream) and only ever grown, as `_backward_scratch` is"""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(dev).cuda_stream))
+    ws = _view_metrics_ws.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        _view_metrics_ws[key] = None
+        ws = _view_metrics_ws[key] = torch.empty((nbytes // 8 + (nbytes >> 5),), dtype=torch.float64, device=dev)
+    return ws
+
+
+def _view_images(t, name, V, H, W, dev):
+    """(tensor, view stride in elements) of a float32 [V,1,H,W] or [V,H,W] whose H W blocks are contiguous; the views may be strided
+    (channel 0 of a [V,3,H,W] tensor is taken where it lies, not copied)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev:
+        raise ValueError(f"view_metrics: {name} must be a float32 tensor on {dev}")
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if tuple(t.shape) != (V, H, W):
+        raise ValueError(f"view_metrics: {name} of shape {tuple(t.shape)} does not fit [{V},1,{H},{W}] or [{V},{H},{W}]")
+    inner = (W == 1 or t.stride(2) == 1) and (H == 1 or t.stride(1) == W)
+    if not inner or (V > 1 and t.stride(0) < H * W):
+        raise ValueError(f"view_metrics: the H W block of every view of {name} must be contiguous (strides {tuple(t.stride())})")
+    return t, (int(t.stride(0)) if V > 1 else H * W)
+
+
+def view_metrics(render, gt_rgb, depth=None, gt_depth=None, mask=None, clamp=True, depth_valid_only=False, out=None):
+    """PSNR, SSIM and depth error of V rendered views against their ground truth in one call (fr_view_metrics, include/fisher_rast.h):
+    {"rows": [V,8] = {psnr, ssim, depth_l1, depth_rmse, mse_r, mse_g, mse_b, depth_count} per view, "summary": [8] = {views kept,
+    mean psnr, mean ssim, mean depth_l1, mean depth_rmse, 0, 0, V}} on the device, on torch's current stream, without a synchronisation.
+    render: float32 [V,3,H,W]; gt_rgb: float32 [V,3,H,W] or uint8 [V,H,W,3|4] (value / 255, channels 0..2); depth / gt_depth: float32
+    [V,1,H,W] or [V,H,W], both or neither, the views may be strided; mask: bool / uint8 [V,H,W] or [V,1,H,W].  `clamp`: the render is
+    clamped to [0,1] first (eval_navigation); `depth_valid_only`: the depth terms over the pixels with gt_depth > 0 (report_progress).
+    `out`: a dict that may hold contiguous float32 device tensors "rows" [V,8] and "summary" [8], written instead of fresh ones.
+    Anything else -- another dtype or device, an H W block that is not contiguous -- raises ValueError."""
+    if not isinstance(render, torch.Tensor) or not render.is_cuda or render.dtype != torch.float32 or render.dim() != 4 or render.shape[1] != 3:
+        raise ValueError("view_metrics: render must be a float32 [V,3,H,W] tensor on a HIP device")
+    dev = render.device
+    V, _, H, W = (int(s) for s in render.shape)
+    if V < 1 or H < 1 or W < 1:
+        raise ValueError(f"view_metrics: an empty render {tuple(render.shape)}")
+    inner = render[0].is_contiguous() and (V == 1 or render.stride(0) >= 3 * H * W)
+    if not inner:
+        raise ValueError(f"view_metrics: the [3,H,W] block of every view of render must be contiguous (strides {tuple(render.stride())})")
+    if not isinstance(gt_rgb, torch.Tensor) or gt_rgb.device != dev or not gt_rgb.is_contiguous():
+        raise ValueError(f"view_metrics: gt_rgb must be a contiguous tensor on {dev}")
+    if gt_rgb.dtype == torch.float32 and tuple(gt_rgb.shape) == (V, 3, H, W):
+        layout, channels = _lib.FR_EVAL_GT_F32_CHW, 3
+    elif gt_rgb.dtype == torch.uint8 and gt_rgb.dim() == 4 and tuple(gt_rgb.shape[:3]) == (V, H, W) and gt_rgb.shape[3] in (3, 4):
+        layout, channels = _lib.FR_EVAL_GT_U8_HWC, int(gt_rgb.shape[3])
+    else:
+        raise ValueError(f"view_metrics: gt_rgb must be float32 [{V},3,{H},{W}] or uint8 [{V},{H},{W},3|4], not {gt_rgb.dtype} {tuple(gt_rgb.shape)}")
+    if (depth is None) != (gt_depth is None):
+        raise ValueError("view_metrics: depth and gt_depth go together (both or neither)")
+    dvs = gvs = H * W
+    if depth is not None:
+        depth, dvs = _view_images(depth, "depth", V, H, W, dev)
+        gt_depth, gvs = _view_images(gt_depth, "gt_depth", V, H, W, dev)
+    m = None
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.device != dev or mask.dtype not in (torch.bool, torch.uint8) or mask.numel() != V * H * W:
+            raise ValueError(f"view_metrics: mask must be a bool or uint8 [{V},{H},{W}] tensor on {dev}")
+        m = mask.reshape(V, H, W).contiguous()
+        m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    given = out or {}
+
+    def new(name, *shape):
+        t = given.get(name)
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"view_metrics: out['{name}'] must be a contiguous float32 tensor of shape {shape} on {dev}")
+        return t
+    rows, summary = new("rows", V, _lib.FR_EVAL_ROW), new("summary", _lib.FR_EVAL_ROW)
+    lib = _lib.load()
+    nbytes = int(lib.fr_view_metrics_workspace_bytes(V, H, W))
+    if nbytes == 0:
+        raise ValueError(f"view_metrics: {V} views of {H} x {W} are outside the library's limits (V <= 65535, H W <= 2^30)")
+    cfg = _lib.ViewMetricsCfg(V, H, W, layout, channels, int(bool(clamp)), int(bool(depth_valid_only)),
+                              int(render.stride(0)) if V > 1 else 3 * H * W, dvs, gvs)
+    with torch.cuda.device(dev):
+        ws = _view_metrics_workspace(dev, nbytes)
+        _lib.check(lib.fr_view_metrics(ctypes.byref(cfg), render.data_ptr(), None if depth is None else depth.data_ptr(), gt_rgb.data_ptr(),
+                                       None if gt_depth is None else gt_depth.data_ptr(), None if m is None else m.data_ptr(),
+                                       rows.data_ptr(), summary.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(dev)), "fr_view_metrics")
+    return {"rows": rows, "summary": summary}
+
+
+def view_metrics_summary(rows, out=None):
+    """The summary [8] over rows [V,8] that several `view_metrics` calls filled slice by slice: one launch on the current stream."""
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dtype != torch.float32 or rows.dim() != 2 \
+            or rows.shape[1] != _lib.FR_EVAL_ROW or rows.shape[0] < 1 or not rows.is_contiguous():
+        raise ValueError("view_metrics_summary: rows must be a contiguous float32 [V,8] tensor on a HIP device, V >= 1")
+    dev = rows.device
+    summary = torch.empty((_lib.FR_EVAL_ROW,), dtype=torch.float32, device=dev) if out is None else out
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().fr_view_metrics_summary(rows.data_ptr(), int(rows.shape[0]), summary.data_ptr(), _stream(dev)),
+                   "fr_view_metrics_summary")
+    return summary

@@ -521,6 +521,42 @@ class RenderOps:
         return target_cls
 
 
+class RenderEvalOps:
+    """Mixin with the render-quality evaluation (fr_view_metrics, include/fisher_rast.h; fisher_rast/render_eval.py): the metric loop
+    of NavTester.eval_navigation (tester_gaussians_navigation.py:1397-1491) over a batch of poses, and report_progress's metrics of
+    one training frame (models/SLAM/utils/eval_helpers.py:230-257).  New names; `render_at_pose` stays as it is.  Needs FisherOps'
+    `_scorer` / `_stack_poses` and RenderOps (install them first)."""
+
+    def eval_views(self, c2ws, rgb_gt, depth_gt=None, chunk=64, on_chunk=None):
+        """PSNR, SSIM and depth error of V camera-to-world poses against Habitat's images -- rgb_gt uint8 [V,H,W,3|4] (observations['rgb']
+        stacked) or float32 [V,3,H,W], depth_gt float32 [V,1,H,W] / [V,H,W] or None -- rendered and scored `chunk` poses at a time with
+        one host read.  Returns a fisher_rast.render_eval.ViewEvaluation: .psnr / .ssim / .depth_mae / .depth_rmse / .kept per view and
+        .mean, the tester's test/psnr, test/ssim, test/depth_mae (views with an infinite PSNR left out, as there).
+        `on_chunk(v0, v1, render, depth)` sees each chunk's clamped images (LPIPS, image dumps)."""
+        from fisher_rast.render_eval import evaluate_views
+        return evaluate_views(self, c2ws, rgb_gt, depth_gt, chunk=chunk, on_chunk=on_chunk)
+
+    def frame_metrics(self, im, gt_im, depth=None, gt_depth=None, mask=None):
+        """report_progress's metrics of one frame on the device, without a host read: {"psnr", "ssim", "depth_l1", "depth_rmse"} as
+        0-dim tensors and "row", the frame's 8 floats.  im, gt_im: float32 [3,H,W]; depth, gt_depth: [1,H,W] or [H,W]; mask: the
+        presence mask [H,W] / [1,H,W] of the tracking form, which multiplies both images and the depth difference.  No clamp; the
+        depth terms run over the pixels with gt_depth > 0.  depth_rmse is sqrt(mean of squares), not the reference's second L1."""
+        from fisher_rast.ops import view_metrics
+
+        def one(t):
+            return None if t is None else t.reshape((1,) + tuple(t.shape[-2:]))
+        r = view_metrics(im.unsqueeze(0), gt_im.unsqueeze(0), one(depth), one(gt_depth), one(mask), clamp=False, depth_valid_only=True)
+        row = r["rows"][0]
+        return {"psnr": row[0], "ssim": row[1], "depth_l1": row[2], "depth_rmse": row[3], "row": row}
+
+    @classmethod
+    def install(cls, target_cls):
+        """Graft the two methods onto the reference's class (after FisherOps.install and RenderOps.install)."""
+        for name in ("eval_views", "frame_metrics"):
+            setattr(target_cls, name, getattr(cls, name))
+        return target_cls
+
+
 class PointScoreOps:
     """Mixin with the per-Gaussian scores of candidate poses (fr_fisher_point_views, include/fisher_rast.h): the candidate scan of
     the reference's `global_planning` (models/SLAM/gaussian.py:1285-1316) -- `pointScores = sum(cur_H * H_train_inv, dim=1)` per
@@ -775,7 +811,7 @@ class OptimizerOps:
         return target_cls
 
 
-class GaussianSLAM(FisherOps, PoseFisherOps, RenderOps, PointScoreOps):
+class GaussianSLAM(FisherOps, PoseFisherOps, RenderOps, RenderEvalOps, PointScoreOps):
     """Standalone carrier of the operator surface: a Gaussian map (param dict), a camera and keyframes."""
 
     def __init__(self, config=None, params=None, intrinsics=None, width=None, height=None, device="cuda"):

@@ -4,6 +4,7 @@ Gaussians (fr_densify_stats / fr_densify_masks / fr_prune_mask, include/fisher_r
 
 `calc_ssim` / `calc_ssim_masked` (slam_external.py:89-120, 144-193) are the fused image-loss kernels (fr_image_loss_forward /
 fr_image_loss_backward through fisher_rast/image_loss.py): one forward launch pair, one backward launch, no host synchronisation.
+`calc_mse` / `calc_psnr` (slam_external.py:68-74) take a float32 [3,H,W] pair on the device through fr_view_metrics.
 
 What the reference then DOES with a mask -- cloning / splitting the parameter tensors, rebuilding the Adam state
 (cat_params_to_optimizer, remove_points, slam_external.py:203-262) and the bodies of prune_gaussians / densify (345-463) -- is the map
@@ -133,6 +134,27 @@ def calc_ssim_masked(img1, img2, mask, window_size=11):
         img1, img2 = img1[0], img2[0]
     H, W = int(img1.shape[-2]), int(img1.shape[-1])
     return _il.image_loss(img1, img2, mask.reshape(1, H, W), 0.0, -1.0, _il.FR_LOSS_L1_SUM, weights_map=True, which=_il.OUT_SSIM)[0]
+
+
+def _on_kernel(img1, img2):
+    """a float32 [3,H,W] pair on one HIP device that asks for no gradient: what fr_view_metrics takes as one view"""
+    return (isinstance(img1, torch.Tensor) and isinstance(img2, torch.Tensor) and img1.is_cuda and img1.device == img2.device
+            and img1.dtype == img2.dtype == torch.float32 and img1.dim() == 3 and img1.shape[0] == 3 and img1.shape == img2.shape
+            and img1.numel() > 0 and not (torch.is_grad_enabled() and (img1.requires_grad or img2.requires_grad)))
+
+
+def calc_mse(img1, img2):
+    """slam_external.py:68-69: the mean squared difference per channel, [C,1].  A float32 [3,H,W] pair on a HIP device is one
+    fr_view_metrics call (binary64 sums in a fixed order, rounded once); anything else takes the torch expression."""
+    if _on_kernel(img1, img2):
+        from fisher_rast.ops import view_metrics
+        return view_metrics(img1.contiguous().unsqueeze(0), img2.contiguous().unsqueeze(0), clamp=False)["rows"][0, 4:7].reshape(3, 1)
+    return torch.square(img1 - img2).reshape(img1.shape[0], -1).mean(dim=1, keepdim=True)
+
+
+def calc_psnr(img1, img2):
+    """slam_external.py:72-74: 20 log10(1 / sqrt(mse)) per channel, [C,1]; +inf where the channels are equal."""
+    return 20 * torch.log10(1.0 / torch.sqrt(calc_mse(img1, img2)))
 
 
 # ---- the map edit: a prune or densify mask applied to the map, its Adam state and its statistics ---------------------------------

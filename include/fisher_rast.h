@@ -751,6 +751,52 @@ int fr_target_select(int32_t P, const float* means3D, const float* scores, float
                      int32_t* out_selected_idx, float* out_threshold, int32_t* status, void* workspace, size_t workspace_bytes,
                      fr_stream_t stream);
 
+/* ---- render-quality evaluation: PSNR, SSIM and depth error per view ------------------------------------------------------------
+ * What NavTester.eval_navigation computes per rendered pose (tester_gaussians_navigation.py:1450-1491: color.clamp_(0, 1),
+ * calc_psnr(color, rgb_gt).mean(), mean |depth - depth_gt|, ssim(color, rgb_gt), the `torch.isinf(psnr)` skip) and report_progress
+ * per training frame (models/SLAM/utils/eval_helpers.py:230-257), for a batch of V views in three launches.  Arithmetic in
+ * csrc/fr_eval_math.h over csrc/fr_loss_math.h (the SSIM map is the image loss's, bit for bit, except where a window's mean is below
+ * 2^-5 in either image: there the reference's raw moments, which the loss's moments about 0.5 cannot match): per pixel binary32, one rounding
+ * per written operation; every sum binary64 -- per-workgroup partials stored plainly and added in a fixed order, a row finalised in
+ * binary64 and rounded once.  No atomics: the same call gives the same bits.  Device pointers, explicit stream, nothing allocated,
+ * nothing read back.
+ *   rows[v]  = {psnr, ssim, depth_l1, depth_rmse, mse_r, mse_g, mse_b, depth_count}
+ *              psnr = the mean over the three channels of 20 log10(1 / sqrt(mse_c)); ssim = the mean of the SSIM map over 3 H W;
+ *              depth_l1 = sum |dd| / depth_count, depth_rmse = sqrt(sum dd^2 / depth_count), dd = (depth - gt_depth) [* mask] in
+ *              binary32.  The reference's own "RMSE" (eval_helpers.py:242-251) takes sqrt of EACH square and so equals its L1;
+ *              that is not reproduced under this name.  depth_count = H W, or with depth_valid_only the pixels with gt_depth > 0
+ *              (none: 0 / 0 = NaN, as torch gives).  Without depth the three depth entries are NaN.
+ *   summary  = {views kept, mean psnr, mean ssim, mean depth_l1, mean depth_rmse, 0, 0, V}: the means over the views the reference
+ *              keeps, added in index order in binary64.  A view whose psnr is infinite (render == target in a channel; an empty
+ *              mask) is left out of every mean; a NaN psnr is not and makes the means NaN; no view kept: NaN.
+ * With a mask (0 / 1 bytes) the clamped render and the target are multiplied by it before PSNR and SSIM, and the depth difference
+ * as well.  The clamp keeps a NaN a NaN, as torch.clamp does. */
+#define FR_EVAL_ROW 8
+enum { FR_EVAL_GT_F32_CHW = 0,    /* gt_rgb: float [V][3][H][W]                                                        */
+       FR_EVAL_GT_U8_HWC  = 1 };  /* gt_rgb: uint8 [V][H][W][gt_channels], channels 0..2 used, value / 255 (Habitat)   */
+typedef struct {
+	int32_t V, H, W;                  /* 1 <= V <= 65535, H W <= 2^30 */
+	int32_t gt_layout, gt_channels;   /* gt_channels: 3 or 4, U8_HWC only                                             */
+	int32_t clamp_render;             /* 1: render clamped to [0,1] first (eval_navigation's color.clamp_)            */
+	int32_t depth_valid_only;         /* 0: depth error averaged over all H W pixels (eval_navigation);               */
+	                                  /* 1: summed where gt_depth > 0, divided by their count (report_progress)       */
+	int64_t render_view_stride, depth_view_stride, gt_depth_view_stride;   /* in elements; >= 3 H W, H W, H W: a view's image is
+	                                     contiguous, the views need not be (the depth of fr_render_views is channel 0 of [V,3,H,W]) */
+} fr_view_metrics_cfg;
+/* Host only; 0 for an argument outside the limits. */
+size_t fr_view_metrics_workspace_bytes(int32_t V, int32_t H, int32_t W);
+/* rows [V][FR_EVAL_ROW] and summary [FR_EVAL_ROW] of a batch.  depth and gt_depth may both be null (colour only); mask [V][H][W]
+ * or null.  FR_EINVAL for a null cfg, render, gt_rgb, rows or summary, V / H / W outside the limits, an unknown layout, gt_channels
+ * other than 3 or 4 for a byte target, a flag that is not 0 or 1, only one of depth / gt_depth, a view stride below its image,
+ * a null, short or not 8-byte aligned workspace. */
+int fr_view_metrics(const fr_view_metrics_cfg* cfg, const float* render, const float* depth, const void* gt_rgb,
+                    const float* gt_depth, const uint8_t* mask /* [V][H][W] 0/1 or null */,
+                    float* rows /* [V][FR_EVAL_ROW] */, float* summary /* [FR_EVAL_ROW] */,
+                    void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* The summary alone over rows [V][FR_EVAL_ROW] that several fr_view_metrics calls filled slice by slice (an evaluation in chunks):
+ * one launch.  FR_EINVAL for a null pointer or V < 1. */
+int fr_view_metrics_summary(const float* rows, int32_t V, float* summary, fr_stream_t stream);
+
 /* ---- measurement hooks (not part of the reference surface) ------------------------------------------ */
 
 /* When enabled, every fr_fisher_views call records a pair of HIP events around its dominant kernel
