@@ -210,6 +210,16 @@ class ViewMetricsCfg(ctypes.Structure):
                [(n, ctypes.c_int64) for n in ("render_view_stride", "depth_view_stride", "gt_depth_view_stride")]
 
 
+FR_LOSS_MASK_STATUS_WORDS = 5
+FR_OUTSIDE_STATUS_WORDS = 6
+
+
+class LossMaskCfg(ctypes.Structure):
+    """fr_loss_mask_cfg (include/fisher_rast.h)"""
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("sil_thres", ctypes.c_float), ("reject_outliers", ctypes.c_int32),
+                ("outlier_ratio", ctypes.c_float), ("need_presence", ctypes.c_int32)]
+
+
 FR_PLAN_STATUS_WORDS = 4
 FR_PLAN_TILE = 64
 FR_PLAN_UNREACHED = 0xFFFFFFFFFFFFFFFF
@@ -235,14 +245,16 @@ EXPORTS = (
     "fr_cloud_index_bytes", "fr_cloud_index_workspace_bytes", "fr_cloud_query_workspace_bytes", "fr_cloud_index_build", "fr_cloud_query",
     "fr_dbscan_workspace_bytes", "fr_target_select_workspace_bytes", "fr_dbscan", "fr_target_select",
     "fr_view_metrics_workspace_bytes", "fr_view_metrics", "fr_view_metrics_summary",
+    "fr_loss_mask_workspace_bytes", "fr_loss_mask", "fr_bg_penalty_workspace_bytes", "fr_bg_penalty_forward", "fr_bg_penalty_backward",
+    "fr_outside_mask_workspace_bytes", "fr_outside_mask",
 )
 
 _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_eval.hip", "fr_math.h",
-                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_eval_math.h", "fr_internal.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_eval.hip", "fr_objloss.hip", "fr_math.h",
+                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_eval_math.h", "fr_objloss_math.h", "fr_internal.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -509,6 +521,24 @@ def load():
         lib.fr_view_metrics.argtypes = [ctypes.POINTER(ViewMetricsCfg)] + [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_void_p]
         lib.fr_view_metrics_summary.restype = ctypes.c_int
         lib.fr_view_metrics_summary.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    if hasattr(lib, "fr_loss_mask"):
+        lib.fr_loss_mask_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_loss_mask_workspace_bytes.argtypes = [ctypes.c_int32] * 2
+        lib.fr_loss_mask.restype = ctypes.c_int
+        lib.fr_loss_mask.argtypes = [ctypes.POINTER(LossMaskCfg), _f32p, _f32p] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_bg_penalty_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_bg_penalty_workspace_bytes.argtypes = [ctypes.c_int32] * 2
+        lib.fr_bg_penalty_forward.restype = ctypes.c_int
+        lib.fr_bg_penalty_forward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _f32p, _f32p, ctypes.c_void_p,
+                                              _f32p, _f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        lib.fr_bg_penalty_backward.restype = ctypes.c_int
+        lib.fr_bg_penalty_backward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _f32p, _f32p, ctypes.c_void_p,
+                                               _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p]
+        lib.fr_outside_mask_workspace_bytes.restype = ctypes.c_size_t
+        lib.fr_outside_mask_workspace_bytes.argtypes = [ctypes.c_int32]
+        lib.fr_outside_mask.restype = ctypes.c_int
+        lib.fr_outside_mask.argtypes = [ctypes.c_int32, ctypes.c_int32, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     _lib = lib
     return lib
 

@@ -30,6 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from diff_gaussian_rasterization import GaussianRasterizer as Renderer
+from fisher_rast import object_loss as _object_loss
 from fisher_rast import ops as _ops
 from fisher_rast.ops import FisherScorer
 from models.SLAM.utils.common_utils import checkpoint_time_idx, load_params_ckpt, save_params, save_params_ckpt
@@ -56,7 +57,31 @@ def _loss_pixel_mask(depth_sil, gt_depth, sil_thres, reject_outliers, need_prese
     return rendered, keep.detach()
 
 
-def make_get_loss(transform_to_frame, calc_loss, fused_rendervar=False):
+def _object_mask_of(curr_data, device):
+    """curr_data['obj_mask_2d'] as the object lines of the reference's get_loss take it (models/SLAM/gaussian_object.py:236-242): bool
+    [H,W] on the render's device, or None when the frame has none"""
+    obj = curr_data.get('obj_mask_2d', None)
+    if obj is None:
+        return None
+    if obj.dtype != torch.bool:
+        obj = obj.bool()
+    if obj.ndim == 3:
+        obj = obj.squeeze(-1)
+    return obj.to(device)
+
+
+def _background_penalty_torch(im, silhouette, obj, lambda_rgb=0.1, lambda_alpha=0.1):
+    """The two background penalties of the object class as the reference writes them (models/SLAM/gaussian_object.py:263-275): the
+    mean |im| and the mean clamped silhouette over the pixels outside the object mask `obj` (bool [H,W]), weighted -- what is added
+    to the colour term."""
+    bg1 = (~obj).unsqueeze(0)
+    bg3 = torch.tile(bg1, (3, 1, 1)).float()
+    l_rgb = (torch.abs(im) * bg3).sum() / bg3.sum().clamp_min(1)
+    l_alpha = (silhouette.clamp(min=0, max=1) * bg1).sum() / bg1.sum().clamp_min(1)
+    return lambda_rgb * l_rgb + lambda_alpha * l_alpha
+
+
+def make_get_loss(transform_to_frame, calc_loss, fused_rendervar=False, fused_mask=False, object_mask=False):
     """Drop-in for the module-level `get_loss` of the reference (models/SLAM/gaussian.py:184-297): same signature, same return
     `(loss, variables, weighted_losses)`.  What changes: the two rasteriser calls of 205-211 (RGB, then depth / silhouette /
     depth^2 on the same Gaussians) are ONE projection / binning / sort with two compositing passes and one fused backward
@@ -68,7 +93,11 @@ def make_get_loss(transform_to_frame, calc_loss, fused_rendervar=False):
     stretch between `params` and the rasteriser -- transform_to_frame, the depth / silhouette features and the activations -- is one
     launch forward and one backward, two with the camera's gradient (`frame_render_vars`, fr_rendervar_forward / _backward), instead
     of the torch chain; a call whose parameters the kernels do not take (not float32, not contiguous, not on one HIP device) goes
-    the torch route, that call only."""
+    the torch route, that call only.  With `object_mask=True` the step is the object class's (models/SLAM/gaussian_object.py:236-275):
+    `curr_data['obj_mask_2d']` is ANDed into the pixel mask and the two background penalties are added to the colour term; a frame
+    without one (missing or None) gets neither.  Off by default: without it `obj_mask_2d` is not read.  With `fused_mask=True` the
+    pixel mask -- and with `object_mask` the AND and the penalties -- come from the kernels (`fisher_rast.object_loss`: fr_loss_mask,
+    fr_bg_penalty_forward / _backward) instead of the torch chain, which stays the route of a call that the kernels do not take."""
     @torch.enable_grad()
     def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_for_loss,
                  sil_thres, use_l1, ignore_outlier_depth_loss, tracking=False,
@@ -89,8 +118,24 @@ def make_get_loss(transform_to_frame, calc_loss, fused_rendervar=False):
             im, radius, depth_sil, rendervar = render_rgb_depth_sil(params, curr_data['cam'], curr_data['w2c'], rendervar['means3D'],
                                                                     rendervar=rendervar, feats=feats)
         variables['means2D'] = rendervar['means2D']      # densification reads the colour render's screen-space gradient (gaussian.py:207)
-        depth, mask = _loss_pixel_mask(depth_sil, curr_data['depth'], sil_thres, ignore_outlier_depth_loss, tracking and use_sil_for_loss)
+        need_presence = tracking and use_sil_for_loss
+        obj = _object_mask_of(curr_data, depth_sil.device) if object_mask else None
+        depth = mask = penalty = None
+        if fused_mask:
+            try:
+                depth, mask = _object_loss.loss_pixel_mask(depth_sil, curr_data['depth'], sil_thres, ignore_outlier_depth_loss, need_presence, obj)
+                if obj is not None:
+                    penalty = _object_loss.background_penalty(im, depth_sil, obj)
+            except _object_loss.ObjectLossUnsupported:
+                depth = mask = penalty = None
+        if mask is None:
+            depth, mask = _loss_pixel_mask(depth_sil, curr_data['depth'], sil_thres, ignore_outlier_depth_loss, need_presence)
+            if obj is not None:
+                mask = mask & obj.unsqueeze(0)
+                penalty = _background_penalty_torch(im, depth_sil[1], obj)
         terms = calc_loss(curr_data, im, depth, mask, mask.repeat(3, 1, 1), use_l1, use_sil_for_loss, ignore_outlier_depth_loss, tracking)
+        if penalty is not None:
+            terms['im'] = terms['im'] + penalty
         weighted = {name: value * loss_weights[name] for name, value in terms.items()}
         total = sum(weighted.values())
         update_seen_and_radius(variables, radius)        # variables['seen'], variables['max_2D_radius'] (gaussian.py:289-291)
@@ -443,13 +488,16 @@ class FisherOps:
         return scorer.run(self._as_w2c(w2cs), H_inv=H_inv_per_view, H_inv_per_view=True)["scores"]
 
     @classmethod
-    def install(cls, target_cls, patch_get_loss=False, fused_loss=False, fused_rendervar=False):
+    def install(cls, target_cls, patch_get_loss=False, fused_loss=False, fused_rendervar=False, fused_mask=False, object_mask=False):
         """Graft the accelerated methods onto the reference's class.  `patch_get_loss=True` also replaces the
         module-level `get_loss` of the module `target_cls` lives in by the fused-render form (`make_get_loss`); off by default --
         a caller that only wants the Fisher scorer keeps the reference's training step untouched.  With `fused_loss=True` as well,
         that get_loss takes its loss terms from this package's `calc_loss` (`calc_loss_mask` where the module has one: the object
         class) -- the fused L1 + SSIM kernels, no host synchronisation -- instead of the reference module's own; off by default.  With `fused_rendervar=True`
-        as well, it builds the render variables with the fused kernels (`make_get_loss(..., fused_rendervar=True)`); off by default."""
+        as well, it builds the render variables with the fused kernels (`make_get_loss(..., fused_rendervar=True)`); off by default.
+        `object_mask=True` makes that get_loss the object class's -- `curr_data['obj_mask_2d']` in the pixel mask, the two background
+        penalties in the colour term -- and `fused_mask=True` takes the pixel mask (and the object lines) from the kernels
+        (`make_get_loss(..., fused_mask=True, object_mask=True)`); both off by default, also for the object class."""
         for name in ("_device", "_as_w2c", "_stack_poses", "_scorer", "_scorer_key", "_keyframe_key", "_same_keyframes", "_PARAM_KEYS", "compute_Hessian", "compute_H_train",
                      "pose_eval", "path_scores"):
             setattr(target_cls, name, getattr(cls, name))
@@ -463,7 +511,8 @@ class FisherOps:
                 from models.SLAM.utils import slam_helpers as _sh
                 loss_fn = _sh.calc_loss_mask if hasattr(mod, "calc_loss_mask") else _sh.calc_loss
             # the keyword only when it is set: a make_get_loss wrapped by a caller with the two-argument signature keeps working
-            mod.get_loss = make_get_loss(mod.transform_to_frame, loss_fn, **(dict(fused_rendervar=True) if fused_rendervar else {}))
+            flags = dict(fused_rendervar=fused_rendervar, fused_mask=fused_mask, object_mask=object_mask)
+            mod.get_loss = make_get_loss(mod.transform_to_frame, loss_fn, **{k: True for k, v in flags.items() if v})
         if not hasattr(target_cls, "FISHER_COLUMNS"):
             target_cls.FISHER_COLUMNS = cls.FISHER_COLUMNS
         target_cls.H_TRAIN_REG = cls.H_TRAIN_REG
@@ -751,18 +800,22 @@ class MapEditOps:
     for the reference's modules: `install(target_cls)` replaces the module-level functions `prune_gaussians`, `densify` and
     `remove_points` of the module `target_cls` lives in (their `track_rgbd` and `prune_invisible` look these names up in the module),
     and nothing on the class itself.  The object-aware branch of `prune_gaussians` asks that module's own
-    `get_gaussians_outside_mask` for the outside mask.  Opt-in: nothing is installed by default."""
+    `get_gaussians_outside_mask` for the outside mask; with `outside_mask="library"` this package's
+    (models/SLAM/utils/slam_external.py: fr_outside_mask, one host read) instead.  Opt-in: nothing is installed by default."""
 
     EDIT_NAMES = ("prune_gaussians", "densify", "remove_points")
 
     @classmethod
-    def install(cls, target_cls):
+    def install(cls, target_cls, outside_mask="module"):
         import sys
         from models.SLAM.utils import slam_external as se
         mod = sys.modules.get(target_cls.__module__)
         if mod is None or not all(hasattr(mod, n) for n in cls.EDIT_NAMES):
             raise ValueError(f"MapEditOps.install: the module of {target_cls.__name__} does not define {cls.EDIT_NAMES}")
-        edit = se.MapEdit(se.HipMapEditBackend(), outside_mask_fn=getattr(mod, "get_gaussians_outside_mask", None))
+        if outside_mask not in ("module", "library"):
+            raise ValueError(f"MapEditOps.install: outside_mask is 'module' or 'library' (got {outside_mask!r})")
+        outside_fn = se.get_gaussians_outside_mask if outside_mask == "library" else getattr(mod, "get_gaussians_outside_mask", None)
+        edit = se.MapEdit(se.HipMapEditBackend(), outside_mask_fn=outside_fn)
         mod.prune_gaussians = edit.prune_gaussians
         mod.densify = edit.densify
         mod.remove_points = edit.remove_points

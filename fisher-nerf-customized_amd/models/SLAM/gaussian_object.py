@@ -186,11 +186,13 @@ class ObjectFisherOps(FisherOps):
         return torch.tensor(scores), torch.stack(c2ws)
 
     @classmethod
-    def install(cls, target_cls, patch_get_loss=False, fused_loss=False, fused_rendervar=False):
+    def install(cls, target_cls, patch_get_loss=False, fused_loss=False, fused_rendervar=False, fused_mask=False, object_mask=False):
         """Graft the 11-column Fisher methods AND the POp-GS estimators onto the reference's GaussianObjectSLAM
-        (`patch_get_loss` / `fused_loss` / `fused_rendervar`: FisherOps.install)."""
+        (`patch_get_loss` / `fused_loss` / `fused_rendervar` / `fused_mask` / `object_mask`: FisherOps.install).  `object_mask=True` is what
+        makes the patched get_loss read `curr_data['obj_mask_2d']`, as the reference's object class does; it is off by default."""
         target_cls.FISHER_COLUMNS = cls.FISHER_COLUMNS
-        super().install(target_cls, patch_get_loss=patch_get_loss, fused_loss=fused_loss, fused_rendervar=fused_rendervar)
+        super().install(target_cls, patch_get_loss=patch_get_loss, fused_loss=fused_loss, fused_rendervar=fused_rendervar,
+                        **{k: True for k, v in dict(fused_mask=fused_mask, object_mask=object_mask).items() if v})
         for name in ("_draw_probes", "_probe_rows", "_pose_probe_rows", "_flat_diag", "_diag_batch", "_diag_scores",
                      "_block_columns", "_visible_indices", "_block_scores", "estimate_diag_JtJ_simple", "compute_H_train_popgs",
                      "pose_eval_popgs", "estimate_block_JtJ", "compute_H_train_blocks", "pose_eval_popgs_blocks"):

@@ -5,6 +5,7 @@ Gaussians (fr_densify_stats / fr_densify_masks / fr_prune_mask, include/fisher_r
 `calc_ssim` / `calc_ssim_masked` (slam_external.py:89-120, 144-193) are the fused image-loss kernels (fr_image_loss_forward /
 fr_image_loss_backward through fisher_rast/image_loss.py): one forward launch pair, one backward launch, no host synchronisation.
 `calc_mse` / `calc_psnr` (slam_external.py:68-74) take a float32 [3,H,W] pair on the device through fr_view_metrics.
+`get_gaussians_outside_mask` (slam_external.py:270-343) is fr_outside_mask through fisher_rast/object_loss.py: two launches and one host read.
 
 What the reference then DOES with a mask -- cloning / splitting the parameter tensors, rebuilding the Adam state
 (cat_params_to_optimizer, remove_points, slam_external.py:203-262) and the bodies of prune_gaussians / densify (345-463) -- is the map
@@ -155,6 +156,38 @@ def calc_mse(img1, img2):
 def calc_psnr(img1, img2):
     """slam_external.py:72-74: 20 log10(1 / sqrt(mse)) per channel, [C,1]; +inf where the channels are equal."""
     return 20 * torch.log10(1.0 / torch.sqrt(calc_mse(img1, img2)))
+
+
+def get_gaussians_outside_mask(params, curr_data, obj_mask_2d, with_indices=True):
+    """slam_external.py:270-343, same arguments and return: (outside_mask bool [N], stats) for the frame `curr_data['id']` of the
+    camera trajectory in `params` -- the Gaussians that do not project into `obj_mask_2d` (those outside the image or behind the
+    camera included), the counts and the ranges of the largest scale inside and outside.  Two launches (fr_outside_mask) and ONE host
+    read, of the status block, in place of the reference's two nonzero calls and four .item() reads; `idx_in` / `idx_out` are taken
+    from the byte masks after the read, with the counts it brought (no further synchronisation).  `with_indices=False` (not in the
+    reference's signature; none of its callers reads the lists) leaves them out of `stats`."""
+    from fisher_rast import object_loss as _ol
+    from models.SLAM.gaussian import frame_w2c              # (that module imports this one)
+    outside, status = _ol.outside_mask(params, frame_w2c(params, curr_data['id']), curr_data['intrinsics'], obj_mask_2d)
+    st = status.cpu()                                        # the one host read
+    counts, ranges = st[:2].tolist(), st[2:].view(torch.float32).tolist()
+    stats = {
+        'in_count': int(counts[0]),
+        'out_count': int(counts[1]),
+        'total': int(outside.shape[0]),
+        'inside_scale_min': ranges[0],
+        'inside_scale_max': ranges[1],
+        'outside_scale_min': ranges[2],
+        'outside_scale_max': ranges[3],
+    }
+    if with_indices:
+        inside = torch.logical_not(outside)
+        if hasattr(torch, "nonzero_static"):
+            stats['idx_in'] = torch.nonzero_static(inside, size=stats['in_count']).squeeze(1)
+            stats['idx_out'] = torch.nonzero_static(outside, size=stats['out_count']).squeeze(1)
+        else:
+            stats['idx_in'] = torch.nonzero(inside, as_tuple=False).squeeze(1)
+            stats['idx_out'] = torch.nonzero(outside, as_tuple=False).squeeze(1)
+    return outside, stats
 
 
 # ---- the map edit: a prune or densify mask applied to the map, its Adam state and its statistics ---------------------------------

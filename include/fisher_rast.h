@@ -41,6 +41,9 @@
  *                           models/SLAM/utils/slam_helpers.py:23-77, models/SLAM/utils/slam_external.py:77-193
  *   fr_frame_ingest_select / fr_frame_ingest_emit <- add_new_gaussians / get_pointcloud / initialize_new_params,
  *                           models/SLAM/gaussian.py:320-414, 75-143, 299-318
+ *   fr_loss_mask / fr_bg_penalty_forward / fr_bg_penalty_backward / fr_outside_mask <- the pixel mask and the object lines of get_loss,
+ *                           models/SLAM/gaussian.py:212-233, models/SLAM/gaussian_object.py:213-275, and get_gaussians_outside_mask,
+ *                           models/SLAM/utils/slam_external.py:270-343
  *   fr_map_edit_plan / fr_map_edit_apply / fr_map_edit_split_children <- remove_points / cat_params_to_optimizer and the split
  *                           children of densify, models/SLAM/utils/slam_external.py:218-262, 411-463 over 25-42
  *   fr_adam_step         <- optimizer.step() of the torch.optim.Adam that get_optimizer builds (seven groups of one tensor),
@@ -498,6 +501,73 @@ int fr_frame_ingest_emit(const fr_frame_ingest_cfg* cfg, const float* color, con
                          const void* workspace, int32_t count, int64_t row_offset,
                          float* means3D, float* rgb_colors, float* unnorm_rotations, float* logit_opacities,
                          float* log_scales, float* mean3_sq_dist, fr_stream_t stream);
+
+/* ---- object-aware training step: loss pixel mask, background penalties, outside mask -----------------------------------
+ * In place of the stretch between the render and the loss terms of get_loss (models/SLAM/gaussian.py:212-233 and, with the object
+ * lines, models/SLAM/gaussian_object.py:213-275) and of get_gaussians_outside_mask (models/SLAM/utils/slam_external.py:270-343).
+ * Nothing is read back to the host and nothing is allocated inside; integer sums and fp64 sums in a fixed order only (the same
+ * call gives the same bits).  Object masks are device bytes [H,W], non-zero = object.
+ *
+ * fr_loss_mask -- the pixels that enter the loss, exactly the reference's:
+ *       keep = gt > 0
+ *       reject_outliers:  err = |gt - d| * (gt > 0);  keep &= err < outlier_ratio * median(err)      (strict; the product in binary32)
+ *       keep &= !isnan(d) & !isnan(d2 - d * d)                                                      (two roundings: inf - inf is NaN)
+ *       need_presence:    keep &= sil > sil_thres                                                   (strict, binary32)
+ *       obj_mask:         keep &= obj != 0
+ *   with the exact lower median of the H W errors (element (n - 1) / 2 of the sorted values; NaN as soon as one error is NaN,
+ *   torch.median's rule), found by a radix select: four histogram launches in front of the mask launch.  Without reject_outliers
+ *   the call is one launch and takes no workspace. */
+#define FR_LOSS_MASK_STATUS_WORDS 5
+typedef struct {
+	int32_t H, W;
+	float sil_thres;                  /* read with need_presence */
+	int32_t reject_outliers;          /* 0 / 1: ignore_outlier_depth_loss */
+	float outlier_ratio;              /* read with reject_outliers: the reference's 10 */
+	int32_t need_presence;            /* 0 / 1: tracking and use_sil_for_loss */
+} fr_loss_mask_cfg;
+
+/* Host-only query (0 for a bad argument): the histograms of the radix select. */
+size_t fr_loss_mask_workspace_bytes(int32_t H, int32_t W);
+/* depth_sil: [3,H,W] rendered depth, silhouette, depth^2; gt_depth: [1,H,W]; obj_mask: bytes [H,W] or null (none).  mask: bytes
+ * [H,W], 0 or 1, every element written once (a torch bool view of it costs nothing).  status: FR_LOSS_MASK_STATUS_WORDS device
+ * int32 = {pixels kept, median is NaN, background pixels (obj_mask == 0; 0 without one), 0, the median's bits (0x7fc00000 when
+ * NaN; 0 without reject_outliers)}.  workspace (fr_loss_mask_workspace_bytes, 8-byte aligned): with reject_outliers only, may be
+ * null otherwise. */
+int fr_loss_mask(const fr_loss_mask_cfg* cfg, const float* depth_sil, const float* gt_depth, const uint8_t* obj_mask,
+                 uint8_t* mask, int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+
+/* fr_bg_penalty_forward / _backward -- the two background penalties of gaussian_object.py:263-275.  With bg = (obj_mask == 0) and
+ * n = count(bg):   L_rgb = sum_{c,p} (|im| * bg) / max(3 n, 1),   L_alpha = sum_p (clamp(sil, 0, 1) * bg) / max(n, 1),
+ * the products in binary32 as the reference takes them (a non-finite im anywhere makes L_rgb NaN, a NaN silhouette L_alpha; an
+ * infinite one clamps to 1), the sums in fp64: per-workgroup partials added in a fixed order, as fr_image_loss_forward does.
+ * im: [3,H,W]; depth_sil: [3,H,W], channel 1 is read.  Two launches forward, one backward. */
+size_t fr_bg_penalty_workspace_bytes(int32_t H, int32_t W);
+/* out4 = {fl(lambda_rgb L_rgb) + fl(lambda_alpha L_alpha), L_rgb, L_alpha, n}; saved2: the two denominators, which
+ * fr_bg_penalty_backward reads.  workspace: fr_bg_penalty_workspace_bytes, 8-byte aligned. */
+int fr_bg_penalty_forward(int32_t H, int32_t W, float lambda_rgb, float lambda_alpha, const float* im, const float* depth_sil,
+                          const uint8_t* obj_mask, float* out4, float* saved2, void* workspace, size_t workspace_bytes,
+                          fr_stream_t stream);
+/* dL_dim [3,H,W] = fl(fl(up lambda_rgb) / max(3 n, 1)) * bg * sign(im), sign(+-0) = sign(NaN) = 0; dL_ddepth_sil [3,H,W]: channel 1 =
+ * fl(fl(up lambda_alpha) / max(n, 1)) * bg where 0 <= sil <= 1 (both ends included; 0 elsewhere and at NaN), channels 0 and 2 exact
+ * zeros.  These are torch autograd's own values, bit for bit; every element is written once.  upstream: DEVICE float (autograd's
+ * 0-dim gradient), read by the kernel. */
+int fr_bg_penalty_backward(int32_t H, int32_t W, float lambda_rgb, float lambda_alpha, const float* im, const float* depth_sil,
+                           const uint8_t* obj_mask, const float* saved2, const float* upstream, float* dL_dim,
+                           float* dL_ddepth_sil, fr_stream_t stream);
+
+/* fr_outside_mask -- which Gaussians do not project into the object mask (slam_external.py:290-315).  Per Gaussian: the camera
+ * point ((r0 x + r1 y) + r2 z) + t per row of w2c, the homogeneous pixel (k_i0 X + k_i1 Y) + k_i2 Z, u = p0 / max(p2, 1e-6), v
+ * likewise; in_img = Z > 0 & 0 <= u < W & 0 <= v < H; the pixel looked up is (clamp(rint(u), 0, W - 1), clamp(rint(v), 0, H - 1)),
+ * round half to even; outside = !(in_img & obj_mask[iv, iu]).  means3D: [P,3]; log_scales: [P,scale_cols], 1 or 3; w2c ([4,4]) and
+ * intrinsics ([3,3]): DEVICE float32, row-major.  outside: bytes [P], 0 or 1.  status: FR_OUTSIDE_STATUS_WORDS device int32 =
+ * {in_count, out_count, the bits of min and of max over the inside Gaussians of max_k exp(log_scales), the same two over the outside
+ * ones}; a range over an empty set or over a set that holds a NaN scale is NaN (0x7fc00000).  Minima and maxima are taken on integer
+ * keys of the log scales and exp of the four extremes alone, through binary64.  Two launches; P = 0 is fine (one). */
+#define FR_OUTSIDE_STATUS_WORDS 6
+size_t fr_outside_mask_workspace_bytes(int32_t P);
+int fr_outside_mask(int32_t P, int32_t scale_cols, const float* means3D, const float* log_scales, const float* w2c,
+                    const float* intrinsics, const uint8_t* obj_mask, int32_t H, int32_t W, uint8_t* outside, int32_t* status,
+                    void* workspace, size_t workspace_bytes, fr_stream_t stream);
 
 /* ---- map edit: a prune or densify mask applied to the map, its Adam state and its statistics --------------------------
  * In place of remove_points / cat_params_to_optimizer and the clone / split of densify (models/SLAM/utils/slam_external.py:218-262,
