@@ -85,12 +85,6 @@ __global__ __launch_bounds__(FRA_THREADS) void k_adam_step(FraArgs a)
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
-static bool fra_overlap(const void* a, const void* b, uint64_t n_a, uint64_t n_b)
-{
-	const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-	return n_a && n_b && a0 < b0 + n_b * 4 && b0 < a0 + n_a * 4;
-}
-
 extern "C" int fr_adam_step(const fr_adam_array* table, int32_t n_arrays, fr_stream_t stream)
 {
 	if (n_arrays < 0 || n_arrays > FR_ADAM_MAX_ARRAYS) return fr_fail(FR_EINVAL, "fr_adam_step: bad argument (n_arrays is 0 .. FR_ADAM_MAX_ARRAYS)");
@@ -114,7 +108,7 @@ extern "C" int fr_adam_step(const fr_adam_array* table, int32_t n_arrays, fr_str
 			{
 				const void* other[4] = {table[j].param, table[j].exp_avg, table[j].exp_avg_sq, table[j].grad};
 				for (int o = 0; o < 4; o++)
-					if (!(j == i && o == w) && fra_overlap(written[w], other[o], (uint64_t)table[i].n, (uint64_t)table[j].n))
+					if (!(j == i && o == w) && fr_overlap(written[w], (size_t)table[i].n * 4, other[o], (size_t)table[j].n * 4))
 						return fr_fail(FR_EINVAL, "fr_adam_step: bad argument (a param, exp_avg or exp_avg_sq range overlaps another range of the table)");
 			}
 	}

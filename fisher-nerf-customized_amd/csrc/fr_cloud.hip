@@ -4,7 +4,8 @@
 // (scripts/eval_3d_reconstruction.py:84-125: three trees, three queries) and novelty_mask_from_pcd_nn (test_utils.py:503-578: a
 // tree over the unchanging environment cloud, every frame).  Here the index is built once and outlives the call:
 //
-//   fr_cloud_index_build   k_cloud_minmax   bounding box and count of the FINITE targets (integer atomics on encoded floats)
+//   fr_cloud_index_build   k_cloud_minmax   bounding box and count of the FINITE targets (fr_block.h's frb_minmax3_finite, then
+//                                           integer atomics on encoded floats)
 //                          k_cloud_tkeys    Morton code << 32 | original index; a non-finite target gets FRC_NO_CODE and sorts last
 //                          fr_sort_keys64   the 64-bit key sort of the Morton sort (fisher_rast.hip)
 //                          k_cloud_gather   the sorted coordinates
@@ -27,9 +28,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fr_internal.h"
+#include "fr_block.h"
 #include "fr_cloud_math.h"
 
 #define FRC_THREADS 256
+static_assert(FRC_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 #define FRC_BOX 1024
 #define FRC_SUB 64
 #define FRC_SUPER 16                  // boxes per super-box: the level above the 1024-point boxes (16384 points)
@@ -44,17 +47,16 @@ struct FrcHead
 };
 
 struct FrcIndexLayout { size_t head, keys, sorted, boxes, sboxes, supers, total; };
-static size_t frc_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static FrcIndexLayout frc_index_layout(int64_t N)
 {
 	FrcIndexLayout L;
 	size_t o = 0;
-	L.head = o; o = frc_align(o + sizeof(FrcHead));
-	L.keys = o; o = frc_align(o + (size_t)N * 8);
-	L.sorted = o; o = frc_align(o + (size_t)N * 12);
-	L.boxes = o; o = frc_align(o + (size_t)((N + FRC_BOX - 1) / FRC_BOX) * 24);
-	L.sboxes = o; o = frc_align(o + (size_t)((N + FRC_SUB - 1) / FRC_SUB) * 24);
-	L.supers = o; o = frc_align(o + (size_t)((N + FRC_SUPER * FRC_BOX - 1) / (FRC_SUPER * FRC_BOX)) * 24);
+	L.head = o; o = fr_align256(o + sizeof(FrcHead));
+	L.keys = o; o = fr_align256(o + (size_t)N * 8);
+	L.sorted = o; o = fr_align256(o + (size_t)N * 12);
+	L.boxes = o; o = fr_align256(o + (size_t)((N + FRC_BOX - 1) / FRC_BOX) * 24);
+	L.sboxes = o; o = fr_align256(o + (size_t)((N + FRC_SUB - 1) / FRC_SUB) * 24);
+	L.supers = o; o = fr_align256(o + (size_t)((N + FRC_SUPER * FRC_BOX - 1) / (FRC_SUPER * FRC_BOX)) * 24);
 	L.total = o;
 	return L;
 }
@@ -65,9 +67,9 @@ static FrcQueryLayout frc_query_layout(int64_t M)
 {
 	FrcQueryLayout L;
 	size_t o = 0;
-	L.qkeys = o; o = frc_align(o + (size_t)M * 8);
-	L.dist = o; o = frc_align(o + (size_t)M * 4);
-	L.partials = o; o = frc_align(o + (size_t)frc_blocks(M) * 32 + 32);
+	L.qkeys = o; o = fr_align256(o + (size_t)M * 8);
+	L.dist = o; o = fr_align256(o + (size_t)M * 4);
+	L.partials = o; o = fr_align256(o + (size_t)frc_blocks(M) * 32 + 32);
 	L.total = o;
 	return L;
 }
@@ -90,36 +92,13 @@ __global__ __launch_bounds__(FRC_THREADS) void k_cloud_minmax(int N, const float
 {
 	__shared__ float s_lo[3][4], s_hi[3][4];
 	__shared__ uint32_t s_cnt[4];
-	float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-	uint32_t cnt = 0;
-	for (int i = blockIdx.x * FRC_THREADS + threadIdx.x; i < N; i += gridDim.x * FRC_THREADS)
-	{
-		const float x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
-		if (!frc_finite3(x, y, z)) continue;                 // must not widen the frame
-		lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
-		lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
-		lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
-		cnt++;
-	}
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1)
-	{
-#pragma unroll
-		for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64)); }
-		cnt += __shfl_xor(cnt, o, 64);
-	}
-	if ((threadIdx.x & 63) == 0)
-	{
-		for (int a = 0; a < 3; a++) { s_lo[a][threadIdx.x >> 6] = lo[a]; s_hi[a][threadIdx.x >> 6] = hi[a]; }
-		s_cnt[threadIdx.x >> 6] = cnt;
-	}
-	__syncthreads();
+	frb_minmax3_finite(pts, N, [](float x, float y, float z) { return frc_finite3(x, y, z); }, s_lo, s_hi, s_cnt);
 	// one set of integer atomics per workgroup: their result does not depend on the order of arrival
 	if (threadIdx.x < 3)
 	{
 		const int a = threadIdx.x;
-		atomicMin(&acc[a], frc_enc(fminf(fminf(s_lo[a][0], s_lo[a][1]), fminf(s_lo[a][2], s_lo[a][3]))));
-		atomicMax(&acc[3 + a], frc_enc(fmaxf(fmaxf(s_hi[a][0], s_hi[a][1]), fmaxf(s_hi[a][2], s_hi[a][3]))));
+		atomicMin(&acc[a], frc_enc(frb_min4(s_lo[a])));
+		atomicMax(&acc[3 + a], frc_enc(frb_max4(s_hi[a])));
 	}
 	if (threadIdx.x == 3) atomicAdd(&acc[6], s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
 }
@@ -440,7 +419,6 @@ __global__ __launch_bounds__(FRC_THREADS) void k_cloud_total(int nblk, const Frc
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------------------------
 
-static bool frc_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 extern "C" size_t fr_cloud_index_bytes(int32_t N)
 {
@@ -465,7 +443,7 @@ extern "C" int fr_cloud_index_build(int32_t N, const float* points, void* index,
 {
 	if (N < 0 || N > FR_CLOUD_MAX_POINTS) return fr_fail(FR_EINVAL, "fr_cloud_index_build: N outside [0, FR_CLOUD_MAX_POINTS]");
 	if (!index || !workspace || (N > 0 && !points)) return fr_fail(FR_EINVAL, "fr_cloud_index_build: null pointer");
-	if (!frc_aligned(points, 4) || !frc_aligned(index, 8) || !frc_aligned(workspace, 8))
+	if (!fr_aligned(points, 4) || !fr_aligned(index, 8) || !fr_aligned(workspace, 8))
 		return fr_fail(FR_EINVAL, "fr_cloud_index_build: misaligned pointer (points 4, index and workspace 8 bytes)");
 	const FrcIndexLayout L = frc_index_layout(N);
 	if (index_bytes < L.total) return fr_fail(FR_EINVAL, "fr_cloud_index_build: index smaller than fr_cloud_index_bytes()");
@@ -518,7 +496,7 @@ extern "C" int fr_cloud_query(const void* index, size_t index_bytes, int32_t N, 
 		if (cfg->H <= 0 || cfg->W <= 0 || cfg->stride <= 0) return fr_fail(FR_EINVAL, "fr_cloud_query: H, W and stride must be positive");
 		if ((int64_t)cfg->H * cfg->W > FR_CLOUD_MAX_POINTS) return fr_fail(FR_EINVAL, "fr_cloud_query: H W beyond FR_CLOUD_MAX_POINTS");
 		if (!cfg->depth || !cfg->kinv || !cfg->c2w) return fr_fail(FR_EINVAL, "fr_cloud_query: null depth, kinv or c2w");
-		if (!frc_aligned(cfg->depth, 4) || !frc_aligned(cfg->kinv, 4) || !frc_aligned(cfg->c2w, 4))
+		if (!fr_aligned(cfg->depth, 4) || !fr_aligned(cfg->kinv, 4) || !fr_aligned(cfg->c2w, 4))
 			return fr_fail(FR_EINVAL, "fr_cloud_query: misaligned depth, kinv or c2w");
 		p.H = cfg->H; p.W = cfg->W; p.stride = cfg->stride; p.flip_z = cfg->flip_z != 0;
 		p.Hs = (cfg->H + cfg->stride - 1) / cfg->stride; p.Ws = (cfg->W + cfg->stride - 1) / cfg->stride;
@@ -529,10 +507,10 @@ extern "C" int fr_cloud_query(const void* index, size_t index_bytes, int32_t N, 
 		M = cfg->M;
 		if (M < 0 || M > FR_CLOUD_MAX_POINTS) return fr_fail(FR_EINVAL, "fr_cloud_query: M outside [0, FR_CLOUD_MAX_POINTS]");
 		if (M > 0 && !cfg->queries) return fr_fail(FR_EINVAL, "fr_cloud_query: null queries");
-		if (!frc_aligned(cfg->queries, 4)) return fr_fail(FR_EINVAL, "fr_cloud_query: misaligned queries");
+		if (!fr_aligned(cfg->queries, 4)) return fr_fail(FR_EINVAL, "fr_cloud_query: misaligned queries");
 	}
-	if (!frc_aligned(index, 8) || !frc_aligned(workspace, 8) || !frc_aligned(cfg->out_dist, 4) || !frc_aligned(cfg->out_idx, 4) ||
-	    !frc_aligned(cfg->out_stats, 8))
+	if (!fr_aligned(index, 8) || !fr_aligned(workspace, 8) || !fr_aligned(cfg->out_dist, 4) || !fr_aligned(cfg->out_idx, 4) ||
+	    !fr_aligned(cfg->out_stats, 8))
 		return fr_fail(FR_EINVAL, "fr_cloud_query: misaligned pointer (index, workspace and out_stats 8, out_dist and out_idx 4 bytes)");
 	const FrcQueryLayout Q = frc_query_layout(M);
 	if (workspace_bytes < Q.total) return fr_fail(FR_EINVAL, "fr_cloud_query: workspace smaller than fr_cloud_query_workspace_bytes()");

@@ -25,19 +25,22 @@
 // Counts that a later kernel needs stay on the device (the status block): grids are sized for the capacity and threads beyond the
 // count return.  Workgroups never wait for each other: what one launch hands to the next goes through the kernel boundary.  Nothing
 // is allocated, nothing is read back, no environment variable is read, no float atomics; every launch and memset is on the caller's stream.
+// The scan, the ballot count / rank, the radix select and the min / max / count of the finite points are fr_block.h's; the order key
+// frk_enc (-0 taken as +0) and the xor trees of the key maxima are this unit's own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fr_internal.h"
+#include "fr_block.h"
 #include "fr_cluster_math.h"
 
 #define FRK_THREADS 256
+static_assert(FRK_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 #define FRK_MAX_GRID 2048
 #define FRK_HIST_ITEMS 8                                   // scores per thread of a histogram workgroup
 
 // status words of fr_target_select (include/fisher_rast.h)
 enum { ST_BAND = 0, ST_ABOVE, ST_CLUSTERS, ST_MAXLABEL, ST_SELECTED, ST_ARGMAX, ST_SIDE, ST_NAN = 9, ST_THRESHOLD, ST_FINITE };
 
-static size_t frk_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static int frk_blocks(int64_t n) { return (int)((n + FRK_THREADS - 1) / FRK_THREADS); }
 
 // ---- DBSCAN -------------------------------------------------------------------------------------------------------------------------
@@ -70,16 +73,16 @@ static FrkDbLayout frk_db_layout(int64_t cap)
 	FrkDbLayout L;
 	size_t o = 0;
 	const size_t nwg = (size_t)frk_blocks(cap);
-	L.acc = o; o = frk_align(o + 64);
-	L.keys = o; o = frk_align(o + (size_t)cap * 8);
-	L.sorted = o; o = frk_align(o + (size_t)cap * 16);
-	L.parent = o; o = frk_align(o + (size_t)cap * 4);
-	L.comp = o; o = frk_align(o + (size_t)cap * 4);
-	L.rank = o; o = frk_align(o + (size_t)cap * 4);
-	L.core = o; o = frk_align(o + (size_t)cap);
-	L.coreo = o; o = frk_align(o + (size_t)cap);
-	L.counts = o; o = frk_align(o + nwg * 4);
-	L.offsets = o; o = frk_align(o + nwg * 4);
+	L.acc = o; o = fr_align256(o + 64);
+	L.keys = o; o = fr_align256(o + (size_t)cap * 8);
+	L.sorted = o; o = fr_align256(o + (size_t)cap * 16);
+	L.parent = o; o = fr_align256(o + (size_t)cap * 4);
+	L.comp = o; o = fr_align256(o + (size_t)cap * 4);
+	L.rank = o; o = fr_align256(o + (size_t)cap * 4);
+	L.core = o; o = fr_align256(o + (size_t)cap);
+	L.coreo = o; o = fr_align256(o + (size_t)cap);
+	L.counts = o; o = fr_align256(o + nwg * 4);
+	L.offsets = o; o = fr_align256(o + nwg * 4);
 	L.total = o;
 	return L;
 }
@@ -107,37 +110,13 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_minmax(FrkDb a)
 {
 	__shared__ float s_lo[3][4], s_hi[3][4];
 	__shared__ uint32_t s_cnt[4];
-	const int n = frk_n(a);
-	float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-	uint32_t cnt = 0;
-	for (int i = blockIdx.x * FRK_THREADS + threadIdx.x; i < n; i += gridDim.x * FRK_THREADS)
-	{
-		const float x = a.pts[3 * (size_t)i], y = a.pts[3 * (size_t)i + 1], z = a.pts[3 * (size_t)i + 2];
-		if (!frk_finite3(x, y, z)) continue;                 // must not widen the frame
-		lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
-		lo[1] = fminf(lo[1], y); hi[1] = fmaxf(hi[1], y);
-		lo[2] = fminf(lo[2], z); hi[2] = fmaxf(hi[2], z);
-		cnt++;
-	}
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1)
-	{
-#pragma unroll
-		for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], o, 64)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], o, 64)); }
-		cnt += __shfl_xor(cnt, o, 64);
-	}
-	if ((threadIdx.x & 63) == 0)
-	{
-		for (int k = 0; k < 3; k++) { s_lo[k][threadIdx.x >> 6] = lo[k]; s_hi[k][threadIdx.x >> 6] = hi[k]; }
-		s_cnt[threadIdx.x >> 6] = cnt;
-	}
-	__syncthreads();
+	frb_minmax3_finite(a.pts, frk_n(a), [](float x, float y, float z) { return frk_finite3(x, y, z); }, s_lo, s_hi, s_cnt);
 	// one set of integer atomics per workgroup: their result does not depend on the order of arrival
 	if (threadIdx.x < 3)
 	{
 		const int k = threadIdx.x;
-		atomicMin(&a.acc[k], frk_enc(fminf(fminf(s_lo[k][0], s_lo[k][1]), fminf(s_lo[k][2], s_lo[k][3]))));
-		atomicMax(&a.acc[3 + k], frk_enc(fmaxf(fmaxf(s_hi[k][0], s_hi[k][1]), fmaxf(s_hi[k][2], s_hi[k][3]))));
+		atomicMin(&a.acc[k], frk_enc(frb_min4(s_lo[k])));
+		atomicMax(&a.acc[3 + k], frk_enc(frb_max4(s_hi[k])));
 	}
 	if (threadIdx.x == 3) atomicAdd(&a.acc[6], s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
 }
@@ -260,26 +239,6 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_union(FrkDb a)
 	});
 }
 
-// number of set predicates in the workgroup, for thread 0 (s_wave[4] is scratch)
-__device__ __forceinline__ uint32_t frk_block_count(bool sel, uint32_t* s_wave)
-{
-	const unsigned long long ballot = __ballot(sel);
-	if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = (uint32_t)__popcll(ballot);
-	__syncthreads();
-	return ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-}
-// number of set predicates in front of this thread in the workgroup
-__device__ __forceinline__ uint32_t frk_block_prefix(bool sel, uint32_t* s_wave)
-{
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const unsigned long long ballot = __ballot(sel);
-	if (lane == 0) s_wave[wave] = (uint32_t)__popcll(ballot);
-	__syncthreads();
-	uint32_t before = (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-	for (int w = 0; w < wave; w++) before += s_wave[w];
-	return before;
-}
-
 __global__ __launch_bounds__(FRK_THREADS) void k_cluster_flatten(FrkDb a)
 {
 	__shared__ uint32_t s_wave[4];
@@ -298,28 +257,8 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_flatten(FrkDb a)
 		a.comp[i] = r;
 		root = r == i;
 	}
-	const uint32_t c = frk_block_count(root, s_wave);
+	const uint32_t c = frb_count256(root, s_wave);
 	if (threadIdx.x == 0) a.counts[blockIdx.x] = c;
-}
-
-// inclusive scan of one value per thread over the 256 threads of the workgroup; s_wave[4] is scratch (free again on return)
-__device__ __forceinline__ uint32_t frk_scan256(uint32_t c, uint32_t* s_wave, uint32_t& total)
-{
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t incl = c;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1)
-	{
-		const uint32_t v = __shfl_up(incl, o, 64);
-		if (lane >= o) incl += v;
-	}
-	if (lane == 63) s_wave[wave] = incl;
-	__syncthreads();
-	uint32_t base = 0;
-	for (int w = 0; w < wave; w++) base += s_wave[w];
-	total = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-	__syncthreads();
-	return incl + base;
 }
 
 // one workgroup: exclusive scan of the per-workgroup counts, the total into *out_total
@@ -327,18 +266,8 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_scan(const uint32_t* __
                                                               int32_t* __restrict__ out_total)
 {
 	__shared__ uint32_t s_wave[4];
-	const int tid = threadIdx.x;
-	uint32_t carry = 0u;
-	for (int base = 0; base < nwg; base += FRK_THREADS)
-	{
-		const int i = base + tid;
-		const uint32_t c = i < nwg ? counts[i] : 0u;
-		uint32_t total;
-		const uint32_t incl = frk_scan256(c, s_wave, total);
-		if (i < nwg) offsets[i] = carry + (incl - c);
-		carry += total;
-	}
-	if (tid == 0) *out_total = (int32_t)carry;
+	const uint32_t total = frb_scan_counts(counts, offsets, nwg, s_wave);
+	if (threadIdx.x == 0) *out_total = (int32_t)total;
 }
 
 __global__ __launch_bounds__(FRK_THREADS) void k_cluster_rank(FrkDb a)
@@ -346,7 +275,7 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_rank(FrkDb a)
 	__shared__ uint32_t s_wave[4];
 	const int i = blockIdx.x * FRK_THREADS + threadIdx.x;
 	const bool root = i < frk_n(a) && a.comp[i] == i;
-	const uint32_t before = frk_block_prefix(root, s_wave);
+	const uint32_t before = frb_rank256(root, s_wave);
 	if (root) a.rank[i] = (int32_t)(a.offsets[blockIdx.x] + before);
 }
 
@@ -452,13 +381,13 @@ static FrkSelLayout frk_sel_layout(int64_t P)
 	FrkSelLayout L;
 	size_t o = 0;
 	const size_t nwg = (size_t)frk_blocks(P);
-	L.head = o; o = frk_align(o + FRK_HEAD_BYTES);
-	L.bscore = o; o = frk_align(o + (size_t)P * 4);
-	L.ascore = o; o = frk_align(o + (size_t)P * 4);
-	L.pts = o; o = frk_align(o + (size_t)P * 12);
-	L.cmax = o; o = frk_align(o + (size_t)P * 4);
-	L.counts = o; o = frk_align(o + nwg * 4);
-	L.offsets = o; o = frk_align(o + nwg * 4);
+	L.head = o; o = fr_align256(o + FRK_HEAD_BYTES);
+	L.bscore = o; o = fr_align256(o + (size_t)P * 4);
+	L.ascore = o; o = fr_align256(o + (size_t)P * 4);
+	L.pts = o; o = fr_align256(o + (size_t)P * 12);
+	L.cmax = o; o = fr_align256(o + (size_t)P * 4);
+	L.counts = o; o = fr_align256(o + nwg * 4);
+	L.offsets = o; o = fr_align256(o + nwg * 4);
 	L.db = o; o = o + frk_db_layout(P).total;
 	L.total = o;
 	return L;
@@ -500,7 +429,7 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_count(FrkSel a)
 		if ((threadIdx.x & 63) == 0 && key) atomicMax(a.argmax, key);
 		if (__ballot(nan) && (threadIdx.x & 63) == 0) atomicOr((unsigned int*)&a.status[ST_NAN], 1u);
 	}
-	const uint32_t c = frk_block_count(sel, s_wave);
+	const uint32_t c = frb_count256(sel, s_wave);
 	if (threadIdx.x == 0) a.counts[blockIdx.x] = c;
 }
 
@@ -510,7 +439,7 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_scatter(FrkSel a)
 	__shared__ uint32_t s_wave[4];
 	const int j = blockIdx.x * FRK_THREADS + threadIdx.x;
 	const bool sel = frk_selected<MODE>(a, j);
-	const uint32_t slot = a.offsets[blockIdx.x] + frk_block_prefix(sel, s_wave);
+	const uint32_t slot = a.offsets[blockIdx.x] + frb_rank256(sel, s_wave);
 	if (!sel || slot >= (uint32_t)a.P) return;                // (always inside: at most P rows are selected)
 	if (MODE == 0)
 	{
@@ -529,33 +458,6 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_scatter(FrkSel a)
 	else a.sel_idx[slot] = a.above_idx[j];
 }
 
-// the bucket of histogram h that holds rank k, for every thread; k becomes the rank inside that bucket and `inside` the number of
-// values in it
-__device__ __forceinline__ uint32_t frk_pick(const uint32_t* __restrict__ h, uint32_t& k, uint32_t& inside, uint32_t* s_wave, uint32_t* s_out)
-{
-	const int tid = threadIdx.x;
-	const uint32_t c = h[tid];
-	uint32_t total;
-	const uint32_t incl = frk_scan256(c, s_wave, total);
-	if (tid == 0) { s_out[0] = 255u; s_out[1] = 0u; s_out[2] = 0u; }      // rank k lies past the counted values: the result is not used
-	__syncthreads();
-	if (incl > k && incl - c <= k) { s_out[0] = (uint32_t)tid; s_out[1] = k - (incl - c); s_out[2] = c; }
-	__syncthreads();
-	const uint32_t bucket = s_out[0];
-	k = s_out[1];
-	inside = s_out[2];
-	__syncthreads();
-	return bucket;
-}
-
-// the prefix that the first `passes` histograms fix for rank k; k becomes the rank left inside it, `inside` the values that share it
-__device__ __forceinline__ uint32_t frk_prefix(const uint32_t* hist, int passes, uint32_t& k, uint32_t& inside, uint32_t* s_wave, uint32_t* s_out)
-{
-	uint32_t prefix = 0u;
-	for (int p = 0; p < passes; p++) prefix = (prefix << 8) | frk_pick(hist + 256 * p, k, inside, s_wave, s_out);
-	return prefix;
-}
-
 template <int PASS>
 __global__ __launch_bounds__(FRK_THREADS) void k_cluster_hist(FrkSel a)
 {
@@ -569,19 +471,17 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_hist(FrkSel a)
 	float w;
 	frk_quantile_rank(a.q, n, &below, &above, &w);
 	k = below;
-	const uint32_t prefix = frk_prefix(a.hist, PASS, k, inside, s_wave, s_out);
+	const uint32_t prefix = frb_select_prefix(a.hist, PASS, k, inside, s_wave, s_out);
 	__syncthreads();
-	constexpr int shift = 24 - 8 * PASS;
 #pragma unroll
 	for (int i = 0; i < FRK_HIST_ITEMS; i++)
 	{
 		const uint32_t j = base + (uint32_t)(i * FRK_THREADS + tid);
 		if (j >= n) continue;
-		const uint32_t u = a.bscore[j];
-		if (PASS == 0 || (u >> ((shift + 8) & 31)) == prefix) atomicAdd(&s_hist[(u >> shift) & 255u], 1u);
+		frb_select_count<PASS>(s_hist, a.bscore[j], prefix);
 	}
 	__syncthreads();
-	if (s_hist[tid]) atomicAdd(&a.hist[256 * PASS + tid], s_hist[tid]);
+	frb_select_flush<PASS>(a.hist, s_hist);
 }
 
 // the smallest encoded band score above the lower order statistic (left at 0xFFFFFFFF when there is none)
@@ -595,7 +495,7 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_next(FrkSel a)
 	float w;
 	frk_quantile_rank(a.q, n, &below, &above, &w);
 	k = below;
-	const uint32_t v = frk_prefix(a.hist, 4, k, inside, s_wave, s_out);
+	const uint32_t v = frb_select_prefix(a.hist, 4, k, inside, s_wave, s_out);
 	uint32_t best = 0xFFFFFFFFu;
 #pragma unroll
 	for (int i = 0; i < FRK_HIST_ITEMS; i++)
@@ -626,7 +526,7 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_threshold(FrkSel a)
 		float w;
 		frk_quantile_rank(a.q, n, &below, &above, &w);
 		k = below;
-		const uint32_t v = frk_prefix(a.hist, 4, k, inside, s_wave, s_out);
+		const uint32_t v = frb_select_prefix(a.hist, 4, k, inside, s_wave, s_out);
 		// `inside` values equal v, this one being number k of them: the next order statistic is v again unless this is the last
 		const uint32_t v_above = (above == below || k + 1u < inside) ? v : *a.next;
 		thr = frk_lerp(frk_dec(v), frk_dec(v_above), w);
@@ -677,8 +577,6 @@ __global__ __launch_bounds__(FRK_THREADS) void k_cluster_winner(FrkSel a)
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------------------------
 
-static bool frk_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 extern "C" size_t fr_dbscan_workspace_bytes(int32_t N)
 {
 	if (N < 0 || N > FR_CLUSTER_MAX_POINTS) return 0;
@@ -698,7 +596,7 @@ extern "C" int fr_dbscan(int32_t N, const float* points, float eps, int32_t min_
 	if (!frk_eps_ok(eps)) return fr_fail(FR_EINVAL, "fr_dbscan: eps must be positive with a normal, finite square");
 	if (min_samples < 1) return fr_fail(FR_EINVAL, "fr_dbscan: min_samples must be at least 1");
 	if (!status || !workspace || (N > 0 && (!points || !labels))) return fr_fail(FR_EINVAL, "fr_dbscan: null pointer");
-	if (!frk_aligned(points, 4) || !frk_aligned(labels, 4) || !frk_aligned(status, 4) || !frk_aligned(workspace, 8))
+	if (!fr_aligned(points, 4) || !fr_aligned(labels, 4) || !fr_aligned(status, 4) || !fr_aligned(workspace, 8))
 		return fr_fail(FR_EINVAL, "fr_dbscan: misaligned pointer (points, labels and status 4, workspace 8 bytes)");
 	if (workspace_bytes < frk_db_layout(N).total) return fr_fail(FR_EINVAL, "fr_dbscan: workspace smaller than fr_dbscan_workspace_bytes()");
 	hipStream_t s = (hipStream_t)stream;
@@ -720,9 +618,9 @@ extern "C" int fr_target_select(int32_t P, const float* means3D, const float* sc
 	if (!status || !workspace || !out_threshold) return fr_fail(FR_EINVAL, "fr_target_select: null pointer (status, workspace, out_threshold)");
 	if (P > 0 && (!means3D || !scores || !out_band_idx || !out_above_idx || !out_labels || !out_selected_idx))
 		return fr_fail(FR_EINVAL, "fr_target_select: null pointer");
-	if (!frk_aligned(means3D, 4) || !frk_aligned(scores, 4) || !frk_aligned(out_band_idx, 4) || !frk_aligned(out_above_idx, 4) ||
-	    !frk_aligned(out_labels, 4) || !frk_aligned(out_selected_idx, 4) || !frk_aligned(out_threshold, 4) || !frk_aligned(status, 4) ||
-	    !frk_aligned(workspace, 8))
+	if (!fr_aligned(means3D, 4) || !fr_aligned(scores, 4) || !fr_aligned(out_band_idx, 4) || !fr_aligned(out_above_idx, 4) ||
+	    !fr_aligned(out_labels, 4) || !fr_aligned(out_selected_idx, 4) || !fr_aligned(out_threshold, 4) || !fr_aligned(status, 4) ||
+	    !fr_aligned(workspace, 8))
 		return fr_fail(FR_EINVAL, "fr_target_select: misaligned pointer (workspace 8, everything else 4 bytes)");
 	const FrkSelLayout L = frk_sel_layout(P);
 	if (workspace_bytes < L.total) return fr_fail(FR_EINVAL, "fr_target_select: workspace smaller than fr_target_select_workspace_bytes()");

@@ -6,7 +6,7 @@
 // views is three launches and no synchronisation:
 //
 //   k_view_metrics_tiles<U8, MASKED>   grid (tiles, views) x 256 threads, a 16 x 16 pixel tile per workgroup with fr_loss.hip's
-//                                      tiling.  The workgroup does the three channels of its tile one after the other: render and
+//                                      tiling and passes (fr_ssim_tile.h).  The workgroup does the three channels of its tile one after the other: render and
 //                                      target go to LDS with a halo of 5 (zero padded; the render clamped, both times the mask),
 //                                      the horizontal 11-tap pass fills 26 rows x 16 columns x 5 moments, the vertical pass gives
 //                                      every lane its pixel's moments and frl_ssim_pixel its SSIM term; a tile with a window that
@@ -26,11 +26,11 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "fr_internal.h"
+#include "fr_block.h"
+#include "fr_ssim_tile.h"
 #include "fr_eval_math.h"
 
-#define FRE_TILE 16
-#define FRE_EXT (FRE_TILE + 2 * FRL_RADIUS)      // 26
-#define FRE_THREADS (FRE_TILE * FRE_TILE)
+static_assert(FRS_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 #define FRE_IN_IMAGE 0x80000000u                 // packed word: bytes 0..2 = the target's bytes, bit 24 = mask, bit 31 = in the image
 #define FRE_MASK_BIT 0x01000000u
 
@@ -47,24 +47,24 @@ struct FrEvalArgs {
 };
 
 template <bool U8, bool MASKED>
-__global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_tiles(FrEvalArgs a)
+__global__ __launch_bounds__(FRS_THREADS) void k_view_metrics_tiles(FrEvalArgs a)
 {
-	__shared__ float s_x[FRE_EXT * FRE_EXT], s_y[FRE_EXT * FRE_EXT];
-	__shared__ uint32_t s_pix[FRE_EXT * FRE_EXT];
-	__shared__ float s_h[5][FRE_EXT * FRE_TILE];
-	__shared__ double s_red[FRE_SUMS][FRE_THREADS / 64];
+	__shared__ float s_x[FRS_EXT * FRS_EXT], s_y[FRS_EXT * FRS_EXT];
+	__shared__ uint32_t s_pix[FRS_EXT * FRS_EXT];
+	__shared__ float s_h[5][FRS_EXT * FRS_TILE];
+	__shared__ double s_red[FRE_SUMS][FRS_THREADS / 64];
 	const int tid = threadIdx.x, v = blockIdx.y;
 	const int tile = blockIdx.x, tx = tile % a.gx, ty = tile / a.gx;
-	const int lx = tid % FRE_TILE, ly = tid / FRE_TILE;
-	const int px = tx * FRE_TILE + lx, py = ty * FRE_TILE + ly;
+	const int lx = tid % FRS_TILE, ly = tid / FRS_TILE;
+	const int px = tx * FRS_TILE + lx, py = ty * FRS_TILE + ly;
 	const bool inside = px < a.W && py < a.H;
 	const size_t hw = (size_t)a.H * a.W;
 	const float* render = a.render + (size_t)v * a.render_vs;
 
 	// what is read once per halo pixel: whether it lies in the image, its mask bit, a byte target's three bytes
-	for (int i = tid; i < FRE_EXT * FRE_EXT; i += FRE_THREADS)
+	for (int i = tid; i < FRS_EXT * FRS_EXT; i += FRS_THREADS)
 	{
-		const int gy = ty * FRE_TILE - FRL_RADIUS + i / FRE_EXT, gx = tx * FRE_TILE - FRL_RADIUS + i % FRE_EXT;
+		const int gy = ty * FRS_TILE - FRL_RADIUS + i / FRS_EXT, gx = tx * FRS_TILE - FRL_RADIUS + i % FRS_EXT;
 		uint32_t w = 0;
 		if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)
 		{
@@ -87,13 +87,13 @@ __global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_tiles(FrEvalArgs a
 	for (int c = 0; c < 3; c++)
 	{
 		__syncthreads();                  // s_pix is written; the previous channel's tiles and moments have been read
-		for (int i = tid; i < FRE_EXT * FRE_EXT; i += FRE_THREADS)
+		for (int i = tid; i < FRS_EXT * FRS_EXT; i += FRS_THREADS)
 		{
 			const uint32_t w = s_pix[i];
 			float xv = 0.0f, yv = 0.0f;
 			if (w & FRE_IN_IMAGE)
 			{
-				const int gy = ty * FRE_TILE - FRL_RADIUS + i / FRE_EXT, gx = tx * FRE_TILE - FRL_RADIUS + i % FRE_EXT;
+				const int gy = ty * FRS_TILE - FRL_RADIUS + i / FRS_EXT, gx = tx * FRS_TILE - FRL_RADIUS + i % FRS_EXT;
 				const size_t oc = (size_t)c * hw + (size_t)gy * a.W + gx;
 				const float m = (w & FRE_MASK_BIT) ? 1.0f : 0.0f;
 				xv = fre_render(render[oc], a.clamp, m, MASKED);
@@ -103,18 +103,10 @@ __global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_tiles(FrEvalArgs a
 			s_x[i] = xv; s_y[i] = yv;
 		}
 		__syncthreads();
-		for (int i = tid; i < FRE_EXT * FRE_TILE; i += FRE_THREADS)
-		{
-			const int r = i / FRE_TILE, q = i % FRE_TILE;
-			float h[5];
-			frl_conv11_moments(&s_x[r * FRE_EXT + q], &s_y[r * FRE_EXT + q], 1, h);
-#pragma unroll
-			for (int k = 0; k < 5; k++) s_h[k][i] = h[k];
-		}
+		frs_rows<frl_conv11_moments>(s_x, s_y, s_h);
 		__syncthreads();
 		float mo[5];
-#pragma unroll
-		for (int k = 0; k < 5; k++) mo[k] = frl_conv11(&s_h[k][ly * FRE_TILE + lx], FRE_TILE);
+		frs_columns(s_h, lx, ly, mo);
 		float dmu, d11, d12;
 		float ssim = frl_ssim_pixel(mo[0], mo[1], mo[2], mo[3], mo[4], dmu, d11, d12);
 		// a window black in one image (fr_eval_math.h): the raw moments, in a second pass through s_h that a tile without such a
@@ -122,25 +114,17 @@ __global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_tiles(FrEvalArgs a
 		const bool dark = inside && fre_window_is_dark(mo[0], mo[1]);
 		if (__syncthreads_or(dark))
 		{
-			for (int i = tid; i < FRE_EXT * FRE_TILE; i += FRE_THREADS)
-			{
-				const int r = i / FRE_TILE, q = i % FRE_TILE;
-				float h[5];
-				fre_conv11_raw_moments(&s_x[r * FRE_EXT + q], &s_y[r * FRE_EXT + q], 1, h);
-#pragma unroll
-				for (int k = 0; k < 5; k++) s_h[k][i] = h[k];
-			}
+			frs_rows<fre_conv11_raw_moments>(s_x, s_y, s_h);
 			__syncthreads();
 			if (dark)
 			{
-#pragma unroll
-				for (int k = 0; k < 5; k++) mo[k] = frl_conv11(&s_h[k][ly * FRE_TILE + lx], FRE_TILE);
+				frs_columns(s_h, lx, ly, mo);
 				ssim = fre_ssim_pixel_raw(mo[0], mo[1], mo[2], mo[3], mo[4]);
 			}
 		}
 		if (inside)
 		{
-			const int o = (ly + FRL_RADIUS) * FRE_EXT + lx + FRL_RADIUS;
+			const int o = (ly + FRL_RADIUS) * FRS_EXT + lx + FRL_RADIUS;
 			const double sq = (double)fre_sq_diff(s_x[o], s_y[o]);
 			if (c == 0) sums[FRE_S_MSE] = sq; else if (c == 1) sums[FRE_S_MSE + 1] = sq; else sums[FRE_S_MSE + 2] = sq;
 			sums[FRE_S_SSIM] += (double)ssim;
@@ -153,7 +137,7 @@ __global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_tiles(FrEvalArgs a
 		const float g = a.gt_depth[(size_t)v * a.gt_depth_vs + o];
 		if (fre_depth_counts(g, a.valid_only))
 		{
-			const float m = (s_pix[(ly + FRL_RADIUS) * FRE_EXT + lx + FRL_RADIUS] & FRE_MASK_BIT) ? 1.0f : 0.0f;
+			const float m = (s_pix[(ly + FRL_RADIUS) * FRS_EXT + lx + FRL_RADIUS] & FRE_MASK_BIT) ? 1.0f : 0.0f;
 			const float dd = fre_depth_diff(a.depth[(size_t)v * a.depth_vs + o], g, m, MASKED);
 			sums[FRE_S_DL1] = (double)fabsf(dd);
 			sums[FRE_S_DSQ] = (double)(dd * dd);
@@ -161,32 +145,19 @@ __global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_tiles(FrEvalArgs a
 		}
 	}
 
-#pragma unroll
-	for (int k = 0; k < FRE_SUMS; k++)
-	{
-		double s = sums[k];
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-		if ((tid & 63) == 0) s_red[k][tid >> 6] = s;
-	}
-	__syncthreads();
-	if (tid < FRE_SUMS)
-		a.partials[((size_t)v * FRE_SUMS + tid) * a.T + tile] = ((s_red[tid][0] + s_red[tid][1]) + s_red[tid][2]) + s_red[tid][3];
+	frb_sum256<FRE_SUMS>(sums, s_red);
+	if (tid < FRE_SUMS) a.partials[((size_t)v * FRE_SUMS + tid) * a.T + tile] = frb_sum4(s_red[tid]);
 }
 
 // A quantity's T partials are added by one wave: lane l adds partials l, l + 64, .. in index order, then the lanes in a fixed tree.
-__global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_rows(const double* __restrict__ partials, int T, double hw, int has_depth,
+__global__ __launch_bounds__(FRS_THREADS) void k_view_metrics_rows(const double* __restrict__ partials, int T, double hw, int has_depth,
                                                                    float* __restrict__ rows)
 {
 	__shared__ double s_sum[FRE_SUMS];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, v = blockIdx.x;
-	for (int q = wave; q < FRE_SUMS; q += FRE_THREADS / 64)
+	for (int q = wave; q < FRE_SUMS; q += FRS_THREADS / 64)
 	{
-		const double* p = partials + ((size_t)v * FRE_SUMS + q) * T;
-		double s = 0.0;
-		for (int t = lane; t < T; t += 64) s += p[t];
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+		const double s = frb_row_sum(partials + ((size_t)v * FRE_SUMS + q) * T, T);
 		if (lane == 0) s_sum[q] = s;
 	}
 	__syncthreads();
@@ -198,14 +169,14 @@ __global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_rows(const double*
 	for (int k = 0; k < FRE_ROW; k++) rows[(size_t)v * FRE_ROW + k] = row[k];
 }
 
-__global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_summary(const float* __restrict__ rows, int V, float* __restrict__ summary)
+__global__ __launch_bounds__(FRS_THREADS) void k_view_metrics_summary(const float* __restrict__ rows, int V, float* __restrict__ summary)
 {
-	__shared__ float s_rows[FRE_THREADS][4];
+	__shared__ float s_rows[FRS_THREADS][4];
 	const int tid = threadIdx.x;
 	double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-	for (int v0 = 0; v0 < V; v0 += FRE_THREADS)
+	for (int v0 = 0; v0 < V; v0 += FRS_THREADS)
 	{
-		const int n = V - v0 < FRE_THREADS ? V - v0 : FRE_THREADS;
+		const int n = V - v0 < FRS_THREADS ? V - v0 : FRS_THREADS;
 		__syncthreads();
 		if (tid < n)
 			for (int k = 0; k < 4; k++) s_rows[tid][k] = rows[(size_t)(v0 + tid) * FRE_ROW + k];
@@ -226,12 +197,12 @@ __global__ __launch_bounds__(FRE_THREADS) void k_view_metrics_summary(const floa
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
-static int fre_tiles(int n) { return (n + FRE_TILE - 1) / FRE_TILE; }
+static int fre_tiles(int n) { return (n + FRS_TILE - 1) / FRS_TILE; }
 
 static bool fre_dims_ok(int32_t V, int32_t H, int32_t W)
 {
 	// the views ride on the grid's y; H W within 2^30 keeps every tile count and every in-view offset far inside 32 bits
-	return V >= 1 && H >= 1 && W >= 1 && V <= 65535 && (int64_t)H * W <= ((int64_t)1 << 30);
+	return V >= 1 && V <= 65535 && fr_image_ok(H, W);
 }
 
 extern "C" size_t fr_view_metrics_workspace_bytes(int32_t V, int32_t H, int32_t W)
@@ -244,7 +215,7 @@ extern "C" int fr_view_metrics_summary(const float* rows, int32_t V, float* summ
 {
 	if (!rows || !summary) return fr_fail(FR_EINVAL, "fr_view_metrics_summary: null pointer (rows, summary)");
 	if (V < 1) return fr_fail(FR_EINVAL, "fr_view_metrics_summary: bad argument (V >= 1)");
-	hipLaunchKernelGGL(k_view_metrics_summary, dim3(1), dim3(FRE_THREADS), 0, (hipStream_t)stream, rows, V, summary);
+	hipLaunchKernelGGL(k_view_metrics_summary, dim3(1), dim3(FRS_THREADS), 0, (hipStream_t)stream, rows, V, summary);
 	return fr_check_launch("k_view_metrics_summary");
 }
 
@@ -280,7 +251,7 @@ extern "C" int fr_view_metrics(const fr_view_metrics_cfg* cfg, const float* rend
 	a.gt_channels = cfg->gt_channels; a.clamp = cfg->clamp_render; a.valid_only = cfg->depth_valid_only;
 	a.partials = (double*)workspace;
 	hipStream_t s = (hipStream_t)stream;
-	const dim3 grid(a.T, cfg->V), block(FRE_THREADS);
+	const dim3 grid(a.T, cfg->V), block(FRS_THREADS);
 	if (cfg->gt_layout == FR_EVAL_GT_U8_HWC)
 	{
 		if (mask) hipLaunchKernelGGL((k_view_metrics_tiles<true, true>), grid, block, 0, s, a);

@@ -20,14 +20,17 @@
 //   k_ingest_emit             one thread per selected cell: back-projection of the cell's top-left pixel, colour bits, (1,0,0,0), 0,
 //                             log scale; c2w is inverted from w2c once per workgroup.
 //
-// Workgroups never wait for each other: what one launch hands to the next goes through the kernel boundary.
+// Workgroups never wait for each other: what one launch hands to the next goes through the kernel boundary.  The radix select, the
+// ballot count / rank and the scan of the counts are the workgroup primitives of fr_block.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "fr_internal.h"
+#include "fr_block.h"
 #include "fr_ingest_math.h"
 
 #define FRI_THREADS 256
+static_assert(FRI_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 #define FRI_HIST_ITEMS 8                                   // pixels per thread of a histogram workgroup
 #define FRI_HIST_BYTES (4 * 256 * sizeof(uint32_t))       // the four histograms; the NaN count sits behind them
 #define FRI_HEAD_BYTES (FRI_HIST_BYTES + 64)
@@ -47,60 +50,21 @@ struct FriArgs {
 	int32_t* status;
 };
 
-// inclusive scan of one value per thread over the 256 threads of the workgroup; s_wave[4] is scratch (free again on return)
-__device__ __forceinline__ uint32_t fri_scan256(uint32_t c, uint32_t* s_wave, uint32_t& total)
-{
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t incl = c;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1)
-	{
-		const uint32_t v = __shfl_up(incl, o, 64);
-		if (lane >= o) incl += v;
-	}
-	if (lane == 63) s_wave[wave] = incl;
-	__syncthreads();
-	uint32_t base = 0;
-	for (int w = 0; w < wave; w++) base += s_wave[w];
-	total = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-	__syncthreads();
-	return incl + base;
-}
-
-// the bucket of histogram h that holds rank k, for every thread; k becomes the rank inside that bucket
-__device__ __forceinline__ uint32_t fri_pick(const uint32_t* __restrict__ h, uint32_t& k, uint32_t* s_wave, uint32_t* s_out)
-{
-	const int tid = threadIdx.x;
-	const uint32_t c = h[tid];
-	uint32_t total;
-	const uint32_t incl = fri_scan256(c, s_wave, total);
-	if (tid == 0) { s_out[0] = 255u; s_out[1] = 0u; }       // rank k lies past the counted values (NaNs were left out): the result is not used
-	__syncthreads();
-	if (incl > k && incl - c <= k) { s_out[0] = (uint32_t)tid; s_out[1] = k - (incl - c); }
-	__syncthreads();
-	const uint32_t bucket = s_out[0];
-	k = s_out[1];
-	__syncthreads();
-	return bucket;
-}
-
-// the prefix that the first `passes` histograms fix, and the rank left inside it
+// the prefix that the first `passes` histograms fix for the lower median, element (n - 1) / 2 of the sorted errors
 __device__ __forceinline__ uint32_t fri_prefix(const FriArgs& a, int passes, uint32_t* s_wave, uint32_t* s_out)
 {
-	uint32_t k = (a.n - 1u) / 2u, prefix = 0u;
-	for (int q = 0; q < passes; q++) prefix = (prefix << 8) | fri_pick(a.hist + 256 * q, k, s_wave, s_out);
-	return prefix;
+	uint32_t k = (a.n - 1u) / 2u, inside;
+	return frb_select_prefix(a.hist, passes, k, inside, s_wave, s_out);
 }
 
 template <int PASS>
 __global__ __launch_bounds__(FRI_THREADS) void k_ingest_hist(FriArgs a)
 {
-	__shared__ uint32_t s_hist[256], s_wave[4], s_out[2];
+	__shared__ uint32_t s_hist[256], s_wave[4], s_out[3];
 	const int tid = threadIdx.x;
 	s_hist[tid] = 0u;
 	const uint32_t prefix = fri_prefix(a, PASS, s_wave, s_out);
 	__syncthreads();
-	constexpr int shift = 24 - 8 * PASS;
 	uint32_t nans = 0u;
 	const uint32_t base = blockIdx.x * (uint32_t)(FRI_THREADS * FRI_HIST_ITEMS);
 #pragma unroll
@@ -110,18 +74,17 @@ __global__ __launch_bounds__(FRI_THREADS) void k_ingest_hist(FriArgs a)
 		if (p >= a.n) continue;
 		const float e = fri_depth_error(a.gt[p], a.depth_sil[p]);
 		if (e != e) { nans++; continue; }
-		const uint32_t u = fri_bits(e);
-		if (PASS == 0 || (u >> ((shift + 8) & 31)) == prefix) atomicAdd(&s_hist[(u >> shift) & 255u], 1u);
+		frb_select_count<PASS>(s_hist, fri_bits(e), prefix);
 	}
 	__syncthreads();
-	if (s_hist[tid]) atomicAdd(&a.hist[256 * PASS + tid], s_hist[tid]);
+	frb_select_flush<PASS>(a.hist, s_hist);
 	if (PASS == 0 && nans) atomicAdd(&a.hist[4 * 256], nans);
 }
 
 __global__ __launch_bounds__(FRI_THREADS) void k_ingest_mask(FriArgs a)
 {
-	__shared__ uint32_t s_wave[4], s_out[2];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	__shared__ uint32_t s_wave[4], s_out[3];
+	const int tid = threadIdx.x;
 	uint32_t med = 0u, has_nan = 0u;
 	float thr = 0.0f;
 	if (a.mode == FR_INGEST_NONPRESENCE)
@@ -145,12 +108,10 @@ __global__ __launch_bounds__(FRI_THREADS) void k_ingest_mask(FriArgs a)
 			}
 		a.pooled[g] = sel ? 1 : 0;
 	}
-	const unsigned long long ballot = __ballot(sel);
-	if (lane == 0) s_wave[wave] = (uint32_t)__popcll(ballot);
-	__syncthreads();
+	const uint32_t count = frb_count256(sel, s_wave);
 	if (tid == 0)
 	{
-		a.counts[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+		a.counts[blockIdx.x] = count;
 		if (blockIdx.x == 0) { a.status[1] = (int32_t)has_nan; a.status[2] = 0; a.status[3] = 0; a.status[4] = (int32_t)med; }
 	}
 }
@@ -159,32 +120,18 @@ __global__ __launch_bounds__(FRI_THREADS) void k_ingest_scan(const uint32_t* __r
                                                              int32_t* __restrict__ status)
 {
 	__shared__ uint32_t s_wave[4];
-	const int tid = threadIdx.x;
-	uint32_t carry = 0u;
-	for (int base = 0; base < nwg; base += FRI_THREADS)
-	{
-		const int i = base + tid;
-		const uint32_t c = i < nwg ? counts[i] : 0u;
-		uint32_t total;
-		const uint32_t incl = fri_scan256(c, s_wave, total);
-		if (i < nwg) offsets[i] = carry + (incl - c);
-		carry += total;
-	}
-	if (tid == 0) status[0] = (int32_t)carry;
+	const uint32_t total = frb_scan_counts(counts, offsets, nwg, s_wave);
+	if (threadIdx.x == 0) status[0] = (int32_t)total;
 }
 
 __global__ __launch_bounds__(FRI_THREADS) void k_ingest_scatter(FriArgs a)
 {
 	__shared__ uint32_t s_wave[4];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int g = blockIdx.x * FRI_THREADS + tid;
+	const int g = blockIdx.x * FRI_THREADS + threadIdx.x;
 	const bool sel = g < a.G && a.pooled[g] != 0;
-	const unsigned long long ballot = __ballot(sel);
-	if (lane == 0) s_wave[wave] = (uint32_t)__popcll(ballot);
-	__syncthreads();
+	const uint32_t before = frb_rank256(sel, s_wave);        // (a barrier: in front of the return)
 	if (!sel) return;
-	uint32_t slot = a.offsets[blockIdx.x] + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-	for (int w = 0; w < wave; w++) slot += s_wave[w];
+	const uint32_t slot = a.offsets[blockIdx.x] + before;
 	if (slot < (uint32_t)a.G) a.idx[slot] = g;            // always: at most G cells are selected
 }
 

@@ -18,39 +18,22 @@
 //                             keyframe, the keyframe's mask where it has one, valid & inside counted by ballot / popcount and
 //                             added to out_counts[k] with one integer atomic per workgroup.
 //
-// Workgroups never wait for each other: what one launch hands to the next goes through the kernel boundary.
+// Workgroups never wait for each other: what one launch hands to the next goes through the kernel boundary.  The ballot count / rank
+// of k_kf_count / k_kf_scatter and the scan of the counts are the workgroup primitives of fr_block.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "fr_internal.h"
+#include "fr_block.h"
 #include "fr_keyframe_math.h"
 
 #define FRK_THREADS 256
+static_assert(FRK_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 #define FRK_CHUNK_ITEMS 4                                  // points per thread of an overlap workgroup
 #define FRK_MAX_WG (FR_KEYFRAME_MAX_POINTS / FRK_THREADS)  // workgroups of k_kf_points / k_kf_pairs at the most
 #define FRK_NAN_BITS 0x7fc00000u                           // the keys of an out-of-range draw: a NaN equals nothing
 #define FRK_FLAG_VALID 1
 #define FRK_FLAG_OUT_OF_RANGE 2                            // left by k_kf_points for k_kf_pairs, which overwrites it
-
-// inclusive scan of one value per thread over the 256 threads of the workgroup; s_wave[4] is scratch (free again on return)
-__device__ __forceinline__ uint32_t frk_scan256(uint32_t c, uint32_t* s_wave, uint32_t& total)
-{
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t incl = c;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1)
-	{
-		const uint32_t v = __shfl_up(incl, o, 64);
-		if (lane >= o) incl += v;
-	}
-	if (lane == 63) s_wave[wave] = incl;
-	__syncthreads();
-	uint32_t base = 0;
-	for (int w = 0; w < wave; w++) base += s_wave[w];
-	total = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-	__syncthreads();
-	return incl + base;
-}
 
 __device__ __forceinline__ bool frk_pixel_valid(const float* __restrict__ depth, const uint8_t* __restrict__ mask, uint32_t p, uint32_t n)
 {
@@ -61,45 +44,28 @@ __global__ __launch_bounds__(FRK_THREADS) void k_kf_count(const float* __restric
                                                           uint32_t* __restrict__ counts)
 {
 	__shared__ uint32_t s_wave[4];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const bool sel = frk_pixel_valid(depth, mask, blockIdx.x * (uint32_t)FRK_THREADS + tid, n);
-	const unsigned long long ballot = __ballot(sel);
-	if (lane == 0) s_wave[wave] = (uint32_t)__popcll(ballot);
-	__syncthreads();
-	if (tid == 0) counts[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+	const bool sel = frk_pixel_valid(depth, mask, blockIdx.x * (uint32_t)FRK_THREADS + threadIdx.x, n);
+	const uint32_t count = frb_count256(sel, s_wave);
+	if (threadIdx.x == 0) counts[blockIdx.x] = count;
 }
 
 __global__ __launch_bounds__(FRK_THREADS) void k_kf_scan(const uint32_t* __restrict__ counts, uint32_t* __restrict__ offsets, int nwg,
                                                          int32_t* __restrict__ status)
 {
 	__shared__ uint32_t s_wave[4];
-	const int tid = threadIdx.x;
-	uint32_t carry = 0u;
-	for (int base = 0; base < nwg; base += FRK_THREADS)
-	{
-		const int i = base + tid;
-		const uint32_t c = i < nwg ? counts[i] : 0u;
-		uint32_t total;
-		const uint32_t incl = frk_scan256(c, s_wave, total);
-		if (i < nwg) offsets[i] = carry + (incl - c);
-		carry += total;
-	}
-	if (tid == 0) { status[0] = (int32_t)carry; status[1] = 0; status[2] = 0; status[3] = 0; }
+	const uint32_t total = frb_scan_counts(counts, offsets, nwg, s_wave);
+	if (threadIdx.x == 0) { status[0] = (int32_t)total; status[1] = 0; status[2] = 0; status[3] = 0; }
 }
 
 __global__ __launch_bounds__(FRK_THREADS) void k_kf_scatter(const float* __restrict__ depth, const uint8_t* __restrict__ mask, uint32_t n,
                                                             const uint32_t* __restrict__ offsets, int32_t* __restrict__ idx)
 {
 	__shared__ uint32_t s_wave[4];
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const uint32_t p = blockIdx.x * (uint32_t)FRK_THREADS + tid;
+	const uint32_t p = blockIdx.x * (uint32_t)FRK_THREADS + threadIdx.x;
 	const bool sel = frk_pixel_valid(depth, mask, p, n);
-	const unsigned long long ballot = __ballot(sel);
-	if (lane == 0) s_wave[wave] = (uint32_t)__popcll(ballot);
-	__syncthreads();
+	const uint32_t before = frb_rank256(sel, s_wave);        // (a barrier: in front of the return)
 	if (!sel) return;
-	uint32_t slot = offsets[blockIdx.x] + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-	for (int w = 0; w < wave; w++) slot += s_wave[w];
+	const uint32_t slot = offsets[blockIdx.x] + before;
 	if (slot < n) idx[slot] = (int32_t)p;                  // always: at most n pixels are selected
 }
 
@@ -249,13 +215,11 @@ __global__ __launch_bounds__(FRK_THREADS) void k_kf_overlap(FrkArgs a)
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
-static bool frk_frame_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 30); }
-
 static int frk_pixel_wgs(int32_t H, int32_t W) { return (int)(((int64_t)H * W + FRK_THREADS - 1) / FRK_THREADS); }
 
 extern "C" size_t fr_keyframe_valid_pixels_workspace_bytes(int32_t H, int32_t W)
 {
-	if (!frk_frame_ok(H, W)) return 0;
+	if (!fr_image_ok(H, W)) return 0;
 	return 2 * (size_t)frk_pixel_wgs(H, W) * sizeof(uint32_t);
 }
 
@@ -281,7 +245,7 @@ extern "C" size_t fr_keyframe_overlap_workspace_bytes(int32_t n)
 extern "C" int fr_keyframe_valid_pixels(int32_t H, int32_t W, const float* depth, const uint8_t* mask, int32_t* idx_out, int32_t* status,
                                         void* workspace, size_t workspace_bytes, fr_stream_t stream)
 {
-	if (!frk_frame_ok(H, W)) return fr_fail(FR_EINVAL, "fr_keyframe_valid_pixels: bad argument (H, W; H W at most 2^30)");
+	if (!fr_image_ok(H, W)) return fr_fail(FR_EINVAL, "fr_keyframe_valid_pixels: bad argument (H, W; H W at most 2^30)");
 	if (!depth || !idx_out || !status) return fr_fail(FR_EINVAL, "fr_keyframe_valid_pixels: null pointer (depth, idx_out, status)");
 	if ((uintptr_t)depth % 4 || (uintptr_t)idx_out % 4 || (uintptr_t)status % 4)
 		return fr_fail(FR_EINVAL, "fr_keyframe_valid_pixels: bad argument (depth, idx_out, status must be 4-byte aligned)");
@@ -308,7 +272,7 @@ extern "C" int fr_keyframe_overlap(const fr_keyframe_cfg* cfg, const float* dept
                                    int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream)
 {
 	if (!cfg) return fr_fail(FR_EINVAL, "fr_keyframe_overlap: null cfg");
-	if (!frk_frame_ok(cfg->H, cfg->W)) return fr_fail(FR_EINVAL, "fr_keyframe_overlap: bad argument (cfg: H, W; H W at most 2^30)");
+	if (!fr_image_ok(cfg->H, cfg->W)) return fr_fail(FR_EINVAL, "fr_keyframe_overlap: bad argument (cfg: H, W; H W at most 2^30)");
 	if (cfg->n < 1 || cfg->n > FR_KEYFRAME_MAX_POINTS) return fr_fail(FR_EINVAL, "fr_keyframe_overlap: bad argument (cfg->n is 1 .. FR_KEYFRAME_MAX_POINTS)");
 	if (cfg->K < 0 || cfg->edge < 0) return fr_fail(FR_EINVAL, "fr_keyframe_overlap: bad argument (cfg: K, edge must not be negative)");
 	if (valid_idx && cfg->n_valid_idx < 0) return fr_fail(FR_EINVAL, "fr_keyframe_overlap: bad argument (cfg->n_valid_idx)");

@@ -15,18 +15,18 @@
 //   k_image_loss_backward<SSIM, MASKED>  same tiling: the adjoint of the symmetric, zero-padded window is the same separable pass
 //                                        over the three saved partial maps.  The upstream gradient is read from device memory.
 //
-// No atomics: the same call gives the same bits.  The arithmetic is csrc/fr_loss_math.h, which the CPU harness compiles too.
+// No atomics: the same call gives the same bits.  The arithmetic is csrc/fr_loss_math.h, which the CPU harness compiles too; the tile
+// geometry and the two passes of the forward are csrc/fr_ssim_tile.h (shared with fr_eval.hip), the fp64 sums fr_block.h's.
 // LDS: 5.4 KB (two 26 x 26 tiles) + 8.3 KB (26 x 16 x 5) forward, 8.1 KB + 5 KB backward.  At 3 x 256 x 256 the three kernels move
 // ~6 MB: launch latency, not bandwidth, is what a call costs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "fr_internal.h"
-#include "fr_loss_math.h"
+#include "fr_block.h"
+#include "fr_ssim_tile.h"
 
-#define FRL_TILE 16
-#define FRL_EXT (FRL_TILE + 2 * FRL_RADIUS)      // 26
-#define FRL_THREADS (FRL_TILE * FRL_TILE)
+static_assert(FRS_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 
 struct FrLossArgs {
 	const float* x;              // [C,H,W] render
@@ -56,43 +56,35 @@ __device__ __forceinline__ void frl_load(const FrLossArgs& a, int c, int py, int
 }
 
 template <bool SSIM, bool MASKED>
-__global__ __launch_bounds__(FRL_THREADS) void k_image_loss_tiles(FrLossArgs a)
+__global__ __launch_bounds__(FRS_THREADS) void k_image_loss_tiles(FrLossArgs a)
 {
-	__shared__ float s_x[SSIM ? FRL_EXT * FRL_EXT : 1], s_y[SSIM ? FRL_EXT * FRL_EXT : 1];
-	__shared__ float s_h[SSIM ? 5 : 1][SSIM ? FRL_EXT * FRL_TILE : 1];
-	__shared__ double s_red[3][FRL_THREADS / 64];
+	__shared__ float s_x[SSIM ? FRS_EXT * FRS_EXT : 1], s_y[SSIM ? FRS_EXT * FRS_EXT : 1];
+	__shared__ float s_h[SSIM ? 5 : 1][SSIM ? FRS_EXT * FRS_TILE : 1];
+	__shared__ double s_red[3][FRS_THREADS / 64];
 	const int tid = threadIdx.x, c = blockIdx.y;
 	const int tile = blockIdx.x, tx = tile % a.gx, ty = tile / a.gx;
-	const int lx = tid % FRL_TILE, ly = tid / FRL_TILE;
-	const int px = tx * FRL_TILE + lx, py = ty * FRL_TILE + ly;
+	const int lx = tid % FRS_TILE, ly = tid / FRS_TILE;
+	const int px = tx * FRS_TILE + lx, py = ty * FRS_TILE + ly;
 	const bool inside = px < a.W && py < a.H;
 	float xv, yv, m;
-	double v_ssim = 0.0, v_l1 = 0.0, v_cnt = 0.0;
-	if (SSIM)
+	double v[3] = {0.0, 0.0, 0.0};                            // SSIM term, |x - y|, mask count
+	if constexpr (SSIM)
 	{
-		for (int i = tid; i < FRL_EXT * FRL_EXT; i += FRL_THREADS)
+		for (int i = tid; i < FRS_EXT * FRS_EXT; i += FRS_THREADS)
 		{
-			const int r = i / FRL_EXT, q = i % FRL_EXT;
+			const int r = i / FRS_EXT, q = i % FRS_EXT;
 			float mm;
-			frl_load<MASKED>(a, c, ty * FRL_TILE - FRL_RADIUS + r, tx * FRL_TILE - FRL_RADIUS + q, s_x[i], s_y[i], mm);
+			frl_load<MASKED>(a, c, ty * FRS_TILE - FRL_RADIUS + r, tx * FRS_TILE - FRL_RADIUS + q, s_x[i], s_y[i], mm);
 		}
 		__syncthreads();
-		for (int i = tid; i < FRL_EXT * FRL_TILE; i += FRL_THREADS)
-		{
-			const int r = i / FRL_TILE, q = i % FRL_TILE;
-			float h[5];
-			frl_conv11_moments(&s_x[r * FRL_EXT + q], &s_y[r * FRL_EXT + q], 1, h);
-#pragma unroll
-			for (int k = 0; k < 5; k++) s_h[k][i] = h[k];
-		}
+		frs_rows<frl_conv11_moments>(s_x, s_y, s_h);
 		__syncthreads();
 		float mo[5];
-#pragma unroll
-		for (int k = 0; k < 5; k++) mo[k] = frl_conv11(&s_h[k][ly * FRL_TILE + lx], FRL_TILE);
+		frs_columns(s_h, lx, ly, mo);
 		float dmu, d11, d12;
 		float ssim = frl_ssim_pixel(mo[0], mo[1], mo[2], mo[3], mo[4], dmu, d11, d12);
-		xv = s_x[(ly + FRL_RADIUS) * FRL_EXT + lx + FRL_RADIUS];
-		yv = s_y[(ly + FRL_RADIUS) * FRL_EXT + lx + FRL_RADIUS];
+		xv = s_x[(ly + FRL_RADIUS) * FRS_EXT + lx + FRL_RADIUS];
+		yv = s_y[(ly + FRL_RADIUS) * FRS_EXT + lx + FRL_RADIUS];
 		m = 1.0f;
 		if (MASKED && inside) m = a.mask[(size_t)c * a.mask_cstride + (size_t)py * a.W + px] ? 1.0f : 0.0f;
 		if (inside)
@@ -101,44 +93,32 @@ __global__ __launch_bounds__(FRL_THREADS) void k_image_loss_tiles(FrLossArgs a)
 			if (MASKED && a.weights_map && m == 0.0f) { ssim = 0.0f; dmu = 0.0f; d11 = 0.0f; d12 = 0.0f; }
 			if (a.ssim_map) a.ssim_map[o] = ssim;
 			a.saved[o] = dmu; a.saved[n + o] = d11; a.saved[2 * n + o] = d12;
-			v_ssim = (double)ssim;
+			v[0] = (double)ssim;
 		}
 	}
 	else
 		frl_load<MASKED>(a, c, py, px, xv, yv, m);
-	if (inside && m != 0.0f) { v_l1 = (double)fabsf(xv - yv); v_cnt = 1.0; }
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1)
-	{
-		v_ssim += __shfl_down(v_ssim, o, 64);
-		v_l1 += __shfl_down(v_l1, o, 64);
-		v_cnt += __shfl_down(v_cnt, o, 64);
-	}
-	if ((tid & 63) == 0) { s_red[0][tid >> 6] = v_ssim; s_red[1][tid >> 6] = v_l1; s_red[2][tid >> 6] = v_cnt; }
-	__syncthreads();
-	if (tid < 3)
-		a.partials[((size_t)tid * a.C + c) * a.T + tile] = ((s_red[tid][0] + s_red[tid][1]) + s_red[tid][2]) + s_red[tid][3];
+	if (inside && m != 0.0f) { v[1] = (double)fabsf(xv - yv); v[2] = 1.0; }
+	frb_sum256<3>(v, s_red);
+	if (tid < 3) a.partials[((size_t)tid * a.C + c) * a.T + tile] = frb_sum4(s_red[tid]);
 }
 
 // out[4] = {loss, L1 term, SSIM mean, count}; out_channel[C] = the channels' SSIM sums / (H W); tail = the two factors of the backward.
 // A row of T partials is added by one wave: lane l adds partials l, l + 64, .. in index order, then the lanes are added in a fixed tree.
-__global__ __launch_bounds__(FRL_THREADS) void k_image_loss_reduce(const double* __restrict__ partials, int C, int T, long long HW,
+__global__ __launch_bounds__(FRS_THREADS) void k_image_loss_reduce(const double* __restrict__ partials, int C, int T, long long HW,
                                                                    float w_l1, float w_ssim, int denom_mode, int weights_map,
                                                                    float* __restrict__ out, float* __restrict__ out_channel,
                                                                    float* __restrict__ tail, double* __restrict__ rows)
 {
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	for (int r = wave; r < 3 * C; r += FRL_THREADS / 64)
+	for (int r = wave; r < 3 * C; r += FRS_THREADS / 64)
 	{
-		double s = 0.0;
-		for (int t = lane; t < T; t += 64) s += partials[(size_t)r * T + t];
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+		const double s = frb_row_sum(partials + (size_t)r * T, T);
 		if (lane == 0) rows[r] = s;
 	}
 	__syncthreads();
 	if (out_channel)
-		for (int c = tid; c < C; c += FRL_THREADS) out_channel[c] = (float)(rows[c] / (double)HW);
+		for (int c = tid; c < C; c += FRS_THREADS) out_channel[c] = (float)(rows[c] / (double)HW);
 	if (tid != 0) return;
 	double q[3];
 	for (int k = 0; k < 3; k++)
@@ -160,37 +140,37 @@ __global__ __launch_bounds__(FRL_THREADS) void k_image_loss_reduce(const double*
 }
 
 template <bool SSIM, bool MASKED>
-__global__ __launch_bounds__(FRL_THREADS) void k_image_loss_backward(FrLossArgs a, const float* __restrict__ tail,
+__global__ __launch_bounds__(FRS_THREADS) void k_image_loss_backward(FrLossArgs a, const float* __restrict__ tail,
                                                                      const float* __restrict__ upstream, float* __restrict__ dL_dx)
 {
-	__shared__ float s_p[SSIM ? 3 : 1][SSIM ? FRL_EXT * FRL_EXT : 1];
-	__shared__ float s_h[SSIM ? 3 : 1][SSIM ? FRL_EXT * FRL_TILE : 1];
+	__shared__ float s_p[SSIM ? 3 : 1][SSIM ? FRS_EXT * FRS_EXT : 1];
+	__shared__ float s_h[SSIM ? 3 : 1][SSIM ? FRS_EXT * FRS_TILE : 1];
 	const int tid = threadIdx.x, c = blockIdx.y;
 	const int tile = blockIdx.x, tx = tile % a.gx, ty = tile / a.gx;
-	const int lx = tid % FRL_TILE, ly = tid / FRL_TILE;
-	const int px = tx * FRL_TILE + lx, py = ty * FRL_TILE + ly;
+	const int lx = tid % FRS_TILE, ly = tid / FRS_TILE;
+	const int px = tx * FRS_TILE + lx, py = ty * FRS_TILE + ly;
 	float D[3] = {0.0f, 0.0f, 0.0f};
 	if (SSIM)
 	{
 		const size_t n = (size_t)a.C * a.H * a.W;
-		for (int i = tid; i < FRL_EXT * FRL_EXT; i += FRL_THREADS)
+		for (int i = tid; i < FRS_EXT * FRS_EXT; i += FRS_THREADS)
 		{
-			const int gy = ty * FRL_TILE - FRL_RADIUS + i / FRL_EXT, gx = tx * FRL_TILE - FRL_RADIUS + i % FRL_EXT;
+			const int gy = ty * FRS_TILE - FRL_RADIUS + i / FRS_EXT, gx = tx * FRS_TILE - FRL_RADIUS + i % FRS_EXT;
 			const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
 			const size_t o = in ? ((size_t)c * a.H + gy) * a.W + gx : 0;
 #pragma unroll
 			for (int k = 0; k < 3; k++) s_p[k][i] = in ? a.saved[k * n + o] : 0.0f;
 		}
 		__syncthreads();
-		for (int i = tid; i < FRL_EXT * FRL_TILE; i += FRL_THREADS)
+		for (int i = tid; i < FRS_EXT * FRS_TILE; i += FRS_THREADS)
 		{
-			const int r = i / FRL_TILE, q = i % FRL_TILE;
+			const int r = i / FRS_TILE, q = i % FRS_TILE;
 #pragma unroll
-			for (int k = 0; k < 3; k++) s_h[k][i] = frl_conv11(&s_p[k][r * FRL_EXT + q], 1);
+			for (int k = 0; k < 3; k++) s_h[k][i] = frl_conv11(&s_p[k][r * FRS_EXT + q], 1);
 		}
 		__syncthreads();
 #pragma unroll
-		for (int k = 0; k < 3; k++) D[k] = frl_conv11(&s_h[k][ly * FRL_TILE + lx], FRL_TILE);
+		for (int k = 0; k < 3; k++) D[k] = frl_conv11(&s_h[k][ly * FRS_TILE + lx], FRS_TILE);
 	}
 	if (px >= a.W || py >= a.H) return;
 	float xv, yv, m;
@@ -213,7 +193,7 @@ static bool frl_cfg_ok(const fr_image_loss_cfg* cfg)
 	return true;
 }
 
-static int frl_tiles(int n) { return (n + FRL_TILE - 1) / FRL_TILE; }
+static int frl_tiles(int n) { return (n + FRS_TILE - 1) / FRS_TILE; }
 
 extern "C" size_t fr_image_loss_workspace_bytes(int32_t C, int32_t H, int32_t W)
 {
@@ -254,7 +234,7 @@ extern "C" int fr_image_loss_forward(const fr_image_loss_cfg* cfg, const float* 
 	FrLossArgs a = frl_args(cfg, img, gt, mask);
 	a.ssim_map = out_ssim_map; a.saved = saved; a.partials = (double*)workspace;
 	hipStream_t s = (hipStream_t)stream;
-	const dim3 grid(a.T, a.C), block(FRL_THREADS);
+	const dim3 grid(a.T, a.C), block(FRS_THREADS);
 	if (ssim)
 	{
 		if (mask) hipLaunchKernelGGL((k_image_loss_tiles<true, true>), grid, block, 0, s, a);
@@ -289,7 +269,7 @@ extern "C" int fr_image_loss_backward(const fr_image_loss_cfg* cfg, const float*
 	a.saved = const_cast<float*>(saved);
 	const float* tail = saved + (ssim ? (size_t)3 * cfg->C * cfg->H * cfg->W : 0);
 	hipStream_t s = (hipStream_t)stream;
-	const dim3 grid(a.T, a.C), block(FRL_THREADS);
+	const dim3 grid(a.T, a.C), block(FRS_THREADS);
 	if (ssim)
 	{
 		if (mask) hipLaunchKernelGGL((k_image_loss_backward<true, true>), grid, block, 0, s, a, tail, upstream, dL_dimg);

@@ -16,14 +16,17 @@
 //   k_edit_split     one thread per child: fr_mapedit_math.h on the child's copied rotation, log scales and mean, in place.
 //
 // Integer sums only: no dependence on the launch geometry.  Workgroups never wait for each other: what one launch hands to the next
-// goes through the kernel boundary.
+// goes through the kernel boundary.  k_edit_scan is three calls of fr_block.h's frb_scan_counts; k_edit_count and k_edit_scatter
+// keep their own ballots, three predicates behind ONE barrier.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "fr_internal.h"
+#include "fr_block.h"
 #include "fr_mapedit_math.h"
 
 #define FRM_THREADS 256
+static_assert(FRM_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 #define FRM_APPLY_MAX_GRID 4096       // workgroups per array of the apply launch; the rest is grid-strided
 
 struct FrmPlanArgs {
@@ -34,26 +37,6 @@ struct FrmPlanArgs {
 	int32_t* idx[3];             // [P] each
 	int32_t* status;
 };
-
-// inclusive scan of one value per thread over the 256 threads of the workgroup; s_wave[4] is scratch (free again on return)
-__device__ __forceinline__ uint32_t frm_scan256(uint32_t c, uint32_t* s_wave, uint32_t& total)
-{
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t incl = c;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1)
-	{
-		const uint32_t v = __shfl_up(incl, o, 64);
-		if (lane >= o) incl += v;
-	}
-	if (lane == 63) s_wave[wave] = incl;
-	__syncthreads();
-	uint32_t base = 0;
-	for (int w = 0; w < wave; w++) base += s_wave[w];
-	total = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-	__syncthreads();
-	return incl + base;
-}
 
 __device__ __forceinline__ bool frm_selected(const FrmPlanArgs& a, int k, int i)
 {
@@ -83,17 +66,8 @@ __global__ __launch_bounds__(FRM_THREADS) void k_edit_scan(const uint32_t* __res
 	const int tid = threadIdx.x;
 	for (int k = 0; k < 3; k++)
 	{
-		uint32_t carry = 0u;
-		for (int base = 0; base < nwg; base += FRM_THREADS)
-		{
-			const int i = base + tid;
-			const uint32_t c = i < nwg ? counts[k * nwg + i] : 0u;
-			uint32_t total;
-			const uint32_t incl = frm_scan256(c, s_wave, total);
-			if (i < nwg) offsets[k * nwg + i] = carry + (incl - c);
-			carry += total;
-		}
-		if (tid == 0) status[k] = (int32_t)carry;
+		const uint32_t total = frb_scan_counts(counts + k * nwg, offsets + k * nwg, nwg, s_wave);
+		if (tid == 0) status[k] = (int32_t)total;
 	}
 	if (tid == 0) status[3] = 0;
 }
@@ -235,12 +209,6 @@ extern "C" int fr_map_edit_plan(int32_t P, const uint8_t* keep, const uint8_t* c
 	return fr_check_launch("k_edit_scatter");
 }
 
-static bool frm_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-	const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-	return na && nb && a0 < b0 + nb && b0 < a0 + na;
-}
-
 extern "C" int fr_map_edit_apply(const fr_map_edit_array* table, int32_t n_arrays, int32_t P, int32_t n_keep, int32_t n_clone, int32_t n_split,
                                  int32_t n_into, const void* workspace, fr_stream_t stream)
 {
@@ -266,9 +234,9 @@ extern "C" int fr_map_edit_apply(const fr_map_edit_array* table, int32_t n_array
 		const size_t nd = (size_t)rows * table[i].cols * 4;
 		for (int j = 0; j < n_arrays; j++)
 		{
-			if (frm_overlap(table[i].dst, nd, table[j].src, (size_t)P * table[j].cols * 4))
+			if (fr_overlap(table[i].dst, nd, table[j].src, (size_t)P * table[j].cols * 4))
 				return fr_fail(FR_EINVAL, "fr_map_edit_apply: bad argument (a destination overlaps a source)");
-			if (j != i && frm_overlap(table[i].dst, nd, table[j].dst, (size_t)rows * table[j].cols * 4))
+			if (j != i && fr_overlap(table[i].dst, nd, table[j].dst, (size_t)rows * table[j].cols * 4))
 				return fr_fail(FR_EINVAL, "fr_map_edit_apply: bad argument (two destinations overlap)");
 		}
 	}

@@ -7,8 +7,8 @@
 // two nonzero calls and four .item() reads (models/SLAM/utils/slam_external.py:270-343).  Here:
 //
 //   k_objloss_hist<PASS> x 4   with reject_outliers only: the exact lower median of the H W depth errors by a radix select on the bit
-//                              patterns, most significant byte first -- the scheme of the frame ingest (fr_ingest.hip), restated here
-//                              so that unit stays as it is.  Integer histograms in LDS, flushed with integer atomics; NaNs are counted
+//                              patterns, most significant byte first -- the radix select of fr_block.h, which the frame ingest
+//                              (fr_ingest.hip) uses too.  Integer histograms in LDS, flushed with integer atomics; NaNs are counted
 //                              apart and make the median NaN.  Integer sums only: no dependence on the launch geometry.
 //   k_objloss_mask             one thread per pixel: walks the histograms to the median (with reject_outliers), the predicate of
 //                              fr_objloss_math.h, the byte, and the kept / background counts by ballot and one integer atomic a
@@ -23,14 +23,17 @@
 //   k_outside_finish           one workgroup reduces those words and writes the status; exp is taken of the four extremes only.
 //
 // No float atomics and no float adds across threads but the fp64 sums in their fixed order: the same call gives the same bits.
-// Nothing is read back to the host.  The arithmetic is csrc/fr_objloss_math.h, which the CPU harness compiles too.
+// Nothing is read back to the host.  The arithmetic is csrc/fr_objloss_math.h, which the CPU harness compiles too; the select, the
+// fp64 workgroup sum (frb_sum256) and the one-wave row sum (frb_row_sum) are fr_block.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "fr_internal.h"
+#include "fr_block.h"
 #include "fr_objloss_math.h"
 
 #define FRO_THREADS 256
+static_assert(FRO_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 #define FRO_HIST_ITEMS 8                                   // pixels per thread of a histogram workgroup
 #define FRO_HIST_BYTES (4 * 256 * sizeof(uint32_t))       // the four histograms; the NaN count sits behind them
 #define FRO_HEAD_BYTES (FRO_HIST_BYTES + 64)
@@ -48,60 +51,21 @@ struct FroMaskArgs {
 	int32_t* status;
 };
 
-// inclusive scan of one value per thread over the 256 threads of the workgroup; s_wave[4] is scratch (free again on return)
-__device__ __forceinline__ uint32_t fro_scan256(uint32_t c, uint32_t* s_wave, uint32_t& total)
-{
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	uint32_t incl = c;
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1)
-	{
-		const uint32_t v = __shfl_up(incl, o, 64);
-		if (lane >= o) incl += v;
-	}
-	if (lane == 63) s_wave[wave] = incl;
-	__syncthreads();
-	uint32_t base = 0;
-	for (int w = 0; w < wave; w++) base += s_wave[w];
-	total = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-	__syncthreads();
-	return incl + base;
-}
-
-// the bucket of histogram h that holds rank k, for every thread; k becomes the rank inside that bucket
-__device__ __forceinline__ uint32_t fro_pick(const uint32_t* __restrict__ h, uint32_t& k, uint32_t* s_wave, uint32_t* s_out)
-{
-	const int tid = threadIdx.x;
-	const uint32_t c = h[tid];
-	uint32_t total;
-	const uint32_t incl = fro_scan256(c, s_wave, total);
-	if (tid == 0) { s_out[0] = 255u; s_out[1] = 0u; }       // rank k lies past the counted values (NaNs were left out): the result is not used
-	__syncthreads();
-	if (incl > k && incl - c <= k) { s_out[0] = (uint32_t)tid; s_out[1] = k - (incl - c); }
-	__syncthreads();
-	const uint32_t bucket = s_out[0];
-	k = s_out[1];
-	__syncthreads();
-	return bucket;
-}
-
-// the prefix that the first `passes` histograms fix
+// the prefix that the first `passes` histograms fix for the lower median, element (n - 1) / 2 of the sorted errors
 __device__ __forceinline__ uint32_t fro_prefix(const FroMaskArgs& a, int passes, uint32_t* s_wave, uint32_t* s_out)
 {
-	uint32_t k = (a.n - 1u) / 2u, prefix = 0u;
-	for (int q = 0; q < passes; q++) prefix = (prefix << 8) | fro_pick(a.hist + 256 * q, k, s_wave, s_out);
-	return prefix;
+	uint32_t k = (a.n - 1u) / 2u, inside;
+	return frb_select_prefix(a.hist, passes, k, inside, s_wave, s_out);
 }
 
 template <int PASS>
 __global__ __launch_bounds__(FRO_THREADS) void k_objloss_hist(FroMaskArgs a)
 {
-	__shared__ uint32_t s_hist[256], s_wave[4], s_out[2];
+	__shared__ uint32_t s_hist[256], s_wave[4], s_out[3];
 	const int tid = threadIdx.x;
 	s_hist[tid] = 0u;
 	const uint32_t prefix = fro_prefix(a, PASS, s_wave, s_out);
 	__syncthreads();
-	constexpr int shift = 24 - 8 * PASS;
 	uint32_t nans = 0u;
 	const uint32_t base = blockIdx.x * (uint32_t)(FRO_THREADS * FRO_HIST_ITEMS);
 #pragma unroll
@@ -111,17 +75,16 @@ __global__ __launch_bounds__(FRO_THREADS) void k_objloss_hist(FroMaskArgs a)
 		if (p >= a.n) continue;
 		const float e = fro_depth_error(a.gt[p], a.depth_sil[p]);
 		if (e != e) { nans++; continue; }
-		const uint32_t u = fro_bits(e);
-		if (PASS == 0 || (u >> ((shift + 8) & 31)) == prefix) atomicAdd(&s_hist[(u >> shift) & 255u], 1u);
+		frb_select_count<PASS>(s_hist, fro_bits(e), prefix);
 	}
 	__syncthreads();
-	if (s_hist[tid]) atomicAdd(&a.hist[256 * PASS + tid], s_hist[tid]);
+	frb_select_flush<PASS>(a.hist, s_hist);
 	if (PASS == 0 && nans) atomicAdd(&a.hist[4 * 256], nans);
 }
 
 __global__ __launch_bounds__(FRO_THREADS) void k_objloss_mask(FroMaskArgs a)
 {
-	__shared__ uint32_t s_wave[4], s_out[2], s_bg[4];
+	__shared__ uint32_t s_wave[4], s_out[3], s_bg[4];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	uint32_t med = 0u, has_nan = 0u;
 	float thr = 0.0f;
@@ -165,26 +128,9 @@ struct FroPenaltyArgs {
 	float lambda_rgb, lambda_alpha;
 };
 
-// the three values of a thread summed over the workgroup in a fixed order: lanes by a shuffle tree, then the four waves in index order
-__device__ __forceinline__ void fro_sum3(double* v, double (*s_red)[FRO_THREADS / 64], double* out)
-{
-	const int tid = threadIdx.x;
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1)
-	{
-		v[0] += __shfl_down(v[0], o, 64);
-		v[1] += __shfl_down(v[1], o, 64);
-		v[2] += __shfl_down(v[2], o, 64);
-	}
-	if ((tid & 63) == 0) { s_red[0][tid >> 6] = v[0]; s_red[1][tid >> 6] = v[1]; s_red[2][tid >> 6] = v[2]; }
-	__syncthreads();
-	if (tid < 3) out[tid] = ((s_red[tid][0] + s_red[tid][1]) + s_red[tid][2]) + s_red[tid][3];
-}
-
 __global__ __launch_bounds__(FRO_THREADS) void k_bg_penalty_partials(FroPenaltyArgs a, double* __restrict__ partials)
 {
 	__shared__ double s_red[3][FRO_THREADS / 64];
-	__shared__ double s_out[3];
 	const int tid = threadIdx.x;
 	double v[3] = {0.0, 0.0, 0.0};
 	const uint32_t base = blockIdx.x * (uint32_t)(FRO_THREADS * FRO_SUM_ITEMS);
@@ -198,9 +144,8 @@ __global__ __launch_bounds__(FRO_THREADS) void k_bg_penalty_partials(FroPenaltyA
 		v[1] += (double)fro_alpha_term(a.depth_sil[(size_t)a.n + p], bg);
 		v[2] += (double)bg;
 	}
-	fro_sum3(v, s_red, s_out);
-	__syncthreads();
-	if (tid < 3) partials[(size_t)tid * a.T + blockIdx.x] = s_out[tid];
+	frb_sum256<3>(v, s_red);
+	if (tid < 3) partials[(size_t)tid * a.T + blockIdx.x] = frb_sum4(s_red[tid]);
 }
 
 // A row of T partials is added by one wave: lane l adds partials l, l + 64, .. in index order, then the lanes are added in a fixed tree.
@@ -211,10 +156,7 @@ __global__ __launch_bounds__(FRO_THREADS) void k_bg_penalty_reduce(const double*
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	if (wave < 3)
 	{
-		double s = 0.0;
-		for (int t = lane; t < T; t += 64) s += partials[(size_t)wave * T + t];
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+		const double s = frb_row_sum(partials + (size_t)wave * T, T);
 		if (lane == 0) s_rows[wave] = s;
 	}
 	__syncthreads();
@@ -330,18 +272,16 @@ __global__ __launch_bounds__(FRO_THREADS) void k_outside_finish(const uint32_t* 
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
-static bool fro_image_ok(int32_t H, int32_t W) { return H > 0 && W > 0 && (int64_t)H * W <= ((int64_t)1 << 30); }
-
 extern "C" size_t fr_loss_mask_workspace_bytes(int32_t H, int32_t W)
 {
-	return fro_image_ok(H, W) ? (size_t)FRO_HEAD_BYTES : 0;
+	return fr_image_ok(H, W) ? (size_t)FRO_HEAD_BYTES : 0;
 }
 
 extern "C" int fr_loss_mask(const fr_loss_mask_cfg* cfg, const float* depth_sil, const float* gt_depth, const uint8_t* obj_mask,
                             uint8_t* mask, int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream)
 {
 	if (!cfg) return fr_fail(FR_EINVAL, "fr_loss_mask: null cfg");
-	if (!fro_image_ok(cfg->H, cfg->W)) return fr_fail(FR_EINVAL, "fr_loss_mask: bad argument (cfg: H, W; H W at most 2^30)");
+	if (!fr_image_ok(cfg->H, cfg->W)) return fr_fail(FR_EINVAL, "fr_loss_mask: bad argument (cfg: H, W; H W at most 2^30)");
 	if (!depth_sil || !gt_depth || !mask || !status) return fr_fail(FR_EINVAL, "fr_loss_mask: null pointer (depth_sil, gt_depth, mask, status)");
 	if (cfg->reject_outliers)
 	{
@@ -382,7 +322,7 @@ static int fro_penalty_tiles(int32_t H, int32_t W)
 
 extern "C" size_t fr_bg_penalty_workspace_bytes(int32_t H, int32_t W)
 {
-	return fro_image_ok(H, W) ? (size_t)3 * fro_penalty_tiles(H, W) * sizeof(double) : 0;
+	return fr_image_ok(H, W) ? (size_t)3 * fro_penalty_tiles(H, W) * sizeof(double) : 0;
 }
 
 static FroPenaltyArgs fro_penalty_args(int32_t H, int32_t W, float lambda_rgb, float lambda_alpha, const float* im, const float* depth_sil,
@@ -399,7 +339,7 @@ extern "C" int fr_bg_penalty_forward(int32_t H, int32_t W, float lambda_rgb, flo
                                      const uint8_t* obj_mask, float* out4, float* saved2, void* workspace, size_t workspace_bytes,
                                      fr_stream_t stream)
 {
-	if (!fro_image_ok(H, W)) return fr_fail(FR_EINVAL, "fr_bg_penalty_forward: bad argument (H, W; H W at most 2^30)");
+	if (!fr_image_ok(H, W)) return fr_fail(FR_EINVAL, "fr_bg_penalty_forward: bad argument (H, W; H W at most 2^30)");
 	if (!im || !depth_sil || !obj_mask || !out4 || !saved2)
 		return fr_fail(FR_EINVAL, "fr_bg_penalty_forward: null pointer (im, depth_sil, obj_mask, out4, saved2)");
 	if (!workspace || workspace_bytes < fr_bg_penalty_workspace_bytes(H, W))
@@ -418,7 +358,7 @@ extern "C" int fr_bg_penalty_backward(int32_t H, int32_t W, float lambda_rgb, fl
                                       const uint8_t* obj_mask, const float* saved2, const float* upstream, float* dL_dim,
                                       float* dL_ddepth_sil, fr_stream_t stream)
 {
-	if (!fro_image_ok(H, W)) return fr_fail(FR_EINVAL, "fr_bg_penalty_backward: bad argument (H, W; H W at most 2^30)");
+	if (!fr_image_ok(H, W)) return fr_fail(FR_EINVAL, "fr_bg_penalty_backward: bad argument (H, W; H W at most 2^30)");
 	if (!im || !depth_sil || !obj_mask || !saved2 || !upstream || !dL_dim || !dL_ddepth_sil)
 		return fr_fail(FR_EINVAL, "fr_bg_penalty_backward: null pointer (im, depth_sil, obj_mask, saved2, upstream, dL_dim, dL_ddepth_sil)");
 	const FroPenaltyArgs a = fro_penalty_args(H, W, lambda_rgb, lambda_alpha, im, depth_sil, obj_mask);
@@ -441,7 +381,7 @@ extern "C" int fr_outside_mask(int32_t P, int32_t scale_cols, const float* means
                                void* workspace, size_t workspace_bytes, fr_stream_t stream)
 {
 	if (P < 0 || (scale_cols != 1 && scale_cols != 3)) return fr_fail(FR_EINVAL, "fr_outside_mask: bad argument (P, scale_cols is 1 or 3)");
-	if (!fro_image_ok(H, W)) return fr_fail(FR_EINVAL, "fr_outside_mask: bad argument (H, W; H W at most 2^30)");
+	if (!fr_image_ok(H, W)) return fr_fail(FR_EINVAL, "fr_outside_mask: bad argument (H, W; H W at most 2^30)");
 	if (!w2c || !intrinsics || !obj_mask || !status) return fr_fail(FR_EINVAL, "fr_outside_mask: null pointer (w2c, intrinsics, obj_mask, status)");
 	if (P > 0 && (!means3D || !log_scales || !outside)) return fr_fail(FR_EINVAL, "fr_outside_mask: null pointer (means3D, log_scales, outside)");
 	if (!workspace || workspace_bytes < fr_outside_mask_workspace_bytes(P))

@@ -394,7 +394,6 @@ __global__ __launch_bounds__(FRP_THREADS) void k_plan_paths(int H, int W, const 
 
 struct PlanLayout { size_t hist, tmp, wtab, dirty, total; int tiles_x, tiles_y; };
 
-static size_t plan_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static PlanLayout plan_layout(const fr_occ_cfg* c)
 {
@@ -403,10 +402,10 @@ static PlanLayout plan_layout(const fr_occ_cfg* c)
 	L.tiles_x = (c->grid_w + FRP_TILE - 1) / FRP_TILE;
 	L.tiles_y = (c->grid_h + FRP_TILE - 1) / FRP_TILE;
 	size_t o = 0;
-	L.wtab = o; o = plan_align(o + n * 16);
-	L.hist = o; o = plan_align(o + n * 4);
-	L.tmp = o; o = plan_align(o + n);
-	L.dirty = o; o = plan_align(o + 2 * (size_t)L.tiles_x * L.tiles_y * 4);
+	L.wtab = o; o = fr_align256(o + n * 16);
+	L.hist = o; o = fr_align256(o + n * 4);
+	L.tmp = o; o = fr_align256(o + n);
+	L.dirty = o; o = fr_align256(o + 2 * (size_t)L.tiles_x * L.tiles_y * 4);
 	L.total = o;
 	return L;
 }

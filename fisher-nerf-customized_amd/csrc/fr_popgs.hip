@@ -18,9 +18,11 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "fr_internal.h"
+#include "fr_block.h"
 #include "fr_math.h"
 
 #define POPGS_THREADS 256
+static_assert(POPGS_THREADS == FRB_THREADS, "fr_block.h is written for 256 threads");
 #define POPGS_MAX_BLOCKS_PER_VIEW 96     // 21 paths x 96 = 2016 workgroups: one resident set of 256 CUs x 8
 
 // workgroups per view: a function of E alone (see above)
@@ -102,12 +104,9 @@ __global__ __launch_bounds__(POPGS_THREADS) void k_popgs_criterion(PopgsArgs a)
 			}
 		}
 	}
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-	__shared__ double s_red[POPGS_THREADS / 64];
-	if ((tid & 63) == 0) s_red[tid >> 6] = sum;
-	__syncthreads();
-	if (tid == 0) a.partials[(size_t)v * gridDim.x + blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+	__shared__ double s_red[1][POPGS_THREADS / 64];
+	frb_sum256<1>(&sum, s_red);
+	if (tid == 0) a.partials[(size_t)v * gridDim.x + blockIdx.x] = frb_sum4(s_red[0]);
 }
 
 // scores[v] = -/+ the view's partials added in index order; exactly 0.0 for a view that sees nothing (tester 2162-2163)
@@ -129,11 +128,6 @@ extern "C" size_t fr_popgs_diag_criterion_workspace_bytes(int32_t V, int64_t E)
 	return (size_t)V * (size_t)popgs_blocks(E) * sizeof(double);
 }
 
-static bool popgs_overlap(const float* a, size_t na, const float* b, size_t nb)
-{
-	return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
-}
-
 extern "C" int fr_popgs_diag_criterion(int32_t V, int32_t K, int64_t E, const float* rows, const float* prior_in,
                                        int64_t prior_in_view_stride, float* prior_out, const uint8_t* accumulate,
                                        const int32_t* vis_count, float lam, int32_t criterion, double* scores,
@@ -151,9 +145,9 @@ extern "C" int fr_popgs_diag_criterion(int32_t V, int32_t K, int64_t E, const fl
 		// in place is fine view by view; anything else that overlaps would let one view read what another has written
 		const size_t n_in = prior_in_view_stride ? (size_t)V * (size_t)E : (size_t)E;
 		const bool same = prior_out == prior_in && (prior_in_view_stride == E || V == 1);
-		if (!same && popgs_overlap(prior_in, n_in, prior_out, (size_t)V * (size_t)E))
+		if (!same && fr_overlap(prior_in, n_in * sizeof(float), prior_out, (size_t)V * (size_t)E * sizeof(float)))
 			return fr_fail(FR_EINVAL, "fr_popgs_diag_criterion: bad argument (prior_out overlaps prior_in without being the same [V, E] block)");
-		if (popgs_overlap(rows, (size_t)V * (size_t)K * (size_t)E, prior_out, (size_t)V * (size_t)E))
+		if (fr_overlap(rows, (size_t)V * (size_t)K * (size_t)E * sizeof(float), prior_out, (size_t)V * (size_t)E * sizeof(float)))
 			return fr_fail(FR_EINVAL, "fr_popgs_diag_criterion: bad argument (prior_out overlaps rows)");
 	}
 	const int nb = popgs_blocks(E);

@@ -7,6 +7,7 @@ function's bytes); bench.py recomputes the id from the library it has loaded and
 change anywhere else in the sources leaves the id alone, a change to the kernel (or to the compiler flags) cannot.
 
     python tools/codeobj.py [path/to/libfisher_rast.so] [kernel-name-substring ...]
+    python tools/codeobj.py [path/to/libfisher_rast.so] --all        one line per function: id, mangled name (to compare two builds)
 """
 import hashlib
 import os
@@ -73,9 +74,22 @@ def kernel_code_id(so_path, kernel_substring, arch="gfx950"):
     return h.hexdigest()[:16]
 
 
+def all_code_ids(so_path, arch="gfx950"):
+    """{mangled name: sha256 (16 hex digits) of its machine code} for every function of the library's gfx950 code objects"""
+    ids = {}
+    for co in _code_objects(open(so_path, "rb").read(), arch):
+        for name, code in _functions(co).items():
+            ids[name] = hashlib.sha256(code).hexdigest()[:16]
+    return ids
+
+
 if __name__ == "__main__":
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = sys.argv[1:]
     so = args.pop(0) if args and args[0].endswith(".so") else os.path.join(root, "fisher-nerf-customized_amd", "fisher_rast", "libfisher_rast.so")
+    if args == ["--all"]:
+        for name, cid in sorted(all_code_ids(so).items()):
+            print(cid, name)
+        sys.exit(0)
     for k in (args or ["k_fisher_tile_v4", "k_preprocess_views", "k_sort_tiles"]):
         print(k, kernel_code_id(so, k))
