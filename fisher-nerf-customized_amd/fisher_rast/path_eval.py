@@ -39,6 +39,67 @@ def rollout(start_c2w, actions, forward_step_size=0.065, turn_angle=10.):
     return out
 
 
+def rollout_device(start_c2w, path_actions, forward_step_size=0.065, turn_angle=10., *, cam_height=None, queue_size=None, device=None,
+                   return_c2w=False):
+    """The roll-out and the inversion of every pose on the device (fisher_occ.h: fr_rollout_actions, binary64, each inverse rounded once
+    to binary32): action lists -> (w2c float32 [n_paths, Q, 4, 4] on the device, zeros behind a list; the lists' lengths).
+    Q = queue_size or the longest list; with return_c2w also the poses, float64 [n_paths, Q, 4, 4].  What `poses_w2c=` of
+    evaluate_paths / evaluate_paths_popgs takes for action lists that do not come from `plan_actions`."""
+    import ctypes
+    from . import _lib
+    lengths = [len(a) for a in path_actions]
+    Q = int(queue_size) if queue_size is not None else max(lengths + [1])
+    if not 1 <= Q <= _lib.FR_ACTION_MAX_QUEUE:
+        raise ValueError(f"the longest action list may have 1 .. {_lib.FR_ACTION_MAX_QUEUE} actions, got {Q}")
+    if max(lengths + [0]) > Q:
+        raise ValueError(f"an action list has {max(lengths)} actions, queue_size is {Q}")
+    start = np.array(start_c2w.detach().cpu().numpy() if isinstance(start_c2w, torch.Tensor) else start_c2w, dtype=np.float64)
+    if start.shape != (4, 4):
+        raise ValueError(f"start_c2w must be 4 x 4, got {start.shape}")
+    if cam_height is not None:
+        start[1, 3] = cam_height
+    n = len(path_actions)
+    acts = np.zeros((n, Q), np.uint8)
+    for i, a in enumerate(path_actions):
+        a = np.asarray(a, dtype=np.int64).reshape(-1)
+        if len(a) and (a.min() < 0 or a.max() > 255):
+            raise ValueError("actions must fit a byte")
+        acts[i, :len(a)] = a
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    w2c = torch.empty((n, Q, 4, 4), dtype=torch.float32, device=dev)
+    c2w = torch.empty((n, Q, 4, 4), dtype=torch.float64, device=dev) if return_c2w else None
+    if n:
+        lib = _lib.load()
+        acts_d = torch.from_numpy(acts).to(dev)
+        lens_d = torch.tensor(lengths, dtype=torch.int32).to(dev)
+        start_a = (ctypes.c_double * 16)(*[float(v) for v in start.reshape(-1)])
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(lib.fr_rollout_actions(start_a, acts_d.data_ptr(), lens_d.data_ptr(), n, Q, float(forward_step_size), float(turn_angle),
+                                              w2c.data_ptr(), None if c2w is None else c2w.data_ptr(), stream), "fr_rollout_actions")
+    return (w2c, lengths, c2w) if return_c2w else (w2c, lengths)
+
+
+def _check_poses_w2c(poses_w2c, path_actions, dev):
+    """the device poses of `poses_w2c=`: [n_paths, Q, 4, 4] float32 on the scorer's device, Q at least the longest list"""
+    if not isinstance(poses_w2c, torch.Tensor):
+        raise ValueError("poses_w2c must be a torch tensor [n_paths, Q, 4, 4] on the device")
+    n, longest = len(path_actions), max([len(a) for a in path_actions] + [0])
+    if poses_w2c.dim() != 4 or tuple(poses_w2c.shape[2:]) != (4, 4) or poses_w2c.shape[0] != n or poses_w2c.shape[1] < longest:
+        raise ValueError(f"poses_w2c has shape {tuple(poses_w2c.shape)}, expected [{n}, Q >= {longest}, 4, 4]")
+    if poses_w2c.dtype != torch.float32:
+        raise ValueError(f"poses_w2c must be float32, got {poses_w2c.dtype}")
+    if poses_w2c.device != torch.device(dev):
+        raise ValueError(f"poses_w2c lives on {poses_w2c.device}, the map on {dev}")
+    return poses_w2c
+
+
+def _gather_w2c(poses_w2c, pairs):
+    """poses_w2c[path, step - 1] for (path, step) pairs, gathered on the device"""
+    idx = torch.tensor([[i, s - 1] for i, s in pairs], dtype=torch.long).to(poses_w2c.device)
+    return poses_w2c[idx[:, 0], idx[:, 1]].contiguous()
+
+
 def pose_log_det(pose_H, pose_reg=0.0):
     """log det(pose_H + pose_reg I) of a [..., 6, 6] batch, in float64 (as NumPy).  A determinant <= 0 gives -inf: the
     reference's torch.log(torch.linalg.det(pose_H)) of a singular matrix."""
@@ -50,14 +111,18 @@ def pose_log_det(pose_H, pose_reg=0.0):
 
 def evaluate_paths(scorer, start_c2w, path_actions, final_EIGs, H_train, *, forward_step_size=0.065, turn_angle=10.,
                    H_reg_lambda=0.1, acc_H_train_every=5, path_point_weight=1.0, path_pose_weight=0.0,
-                   path_end_weight=0.0, vol_weighted_H=False, gs_pts_cnt=1.0, cam_height=None, pose_fisher=False, pose_reg=0.0):
+                   path_end_weight=0.0, vol_weighted_H=False, gs_pts_cnt=1.0, cam_height=None, pose_fisher=False, pose_reg=0.0,
+                   poses_w2c=None):
     """Returns the list of total_path_EIG values (tester 1713-1718).  `scorer` is a FisherScorer of the current map,
     `H_train` the [P,C] keyframe accumulator.
     The reference adds `path_pose_weight * log(det(pose_H))` at EVERY step of a path (tester 1697-1701), with the identity
     placeholder as pose_H: a zero term.  pose_fisher=False keeps that (the term is left out; the result is what it always was).
     pose_fisher=True takes pose_H from `scorer.pose_fisher` -- the camera-pose Fisher information of the step's view, every step of
     every path in one batched call -- and adds `path_pose_weight * log det(pose_H + pose_reg I)` (float64) per step, in the
-    reference's order of the terms; a determinant <= 0 adds -inf, as the reference's log(det) of a singular matrix would."""
+    reference's order of the terms; a determinant <= 0 adds -inf, as the reference's log(det) of a singular matrix would.
+    poses_w2c: a device tensor float32 [n_paths, Q, 4, 4] holding the inverse of the pose after every action of every path
+    (`PathPlanOps.plan_actions`' w2c, or `rollout_device`); with it nothing is rolled out or inverted on the host, and `start_c2w`,
+    the step sizes and `cam_height` are not read."""
     dev = scorer.dev
     P, C = scorer.P, scorer.columns
     start = np.array(start_c2w, dtype=np.float64, copy=True)
@@ -66,15 +131,21 @@ def evaluate_paths(scorer, start_c2w, path_actions, final_EIGs, H_train, *, forw
     n_paths = len(path_actions)
     # accumulation steps: 1-based step s with (s + 1) % acc == 0
     acc_steps = [[s for s in range(1, len(a) + 1) if (s + 1) % acc_H_train_every == 0] for a in path_actions]
-    poses = [rollout(start, a, forward_step_size, turn_angle) for a in path_actions]
+    if poses_w2c is not None:
+        poses_w2c = _check_poses_w2c(poses_w2c, path_actions, dev)
+    else:
+        poses = [rollout(start, a, forward_step_size, turn_angle) for a in path_actions]
     totals = [0.0] * n_paths
     point_terms = [[] for _ in range(n_paths)]
     H_path = {i: H_train.clone() for i in range(n_paths) if acc_steps[i]}
     rounds = max((len(s) for s in acc_steps), default=0)
     for m in range(rounds):
         active = [i for i in range(n_paths) if len(acc_steps[i]) > m]
-        c2w = np.stack([poses[i][acc_steps[i][m] - 1] for i in active])
-        w2c = torch.from_numpy(np.linalg.inv(c2w)).float().to(dev)
+        if poses_w2c is not None:
+            w2c = _gather_w2c(poses_w2c, [(i, acc_steps[i][m]) for i in active])
+        else:
+            c2w = np.stack([poses[i][acc_steps[i][m] - 1] for i in active])
+            w2c = torch.from_numpy(np.linalg.inv(c2w)).float().to(dev)
         H_inv = torch.stack([torch.reciprocal(H_path[i] + H_reg_lambda) for i in active])
         if vol_weighted_H:
             H_inv = H_inv / gs_pts_cnt
@@ -90,10 +161,14 @@ def evaluate_paths(scorer, start_c2w, path_actions, final_EIGs, H_train, *, forw
     if pose_fisher:
         # every step of every path in one call (the scorer splits it by its launch limit); the terms summed in the reference's order:
         # per step the pose term, then the point term where the step is an accumulation step
-        all_c2w = np.concatenate([poses[i] for i in range(n_paths)]) if n_paths else np.zeros((0, 4, 4))
         pose_terms = np.zeros(0)
-        if len(all_c2w):
-            w2c_all = torch.from_numpy(np.linalg.inv(all_c2w)).float().to(dev)
+        if poses_w2c is not None:
+            steps = [(i, s) for i in range(n_paths) for s in range(1, len(path_actions[i]) + 1)]
+            w2c_all = _gather_w2c(poses_w2c, steps) if steps else None
+        else:
+            all_c2w = np.concatenate([poses[i] for i in range(n_paths)]) if n_paths else np.zeros((0, 4, 4))
+            w2c_all = torch.from_numpy(np.linalg.inv(all_c2w)).float().to(dev) if len(all_c2w) else None
+        if w2c_all is not None:
             pose_terms = path_pose_weight * pose_log_det(scorer.pose_fisher(w2c_all), pose_reg)
         k0 = 0
         for i in range(n_paths):
@@ -167,14 +242,16 @@ def popgs_rows_from_flat(H_diag, P):
 
 def evaluate_paths_popgs(slam, start_c2w, path_actions, final_EIGs, H_train_diag, *, criterion="topt", lam=1e-6, K=4,
                          forward_step_size=0.065, turn_angle=10., acc_H_train_every=5, path_point_weight=1.0,
-                         path_end_weight=0.0, object_path_end_weight=0.0, cam_height=None, probes=None, chunk_bytes=4 << 30):
+                         path_end_weight=0.0, object_path_end_weight=0.0, cam_height=None, probes=None, chunk_bytes=4 << 30,
+                         poses_w2c=None):
     """The list of total_path_EIG values of `path_evaluation_popgs` (tester 2121-2193), one per path.
     `slam`: a GaussianObjectSLAM with the grafted `_pose_probe_rows`; `H_train_diag`: what `compute_H_train_popgs` returns.
     `probes`: None draws the K upstream-gradient images of every accumulation step with torch.randn on the device; otherwise a
     callable probes(path_index, acc_index) -> [K, 3, H, W] (acc_index counts the path's accumulation steps from 0).  The
     reference's random stream (one draw per step, used or not) is not reproduced.
     Memory: one round holds paths x K x P x 44 bytes of probe rows (1.85 GB at 21 paths, K = 4, P = 500k; rounds beyond
-    `chunk_bytes` are cut into several launches) beside the state, P x 44 bytes per path with two or more accumulation steps."""
+    `chunk_bytes` are cut into several launches) beside the state, P x 44 bytes per path with two or more accumulation steps.
+    poses_w2c: as in `evaluate_paths` -- the device poses [n_paths, Q, 4, 4] in place of the host roll-out and inversion."""
     from . import ops
     crit = str(criterion).lower()
     if crit not in ("topt", "dopt"):
@@ -186,7 +263,10 @@ def evaluate_paths_popgs(slam, start_c2w, path_actions, final_EIGs, H_train_diag
     n_paths = len(path_actions)
     order, rounds = popgs_round_schedule([len(a) for a in path_actions], acc_H_train_every)
     place = {i: r for r, i in enumerate(order)}
-    poses = [rollout(start, a, forward_step_size, turn_angle) for a in path_actions]
+    if poses_w2c is not None:
+        poses_w2c = _check_poses_w2c(poses_w2c, path_actions, slam.params['means3D'].device)
+    else:
+        poses = [rollout(start, a, forward_step_size, turn_angle) for a in path_actions]
     point_terms = [[] for _ in range(n_paths)]
     if rounds:
         P = int(slam.params['means3D'].shape[0])
@@ -201,8 +281,11 @@ def evaluate_paths_popgs(slam, start_c2w, path_actions, final_EIGs, H_train_diag
         for v0, v1 in zip(cuts[:-1], cuts[1:]):
             part = rnd[v0:v1]
             assert all(place[i] == v0 + k for k, (i, _, _) in enumerate(part))
-            c2w = np.stack([poses[i][s - 1] for i, s, _ in part])
-            w2c = torch.from_numpy(np.linalg.inv(c2w)).float().to(dev)
+            if poses_w2c is not None:
+                w2c = _gather_w2c(poses_w2c, [(i, s) for i, s, _ in part])
+            else:
+                c2w = np.stack([poses[i][s - 1] for i, s, _ in part])
+                w2c = torch.from_numpy(np.linalg.inv(c2w)).float().to(dev)
             zs = None if probes is None else [z for i, _, _ in part for z in probes(i, m)]
             rows, vis = slam._pose_probe_rows(w2c, K, zs)
             writes = v1 <= n_state

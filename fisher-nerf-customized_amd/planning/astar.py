@@ -5,6 +5,8 @@ In scope (same names, arguments and return conventions as the reference):
     build_frontiers (540-683)          generate_candidate (1406-1430)  generate_candidate_object (1432-1469)
     the free-space filter of the candidate loop (1383-1401)            sample_random_candidate (782-837)
     setup_start + planning (449-538, 1591-1777): `PathPlanOps`, one cost field from the start, paths to all goals
+    `PathPlanOps.plan_actions`: the loop of NavTester.action_planning (tester_gaussians_navigation.py:2231-2330), every goal's path
+    and action list and the poses along it from two calls and one host read (`ActionPlan`)
 Visualisation, the RRT planner and the VLM frontier selection are NOT rebuilt: they are reference Python that stays as it
 is.  `OccupancyOps.install(cls)` / `PathPlanOps.install(cls)` graft the accelerated methods onto the reference class;
 `AstarPlanner` below is the same operator surface as a standalone object for tests and benchmarks.
@@ -298,6 +300,37 @@ class OccupancyOps:
         return planner_cls
 
 
+class ActionPlan:
+    """What `PathPlanOps.plan_actions` returns.  Per goal, in goal order (G goals, Q = queue_size):
+        paths       the grid paths as plan_paths gives them      n_actions  int32 [G], -1 without a path
+        keep        uint8 [G]: has a path, and no earlier goal with a path has the same action list
+        actions     uint8 [G, Q]      map_xz  int32 [G, Q, 2]    c2w_xz  float64 [G, Q, 2]   (zeros behind a list)
+        w2c         DEVICE float32 [G, Q, 4, 4]: the inverse of the pose after each action; `kept_w2c()` gathers the kept rows there
+    and of the kept goals only, as the reference's lists:
+        kept_index, valid_global_points, path_actions, paths_arr (a path of one point has the goal cell appended, as the
+        reference leaves it), world_path / map_path (the `action == 1` entries: tester 1707-1711)
+    `triple()` is action_planning's return value; `reads` the host reads the call made."""
+
+    def __init__(self, goal_c2ws, paths, n_actions, keep, actions, map_xz, c2w_xz, w2c, finishes, reads):
+        self.paths, self.n_actions, self.keep, self.actions, self.map_xz, self.c2w_xz, self.w2c, self.reads = \
+            paths, n_actions, keep, actions, map_xz, c2w_xz, w2c, reads
+        self.kept_index = [int(k) for k in np.nonzero(keep)[0]]
+        self.valid_global_points = [goal_c2ws[k] for k in self.kept_index]
+        self.path_actions = [[int(a) for a in actions[k, :n_actions[k]]] for k in self.kept_index]
+        self.paths_arr = [np.concatenate([paths[k], finishes[k][None, :]], axis=0) if len(paths[k]) == 1 else paths[k] for k in self.kept_index]
+        fwd = [np.nonzero(actions[k, :n_actions[k]] == 1)[0] for k in self.kept_index]
+        self.world_path = [[c2w_xz[k, j].copy() for j in f] for k, f in zip(self.kept_index, fwd)]
+        self.map_path = [[map_xz[k, j].astype(np.int64) for j in f] for k, f in zip(self.kept_index, fwd)]
+
+    def triple(self):
+        return self.valid_global_points, self.path_actions, self.paths_arr
+
+    def kept_w2c(self, rows=None):
+        """w2c of the kept goals (or of `rows`, positions in the kept lists), gathered on the device: [n, Q, 4, 4]"""
+        idx = self.kept_index if rows is None else [self.kept_index[r] for r in rows]
+        return self.w2c[torch.as_tensor(idx, dtype=torch.long, device=self.w2c.device)]
+
+
 class PathPlanOps:
     """Mixin with the action-planning stage: `setup_start` + `planning` (astar.py:449-538, 1591-1777) and the batched `plan_paths`.
 
@@ -421,6 +454,96 @@ class PathPlanOps:
         """ the path to one goal (row, col): (M, 2) int array in x-z order, or np.array([]) """
         return self.plan_paths([self._plan_cell(goal)])[0]
 
+    # -- astar.py:1372-1381 ------------------------------------------------------------------------------------------
+    def _map_center_host(self):
+        """map_center on the host, in its own dtype: the copy _occ_cfg holds until the tensor is replaced or written (no read per call)"""
+        if isinstance(self.map_center, torch.Tensor):
+            self._occ_cfg()
+            return self._occ_mc_held[2]
+        return np.asarray(self.map_center)
+
+    def _plan_to_map(self, coord):
+        """convert_to_map (astar.py:1372-1376) on the held copy of the map centre"""
+        map_center = self._map_center_host()
+        cam_pos_x = int((coord[0] - map_center[0]) / self.cell_size + self.grid_dim[0] // 2)
+        cam_pos_z = int((coord[1] - map_center[1]) / self.cell_size + self.grid_dim[1] // 2)
+        return np.array([cam_pos_x, cam_pos_z])
+
+    def convert_to_map(self, coord):
+        return self._plan_to_map(coord)
+
+    def convert_to_world(self, coord):
+        map_center = self._map_center_host()
+        return (coord - np.asarray(self.grid_dim) / 2) * self.cell_size + map_center
+
+    # -- tester_gaussians_navigation.py:2227-2330 --------------------------------------------------------------------
+    @torch.no_grad()
+    def plan_actions(self, goal_c2ws, agent_c2w, *, forward_step_size, turn_angle, queue_size, cam_height=None):
+        """The loop of NavTester.action_planning after `setup_start`: [G, 4, 4] goal poses and the agent's pose -> an ActionPlan.
+        Goals and start become cells on the host as the tester makes them (convert_to_map(...)[[1, 0]], the goal's height replaced by the
+        agent's); fr_plan_paths and fr_plan_actions run back to back on the device; ONE host read brings lengths, paths, action
+        counts, keep flags, actions, cells and x-z positions over (a path longer than PLAN_MAX_LEN points repeats the calls and the
+        read once, as plan_paths does).  The poses' inverses stay on the device (ActionPlan.w2c)."""
+        lib = _lib.load()
+        plan = self._plan
+        dev = plan["field"].device
+        Q = int(queue_size)
+        if not 1 <= Q <= _lib.FR_ACTION_MAX_QUEUE:
+            raise ValueError(f"queue_size must be 1 .. {_lib.FR_ACTION_MAX_QUEUE}, got {queue_size}")
+        if not (float(forward_step_size) > 0 and float(turn_angle) > 0):
+            raise ValueError("forward_step_size and turn_angle must be positive")
+        agent = np.array(agent_c2w.detach().cpu().numpy() if isinstance(agent_c2w, torch.Tensor) else agent_c2w)
+        if agent.shape != (4, 4):
+            raise ValueError(f"agent_c2w must be 4 x 4, got {agent.shape}")
+        goal_np = goal_c2ws.detach().cpu().numpy() if isinstance(goal_c2ws, torch.Tensor) else np.asarray(goal_c2ws)
+        goal_np = goal_np.reshape(-1, 4, 4) if goal_np.size else np.zeros((0, 4, 4), np.float32)
+        current_agent_pos = agent[:3, 3]
+        start = self._plan_to_map(current_agent_pos[[0, 2]])[[1, 0]]
+        if self._plan_cell(start) != plan["start"]:
+            raise ValueError(f"the agent stands on cell {self._plan_cell(start)}, the cost field was set up from {plan['start']}: run setup_start first")
+        G = int(goal_np.shape[0])
+        finishes = np.zeros((G, 2), np.int64)
+        for k, pose_np in enumerate(goal_np):
+            pos_np = pose_np[:3, 3].copy()
+            pos_np[1] = current_agent_pos[1]
+            finishes[k] = self._plan_to_map(pos_np[[0, 2]])[[1, 0]]
+        height = float(self.cam_height if cam_height is None else cam_height)
+        if G == 0:
+            return ActionPlan(goal_np, [], np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros((0, Q), np.uint8), np.zeros((0, Q, 2), np.int32),
+                              np.zeros((0, Q, 2)), torch.zeros((0, Q, 4, 4), dtype=torch.float32, device=dev), finishes, reads=0)
+        if np.abs(finishes).max() >= 2 ** 31:
+            raise ValueError("a goal lies too far outside the map for a 32-bit cell")
+        g = torch.from_numpy(finishes.astype(np.int32)).to(dev)
+        poses = torch.from_numpy(np.ascontiguousarray(goal_np, np.float32).reshape(G, 16)).to(dev)
+        agent_a = (ctypes.c_double * 16)(*[float(v) for v in agent.reshape(-1)])
+        w2c = torch.empty((G, Q, 4, 4), dtype=torch.float32, device=dev)
+        shortcut = 1 if getattr(self, "shortcut_path", True) else 0
+        max_len = int(self.PLAN_MAX_LEN)
+        reads = 0
+        while True:
+            # one buffer, one copy down: [c2w_xz f64 | lengths, paths, n_actions, map_xz i32 | keep, actions u8], each part 8-byte aligned
+            sizes = (16 * G * Q, 4 * G, 8 * G * max_len, 4 * G, 8 * G * Q, G, G * Q)
+            offs = np.concatenate([[0], np.cumsum([(s + 7) & ~7 for s in sizes])])
+            out = torch.empty((int(offs[-1]),), dtype=torch.uint8, device=dev)
+            part = [out[int(o):int(o) + s] for o, s in zip(offs[:-1], sizes)]
+            ptr = [p.data_ptr() for p in part]
+            _lib.check(lib.fr_plan_paths(ctypes.byref(plan["cfg"]), plan["field"].data_ptr(), plan["occ_plan"].data_ptr(), plan["start"][0],
+                                         plan["start"][1], g.data_ptr(), G, shortcut, ptr[2], max_len, ptr[1], self._stream()), "fr_plan_paths")
+            _lib.check(lib.fr_plan_actions(ctypes.byref(plan["cfg"]), ptr[2], max_len, ptr[1], g.data_ptr(), poses.data_ptr(), G, agent_a, height,
+                                           float(forward_step_size), float(turn_angle), Q, float(self.cell_size), ptr[6], ptr[3], ptr[5],
+                                           w2c.data_ptr(), ptr[0], ptr[4], self._stream()), "fr_plan_actions")
+            host = self._plan_read(out)
+            reads += 1
+            h = [host[int(o):int(o) + s] for o, s in zip(offs[:-1], sizes)]
+            lens = h[1].view(np.int32)
+            if (lens >= 0).all():
+                break
+            max_len = int(self.grid_dim[0]) * int(self.grid_dim[1]) + 1
+        pts = h[2].view(np.int32).reshape(G, max_len, 2)
+        paths = [pts[k, :lens[k]].astype(np.int64) if lens[k] > 0 else np.array([]) for k in range(G)]
+        return ActionPlan(goal_np, paths, h[3].view(np.int32).copy(), h[5].copy(), h[6].reshape(G, Q).copy(), h[4].view(np.int32).reshape(G, Q, 2).copy(),
+                          h[0].view(np.float64).reshape(G, Q, 2).copy(), w2c, finishes, reads=reads)
+
     def plan_field(self):
         """(cost float32 [H, W], -1 where the start does not reach; parent int32 [H, W, 2] = (row, col), -1 there)"""
         words = self._plan_read(self._plan["field"]).view(np.uint64)
@@ -434,9 +557,12 @@ class PathPlanOps:
     @classmethod
     def install(cls, planner_cls):
         """Graft the planning stage onto the reference's AstarPlanner class (after OccupancyOps.install, whose internals it uses)."""
-        for name in ("setup_start", "planning", "plan_paths", "plan_field", "_plan_cell", "_plan_read", "_localization_error", "occ_map_np",
-                     "free_space_np", "PLAN_MAX_LEN"):
+        for name in ("setup_start", "planning", "plan_paths", "plan_actions", "plan_field", "_plan_cell", "_plan_to_map", "_map_center_host", "_plan_read", "_localization_error",
+                     "occ_map_np", "free_space_np", "PLAN_MAX_LEN"):
             setattr(planner_cls, name, cls.__dict__[name])
+        for name in ("convert_to_map", "convert_to_world"):                     # the reference class has its own
+            if not hasattr(planner_cls, name):
+                setattr(planner_cls, name, cls.__dict__[name])
         cls._localization_error(planner_cls)
         return planner_cls
 

@@ -135,6 +135,41 @@ int fr_plan_paths(const fr_occ_cfg* cfg, const uint64_t* field, const uint8_t* o
                   const int32_t* goals, int32_t n_goals, int32_t shortcut, int32_t* paths, int32_t max_len, int32_t* lengths,
                   fr_stream_t stream);
 
+/* ---- action planning: every goal's path to the agent's action list, and the poses along it -----------------------------------
+ * Replaces the second half of NavTester.action_planning (tester_gaussians_navigation.py:2246-2330): the waypoint follower that
+ * walks a grid path with the agent's three actions (1 forward by forward_step_size along the camera's +z, 2 / 3 yaw by -/+
+ * turn_angle degrees), the final re-orientation towards the goal pose, the duplicate-list filter -- and the roll-out and inversion
+ * of the poses that the path evaluation repeats on the host (1684-1687).  Binary64 arithmetic (csrc/fr_action_math.h), quirks kept.
+ *
+ *   fr_plan_actions     paths int32 [n_goals][max_len][2] and lengths int32 [n_goals] as fr_plan_paths leaves them; goals int32
+ *                       [n_goals][2] = (row, col), read only for a path of one point, which gets it appended as the reference does;
+ *                       goals_c2w float32 [n_goals][16] row-major; agent_c2w: HOST double [16], taken to be rigid, its height
+ *                       replaced by cam_height.  cell_size is the planner's own binary64 value (cfg's binary32 one is not read here:
+ *                       the reference converts cells with the Python float); the map centre is cfg's, promoted.  Outputs (device):
+ *                         actions   uint8 [n_goals][queue_size]
+ *                         n_actions int32 [n_goals]                    -1 where lengths[g] <= 0: the goal has no path
+ *                         keep      uint8 [n_goals]                    1 where the goal has a path and no earlier goal with a path
+ *                                                                      produced the same list (an empty list is a list)
+ *                         w2c       float32 [n_goals][queue_size][16]  the inverse of the pose after each action, rounded once
+ *                         c2w_xz    float64 [n_goals][queue_size][2]   the pose's x and z after each action
+ *                         map_xz    int32 [n_goals][queue_size][2]     their cell, int((v - centre) / cell_size + grid_dim // 2)
+ *                       Entries past n_actions[g] are written as zeros.  The entries with action 1 are the reference's world_path /
+ *                       map_path.  Two launches: the lists, then the duplicate search.
+ *   fr_rollout_actions  the roll-out alone, for lists from elsewhere: start_c2w HOST double [16] (used as it is), actions uint8
+ *                       [n_lists][queue_size], n_actions int32 [n_lists] (negative counts as 0); w2c float32 [n_lists][queue_size][16],
+ *                       c2w float64 [n_lists][queue_size][16] or null, zeros past a list's end.  Given fr_plan_actions' lists and its
+ *                       start, w2c comes out bit for bit the same.
+ * queue_size: 1 .. FR_ACTION_MAX_QUEUE, else FR_EINVAL.  n_goals / n_lists = 0 returns FR_OK without a launch. */
+#define FR_ACTION_MAX_QUEUE 128
+
+int fr_plan_actions(const fr_occ_cfg* cfg, const int32_t* paths, int32_t max_len, const int32_t* lengths, const int32_t* goals,
+                    const float* goals_c2w, int32_t n_goals, const double* agent_c2w, double cam_height, double forward_step_size,
+                    double turn_angle, int32_t queue_size, double cell_size, uint8_t* actions, int32_t* n_actions, uint8_t* keep,
+                    float* w2c, double* c2w_xz, int32_t* map_xz, fr_stream_t stream);
+
+int fr_rollout_actions(const double* start_c2w, const uint8_t* actions, const int32_t* n_actions, int32_t n_lists, int32_t queue_size,
+                       double forward_step_size, double turn_angle, float* w2c, double* c2w, fr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
