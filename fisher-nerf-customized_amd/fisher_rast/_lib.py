@@ -224,6 +224,7 @@ FR_PLAN_STATUS_WORDS = 4
 FR_PLAN_TILE = 64
 FR_PLAN_UNREACHED = 0xFFFFFFFFFFFFFFFF
 FR_ACTION_MAX_QUEUE = 128
+FR_ACTION_OBJECT_MAX = 200
 
 
 # every symbol include/fisher_rast.h and include/fisher_occ.h declare
@@ -243,7 +244,8 @@ EXPORTS = (
     "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
     "fr_occ_ring_candidates", "fr_occ_free_candidates",
     "fr_plan_workspace_bytes", "fr_plan_round_cap", "fr_plan_grid", "fr_plan_tiers", "fr_plan_field", "fr_plan_paths",
-    "fr_plan_actions", "fr_rollout_actions",
+    "fr_plan_actions", "fr_rollout_actions", "fr_plan_actions_object",
+    "fr_occ_object_cells", "fr_occ_grid_candidates",
     "fr_cloud_index_bytes", "fr_cloud_index_workspace_bytes", "fr_cloud_query_workspace_bytes", "fr_cloud_index_build", "fr_cloud_query",
     "fr_dbscan_workspace_bytes", "fr_target_select_workspace_bytes", "fr_dbscan", "fr_target_select",
     "fr_view_metrics_workspace_bytes", "fr_view_metrics", "fr_view_metrics_summary",
@@ -255,8 +257,8 @@ _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_action.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_eval.hip", "fr_objloss.hip", "fr_math.h",
-                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_action_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_eval_math.h", "fr_objloss_math.h", "fr_internal.h", "fr_block.h", "fr_ssim_tile.h")] + \
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_action.hip", "fr_action_object.hip", "fr_goal.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_eval.hip", "fr_objloss.hip", "fr_math.h",
+                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_action_math.h", "fr_action_object_math.h", "fr_goal_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_eval_math.h", "fr_objloss_math.h", "fr_internal.h", "fr_block.h", "fr_ssim_tile.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
@@ -504,6 +506,14 @@ def load():
         lib.fr_plan_actions.argtypes = [occp, vp, i32, vp, vp, vp, i32, f64p, f64, f64, f64, i32, f64, vp, vp, vp, vp, vp, vp, vp]
         lib.fr_rollout_actions.restype = ctypes.c_int
         lib.fr_rollout_actions.argtypes = [f64p, vp, vp, i32, i32, f64, f64, vp, vp, vp]
+    if hasattr(lib, "fr_plan_actions_object"):
+        vp, i32, f64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_float
+        lib.fr_plan_actions_object.restype = ctypes.c_int
+        lib.fr_plan_actions_object.argtypes = [occp, vp, i32, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_double), f64, f64, f64, f64] + [vp] * 9
+        lib.fr_occ_object_cells.restype = ctypes.c_int
+        lib.fr_occ_object_cells.argtypes = [occp, vp, i32, i32, vp, i32, vp, vp, ctypes.c_size_t, vp]
+        lib.fr_occ_grid_candidates.restype = ctypes.c_int
+        lib.fr_occ_grid_candidates.argtypes = [occp, vp, i32, vp, vp, i32, f32, f32, i32, i32, i32, f32, ctypes.c_uint32, vp, i32, vp, vp, vp]
     if hasattr(lib, "fr_cloud_query"):
         for f in (lib.fr_cloud_index_bytes, lib.fr_cloud_index_workspace_bytes, lib.fr_cloud_query_workspace_bytes):
             f.restype = ctypes.c_size_t

@@ -8,7 +8,14 @@ host read.  `plan_best_path` sorts the goals by EIG, plans, and scores at most 2
 What differs from the reference: a kept path with no action makes the reference divide by zero; here it is
 left out of the scoring and listed in the result.  The reference pairs the i-th KEPT path with EIGs[i] -- it zips the filtered lists
 against the unfiltered EIGs -- which is kept; `align_EIGs=True` pairs a path with its own goal's EIG instead.
-Not rebuilt: action_planning_object_adv / _object, path_object_evaluation, the PNG and pickle outputs.
+
+The object round (tester 1738-1818): `action_planning_object_adv` is `setup_start` + `PathPlanOps.plan_actions_object`, and
+`plan_best_object_path` chains `GoalSelectOps.global_object_planning`, the object map's H_train, the adv follower and the scoring of at
+most 21 paths.  What differs there is said in INTEGRATION.md section 4b.3; in short: for criteria "fisher" the reference's
+path_evaluation overwrites every point_EIG with 0 and takes log det of a placeholder eye(6), so a path's value is
+object_path_end_weight * final_EIG (final_EIG / len when that weight is 0) -- computed here on the host, with no Hessian launched.
+Not rebuilt: action_planning_object (superseded by _adv in the reference), path_object_evaluation (its call is commented out there),
+num_uniform_H_train, draw_final_map, the PNG and pickle outputs.
 """
 import numpy as np
 import torch
@@ -94,4 +101,91 @@ def plan_best_path(scorer_or_slam, planner, global_points, EIGs, H_train, curren
         five = (plan.path_actions[best], plan.map_path[best], plan.valid_global_points[best], plan.world_path[best], plan.paths_arr[best])
     out = BestPath(five + (list(totals),))
     out.plan, out.scored, out.skipped_empty, out.best_index, out.global_points, out.EIGs = plan, scored, skipped, best, global_points, EIGs
+    return out
+
+
+# ---- the object round ------------------------------------------------------------------------------------------------------------------
+
+def _object_step_cfg(cfg):
+    """forward_step_size and turn_angle from keyword arguments or a slam_config-shaped mapping (the adv follower has no queue size)"""
+    missing = [k for k in _STEP_KEYS[:2] if k not in cfg]
+    if missing:
+        raise ValueError(f"the step configuration lacks {missing}")
+    return {k: cfg[k] for k in _STEP_KEYS[:2]}
+
+
+def action_planning_object_adv(planner, global_points, current_agent_pose, gaussian_points, t, return_plan=False, **step_cfg):
+    """NavTester.action_planning_object_adv on a planner with PathPlanOps: (valid_global_points, path_actions, paths_arr) -- the
+    pruned paths -- or the ObjectActionPlan that holds them with return_plan=True.  step_cfg: forward_step_size, turn_angle."""
+    step = _object_step_cfg(step_cfg)
+    current_agent_pose = _np(current_agent_pose)
+    start = planner._plan_to_map(current_agent_pose[[0, 2], 3])[[1, 0]]
+    planner.setup_start(start, gaussian_points, t)
+    plan = planner.plan_actions_object(_np(global_points), current_agent_pose, **step)
+    return plan if return_plan else plan.triple()
+
+
+def fisher_object_path_value(final_EIG, n_actions, object_path_end_weight=0.0):
+    """total_path_EIG of path_evaluation (tester 1900-1964) as the reference computes it today: point_EIG is overwritten with 0
+    (1933, 1940) and pose_EIG is log det of the object map's placeholder eye(6), 0 -- what is left is the end term"""
+    final = float(final_EIG.item() if hasattr(final_EIG, "item") else final_EIG)
+    if object_path_end_weight > 0:
+        return float(object_path_end_weight) * final
+    return final / int(n_actions)
+
+
+class BestObjectPath(tuple):
+    """plan_best_object_path's result: the reference's (best_path, best_map_path, best_goal, best_world_path, best_global_path,
+    global_points, EIGs); as attributes also `plan` (the ObjectActionPlan), `totals`, `scored` (positions in the kept lists, in
+    order), `best_index` (position in the kept lists or None), `candidate_object_pose`."""
+
+
+def plan_best_object_path(obj_slam, slam, planner, current_agent_pose, expansion, t, cfg, criteria, H_train=None):
+    """NavTester.plan_best_object_path (tester 1738-1818) on a planner with GoalSelectOps and PathPlanOps.  obj_slam / slam: the object
+    and the scene SLAM objects (`gaussian_points`; obj_slam's pose_eval / pose_eval_popgs, compute_H_train_popgs and, optionally,
+    pose_proposal).  cfg: a mapping with forward_step_size, turn_angle and, optionally, object_path_end_weight, path_end_weight,
+    path_point_weight, acc_H_train_every, lam, K.  criteria: "fisher", or "topt" / "dopt".  H_train: the POp-GS prior when the
+    caller already holds it (not read for "fisher")."""
+    crit = str(criteria).lower()
+    current_agent_pose = _np(current_agent_pose)
+    current_agent_pos = current_agent_pose[:3, 3]
+    pose_proposal_fn = getattr(obj_slam, "pose_proposal", None)
+    if crit == "fisher":
+        res = planner.global_object_planning(obj_slam.pose_eval, obj_slam.gaussian_points, slam.gaussian_points, pose_proposal_fn, expansion=expansion,
+                                             visualize=False, agent_pose=current_agent_pos)
+    else:
+        res = planner.global_object_planning(obj_slam.pose_eval_popgs, obj_slam.gaussian_points, slam.gaussian_points, pose_proposal_fn,
+                                             expansion=expansion, visualize=False, agent_pose=current_agent_pos, criterion=criteria)
+    global_points, EIGs, _, candidate_object_pose = res
+    EIGs = _np(EIGs).reshape(-1)
+    global_points = _np(global_points).reshape(-1, 4, 4)
+    sort_index = np.argsort(EIGs)[::-1]
+    global_points = global_points[sort_index]
+    EIGs = EIGs[sort_index]
+    plan = action_planning_object_adv(planner, global_points, current_agent_pose, slam.gaussian_points, t, return_plan=True, **_object_step_cfg(cfg))
+    scored = list(range(len(plan.kept_index)))[:MAX_SCORED_PATHS]
+    finals = [float(EIGs[i]) for i in scored]                    # the i-th KEPT path with EIGs[i], as the reference zips them
+    w_end = float(cfg.get("object_path_end_weight", 0.0))
+    if crit == "fisher":
+        totals = [fisher_object_path_value(f, len(plan.path_actions[i]), w_end) for i, f in zip(scored, finals)]
+        floor = -1.                                              # tester 1891
+    else:
+        if H_train is None and scored:
+            H_train = obj_slam.compute_H_train_popgs()
+        kw = {k: cfg[k] for k in ("lam", "K", "acc_H_train_every", "path_point_weight", "path_end_weight") if k in cfg}
+        totals = []
+        if scored:
+            totals = path_eval.evaluate_paths_popgs(obj_slam, current_agent_pose, [plan.path_actions[i] for i in scored], finals, H_train,
+                                                    criterion=crit, object_path_end_weight=w_end, poses_w2c=plan.kept_w2c(scored), **kw)
+        floor = -float("inf")                                    # tester 2114
+    best, best_EIG = None, floor
+    for i, total in zip(scored, totals):                         # the first maximum above the floor
+        if total > best_EIG:
+            best, best_EIG = i, total
+    if best is None:
+        five = (None, None, None, None, None)
+    else:
+        five = (plan.path_actions[best], plan.map_path[best], plan.valid_global_points[best], plan.world_path[best], plan.paths_arr[best])
+    out = BestObjectPath(five + (global_points, EIGs))
+    out.plan, out.totals, out.scored, out.best_index, out.candidate_object_pose = plan, list(totals), scored, best, candidate_object_pose
     return out

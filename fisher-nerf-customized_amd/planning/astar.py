@@ -7,8 +7,11 @@ In scope (same names, arguments and return conventions as the reference):
     setup_start + planning (449-538, 1591-1777): `PathPlanOps`, one cost field from the start, paths to all goals
     `PathPlanOps.plan_actions`: the loop of NavTester.action_planning (tester_gaussians_navigation.py:2231-2330), every goal's path
     and action list and the poses along it from two calls and one host read (`ActionPlan`)
+    `PathPlanOps.plan_actions_object`: the loop of NavTester.action_planning_object_adv (2385-2496), up to 200 actions (`ObjectActionPlan`)
+    `GoalSelectOps`: global_planning (843-1000), build_object_frontiers (686-734), generate_candidate_adv_object (1471-1588),
+    global_object_planning (1151-1346), built from the stages above
 Visualisation, the RRT planner and the VLM frontier selection are NOT rebuilt: they are reference Python that stays as it
-is.  `OccupancyOps.install(cls)` / `PathPlanOps.install(cls)` graft the accelerated methods onto the reference class;
+is.  `OccupancyOps.install(cls)` / `PathPlanOps.install(cls)` / `GoalSelectOps.install(cls)` graft the methods onto the reference class;
 `AstarPlanner` below is the same operator surface as a standalone object for tests and benchmarks.
 
 What changes underneath: the reference bins the depth samples with torch ops and then walks every occupied cell in a
@@ -331,6 +334,17 @@ class ActionPlan:
         return self.w2c[torch.as_tensor(idx, dtype=torch.long, device=self.w2c.device)]
 
 
+class ObjectActionPlan(ActionPlan):
+    """What `PathPlanOps.plan_actions_object` returns: an ActionPlan with Q = 200 whose `keep` drops a list without an action, and
+    whose `paths_arr` are the PRUNED paths (int32 [M, 2]), as action_planning_object_adv returns them; `pruned` holds every goal's
+    (an empty array without a path)."""
+
+    def __init__(self, goal_c2ws, paths, pruned, n_actions, keep, actions, map_xz, c2w_xz, w2c, finishes, reads):
+        super().__init__(goal_c2ws, [np.zeros((0, 2), np.int64)] * len(paths), n_actions, keep, actions, map_xz, c2w_xz, w2c, finishes, reads)
+        self.paths, self.pruned = paths, pruned
+        self.paths_arr = [pruned[k] for k in self.kept_index]
+
+
 class PathPlanOps:
     """Mixin with the action-planning stage: `setup_start` + `planning` (astar.py:449-538, 1591-1777) and the batched `plan_paths`.
 
@@ -476,6 +490,27 @@ class PathPlanOps:
         map_center = self._map_center_host()
         return (coord - np.asarray(self.grid_dim) / 2) * self.cell_size + map_center
 
+    def _action_inputs(self, goal_c2ws, agent_c2w):
+        """(the agent's pose float64 [4, 4], the goal poses [G, 4, 4], their cells int64 [G, 2] = (row, col)) as the tester makes them:
+        convert_to_map(...)[[1, 0]], the goal's height replaced by the agent's; the agent must stand on the cost field's start cell"""
+        plan = self._plan
+        agent = np.array(agent_c2w.detach().cpu().numpy() if isinstance(agent_c2w, torch.Tensor) else agent_c2w)
+        if agent.shape != (4, 4):
+            raise ValueError(f"agent_c2w must be 4 x 4, got {agent.shape}")
+        goal_np = goal_c2ws.detach().cpu().numpy() if isinstance(goal_c2ws, torch.Tensor) else np.asarray(goal_c2ws)
+        goal_np = goal_np.reshape(-1, 4, 4) if goal_np.size else np.zeros((0, 4, 4), np.float32)
+        current_agent_pos = agent[:3, 3]
+        start = self._plan_to_map(current_agent_pos[[0, 2]])[[1, 0]]
+        if self._plan_cell(start) != plan["start"]:
+            raise ValueError(f"the agent stands on cell {self._plan_cell(start)}, the cost field was set up from {plan['start']}: run setup_start first")
+        G = int(goal_np.shape[0])
+        finishes = np.zeros((G, 2), np.int64)
+        for k, pose_np in enumerate(goal_np):
+            pos_np = pose_np[:3, 3].copy()
+            pos_np[1] = current_agent_pos[1]
+            finishes[k] = self._plan_to_map(pos_np[[0, 2]])[[1, 0]]
+        return agent, goal_np, finishes
+
     # -- tester_gaussians_navigation.py:2227-2330 --------------------------------------------------------------------
     @torch.no_grad()
     def plan_actions(self, goal_c2ws, agent_c2w, *, forward_step_size, turn_angle, queue_size, cam_height=None):
@@ -492,21 +527,8 @@ class PathPlanOps:
             raise ValueError(f"queue_size must be 1 .. {_lib.FR_ACTION_MAX_QUEUE}, got {queue_size}")
         if not (float(forward_step_size) > 0 and float(turn_angle) > 0):
             raise ValueError("forward_step_size and turn_angle must be positive")
-        agent = np.array(agent_c2w.detach().cpu().numpy() if isinstance(agent_c2w, torch.Tensor) else agent_c2w)
-        if agent.shape != (4, 4):
-            raise ValueError(f"agent_c2w must be 4 x 4, got {agent.shape}")
-        goal_np = goal_c2ws.detach().cpu().numpy() if isinstance(goal_c2ws, torch.Tensor) else np.asarray(goal_c2ws)
-        goal_np = goal_np.reshape(-1, 4, 4) if goal_np.size else np.zeros((0, 4, 4), np.float32)
-        current_agent_pos = agent[:3, 3]
-        start = self._plan_to_map(current_agent_pos[[0, 2]])[[1, 0]]
-        if self._plan_cell(start) != plan["start"]:
-            raise ValueError(f"the agent stands on cell {self._plan_cell(start)}, the cost field was set up from {plan['start']}: run setup_start first")
+        agent, goal_np, finishes = self._action_inputs(goal_c2ws, agent_c2w)
         G = int(goal_np.shape[0])
-        finishes = np.zeros((G, 2), np.int64)
-        for k, pose_np in enumerate(goal_np):
-            pos_np = pose_np[:3, 3].copy()
-            pos_np[1] = current_agent_pos[1]
-            finishes[k] = self._plan_to_map(pos_np[[0, 2]])[[1, 0]]
         height = float(self.cam_height if cam_height is None else cam_height)
         if G == 0:
             return ActionPlan(goal_np, [], np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros((0, Q), np.uint8), np.zeros((0, Q, 2), np.int32),
@@ -544,6 +566,61 @@ class PathPlanOps:
         return ActionPlan(goal_np, paths, h[3].view(np.int32).copy(), h[5].copy(), h[6].reshape(G, Q).copy(), h[4].view(np.int32).reshape(G, Q, 2).copy(),
                           h[0].view(np.float64).reshape(G, Q, 2).copy(), w2c, finishes, reads=reads)
 
+    # -- tester_gaussians_navigation.py:2385-2496 --------------------------------------------------------------------
+    @torch.no_grad()
+    def plan_actions_object(self, goal_c2ws, agent_c2w, *, forward_step_size, turn_angle, cam_height=None):
+        """The loop of NavTester.action_planning_object_adv after `setup_start`: [G, 4, 4] goal poses and the agent's pose -> an
+        ObjectActionPlan (Q = FR_ACTION_OBJECT_MAX = 200; the planning queue does not cut these lists).  fr_plan_paths and
+        fr_plan_actions_object run back to back on the device; ONE host read brings lengths, paths, pruned paths, action counts, keep
+        flags, actions, cells and x-z positions over (a path longer than PLAN_MAX_LEN points repeats the calls and the read once, as
+        plan_actions does).  The poses' inverses stay on the device (ObjectActionPlan.w2c)."""
+        lib = _lib.load()
+        plan = self._plan
+        dev = plan["field"].device
+        Q = _lib.FR_ACTION_OBJECT_MAX
+        if not (float(forward_step_size) > 0 and float(turn_angle) > 0):
+            raise ValueError("forward_step_size and turn_angle must be positive")
+        agent, goal_np, finishes = self._action_inputs(goal_c2ws, agent_c2w)
+        G = int(goal_np.shape[0])
+        height = float(self.cam_height if cam_height is None else cam_height)
+        if G == 0:
+            return ObjectActionPlan(goal_np, [], [], np.zeros(0, np.int32), np.zeros(0, np.uint8), np.zeros((0, Q), np.uint8), np.zeros((0, Q, 2), np.int32),
+                                    np.zeros((0, Q, 2)), torch.zeros((0, Q, 4, 4), dtype=torch.float32, device=dev), finishes, reads=0)
+        if np.abs(finishes).max() >= 2 ** 31:
+            raise ValueError("a goal lies too far outside the map for a 32-bit cell")
+        g = torch.from_numpy(finishes.astype(np.int32)).to(dev)
+        poses = torch.from_numpy(np.ascontiguousarray(goal_np, np.float32).reshape(G, 16)).to(dev)
+        agent_a = (ctypes.c_double * 16)(*[float(v) for v in agent.reshape(-1)])
+        w2c = torch.empty((G, Q, 4, 4), dtype=torch.float32, device=dev)
+        shortcut = 1 if getattr(self, "shortcut_path", True) else 0
+        max_len = int(self.PLAN_MAX_LEN)
+        reads = 0
+        while True:
+            # one buffer, one copy down: [c2w_xz f64 | lengths, paths, n_actions, map_xz, pruned, pruned_len i32 | keep, actions u8], each part 8-byte aligned
+            sizes = (16 * G * Q, 4 * G, 8 * G * max_len, 4 * G, 8 * G * Q, 8 * G * (max_len + 1), 4 * G, G, G * Q)
+            offs = np.concatenate([[0], np.cumsum([(s + 7) & ~7 for s in sizes])])
+            out = torch.empty((int(offs[-1]),), dtype=torch.uint8, device=dev)
+            ptr = [out[int(o):int(o) + s].data_ptr() for o, s in zip(offs[:-1], sizes)]
+            _lib.check(lib.fr_plan_paths(ctypes.byref(plan["cfg"]), plan["field"].data_ptr(), plan["occ_plan"].data_ptr(), plan["start"][0],
+                                         plan["start"][1], g.data_ptr(), G, shortcut, ptr[2], max_len, ptr[1], self._stream()), "fr_plan_paths")
+            _lib.check(lib.fr_plan_actions_object(ctypes.byref(plan["cfg"]), ptr[2], max_len, ptr[1], g.data_ptr(), poses.data_ptr(), G, agent_a, height,
+                                                  float(forward_step_size), float(turn_angle), float(self.cell_size), ptr[8], ptr[3], ptr[7],
+                                                  w2c.data_ptr(), ptr[0], ptr[4], ptr[5], ptr[6], self._stream()), "fr_plan_actions_object")
+            host = self._plan_read(out)
+            reads += 1
+            h = [host[int(o):int(o) + s] for o, s in zip(offs[:-1], sizes)]
+            lens = h[1].view(np.int32)
+            if (lens >= 0).all():
+                break
+            max_len = int(self.grid_dim[0]) * int(self.grid_dim[1]) + 1
+        pts = h[2].view(np.int32).reshape(G, max_len, 2)
+        paths = [pts[k, :lens[k]].astype(np.int64) if lens[k] > 0 else np.array([]) for k in range(G)]
+        pruned_len = h[6].view(np.int32)
+        pr = h[5].view(np.int32).reshape(G, max_len + 1, 2)
+        pruned = [pr[k, :pruned_len[k]].copy() if pruned_len[k] > 0 else np.zeros((0, 2), np.int32) for k in range(G)]
+        return ObjectActionPlan(goal_np, paths, pruned, h[3].view(np.int32).copy(), h[7].copy(), h[8].reshape(G, Q).copy(),
+                                h[4].view(np.int32).reshape(G, Q, 2).copy(), h[0].view(np.float64).reshape(G, Q, 2).copy(), w2c, finishes, reads=reads)
+
     def plan_field(self):
         """(cost float32 [H, W], -1 where the start does not reach; parent int32 [H, W, 2] = (row, col), -1 there)"""
         words = self._plan_read(self._plan["field"]).view(np.uint64)
@@ -557,7 +634,7 @@ class PathPlanOps:
     @classmethod
     def install(cls, planner_cls):
         """Graft the planning stage onto the reference's AstarPlanner class (after OccupancyOps.install, whose internals it uses)."""
-        for name in ("setup_start", "planning", "plan_paths", "plan_actions", "plan_field", "_plan_cell", "_plan_to_map", "_map_center_host", "_plan_read", "_localization_error",
+        for name in ("setup_start", "planning", "plan_paths", "plan_actions", "plan_actions_object", "_action_inputs", "plan_field", "_plan_cell", "_plan_to_map", "_map_center_host", "_plan_read", "_localization_error",
                      "occ_map_np", "free_space_np", "PLAN_MAX_LEN"):
             setattr(planner_cls, name, cls.__dict__[name])
         for name in ("convert_to_map", "convert_to_world"):                     # the reference class has its own
@@ -567,11 +644,215 @@ class PathPlanOps:
         return planner_cls
 
 
+class GoalSelectOps:
+    """Mixin with goal selection: `global_planning` (astar.py:843-1000) and the object round's `build_object_frontiers` (686-734),
+    `generate_candidate_adv_object` (1471-1588) and `global_object_planning` (1151-1346), built from the library's stages.  Needs
+    OccupancyOps' methods and, beyond its attributes, K_object, radius_object, min_range_object, centering, add_random_gaussians.
+
+    What differs from the reference: `visualize` is accepted and writes NOTHING -- no PNG; cv2 and
+    matplotlib are not imported.  The "vlm" frontier method raises, as build_frontiers does.  The candidates' draws come from the
+    counter-based generator (`candidate_seed` / torch.manual_seed), not from torch.rand / torch.randint.  The widening loop
+    `while len(candidate_pose) == 0` ends with an error after MAX_WIDENINGS rounds instead of spinning for ever."""
+
+    TOPK = 20                      # astar.py:992, 1338
+    MAX_WIDENINGS = 64             # the radius has grown by 1.5 ** 64 by then
+    GAUSSIAN_PER_GRID = 200        # astar.py:1353
+
+    # -- astar.py:686-734 ----------------------------------------------------------------------------------------------
+    def build_object_frontiers(self, gaussian_points, use_convex_hull=True):
+        """The centres (world x-z, float64 [N, 2], np.where order) of the map cells that hold more than 3 of the object's Gaussians,
+        or None.  One launch chain (fr_occ_object_cells) in place of torch.unique over the cloud; the cells and their count also stay
+        on the device (`_object_cells_dev`) for generate_candidate_adv_object.  A Gaussian with a non-finite x or z is not counted.
+        use_convex_hull is accepted and unused, as in the reference."""
+        self._object_cells_dev = None
+        if gaussian_points is None or gaussian_points.numel() == 0:
+            return None
+        lib = _lib.load()
+        dev = self.occ_map.device
+        pts = gaussian_points.detach().to(dev).float().contiguous()
+        cfg = self._occ_cfg()
+        ws, need = self._occ_workspace(cfg)
+        gw, gh = int(self.grid_dim[0]), int(self.grid_dim[1])
+        max_cells = gw * gh
+        cells = torch.empty((max_cells, 2), dtype=torch.int32, device=dev)
+        counts = torch.empty((2,), dtype=torch.int32, device=dev)
+        _lib.check(lib.fr_occ_object_cells(ctypes.byref(cfg), pts.data_ptr(), int(pts.shape[0]), 3, cells.data_ptr(), max_cells, counts.data_ptr(),
+                                           ws.data_ptr(), need, self._stream()), "fr_occ_object_cells")
+        n = int(counts.cpu()[0])
+        if n == 0:
+            return None
+        self._object_cells_dev = (cells, counts, n)
+        map_center = self.map_center.cpu().numpy() if torch.is_tensor(self.map_center) else np.asarray(self.map_center)
+        select_pixels = cells[:n].cpu().numpy().astype(np.int64)                    # (col, row) in np.where order
+        return (select_pixels - np.array([[gw // 2, gh // 2]])) * float(self.cell_size) + map_center[None, :]
+
+    # -- astar.py:1471-1588 ----------------------------------------------------------------------------------------------
+    @staticmethod
+    def _n_theta(theta_step_deg):
+        """max(1, round(2 pi / deg2rad(step))) as the reference takes it: in binary32, round half to even"""
+        step_rad = np.deg2rad(np.float32(theta_step_deg))
+        if not (np.isfinite(step_rad) and step_rad > 0):
+            raise ValueError(f"theta_step_deg must be positive and finite, got {theta_step_deg}")
+        return max(1, int(np.round(np.float32(2 * math.pi) / step_rad)))
+
+    def _grid_candidates(self, center_point, expansion=1, theta_step_deg=15.0, radial_bins=6, radial_spacing="linear", eroded=None, min_free=40,
+                         seed=None, cells_dev=None):
+        """K_object poses on the ordered grid of rings and angles (fr_occ_grid_candidates): ([K, 4, 4] c2w, [K] bool keep).  The
+        centres are the (x, z) rows of center_point, or -- cells_dev = (cells, counts, n) of build_object_frontiers -- the object
+        cells on the device, with no host copy in between."""
+        lib = _lib.load()
+        dev = self.occ_map.device
+        K = int(self.K_object)
+        c2w = torch.empty((K, 4, 4), dtype=torch.float32, device=dev)
+        keep = torch.empty((K,), dtype=torch.uint8, device=dev)
+        cfg = self._occ_cfg()
+        seed = self._next_seed() if seed is None else int(seed) & 0xFFFFFFFF
+        self.last_candidate_seed = seed
+        if cells_dev is not None:
+            centers, n_centers, cells, n_dev = None, int(cells_dev[0].shape[0]), cells_dev[0].data_ptr(), cells_dev[1].data_ptr()
+        else:
+            held = center_point.detach().to(dev).float()[:, :2].contiguous()
+            centers, n_centers, cells, n_dev = held.data_ptr(), int(held.shape[0]), None, None
+        _lib.check(lib.fr_occ_grid_candidates(ctypes.byref(cfg), centers, n_centers, cells, n_dev, K, float(self.min_range_object),
+                                              float(self.radius_object * expansion), self._n_theta(theta_step_deg), max(1, int(radial_bins)),
+                                              1 if radial_spacing == "sqrt_area" else 0, float(self.cam_height), seed,
+                                              None if eroded is None else eroded.data_ptr(), int(min_free), c2w.data_ptr(), keep.data_ptr(),
+                                              self._stream()), "fr_occ_grid_candidates")
+        return c2w, keep.bool()
+
+    def generate_candidate_adv_object(self, center_point: torch.Tensor, expansion: float = 1, mode: str = "random", theta_step_deg: float = 15.0,
+                                      radial_bins: int = 6, radial_spacing: str = "linear", seed=None):
+        """ Sample camera poses around the (one or more) center points: (K_object, 4, 4).
+        mode="random": the random ring (fr_occ_ring_candidates); mode="sorted": the ordered grid (fr_occ_grid_candidates) """
+        if mode.lower() == "random":
+            return self._ring_candidates(center_point, self.K_object, self.min_range_object, self.radius_object * expansion, seed=seed)[0]
+        if mode.lower() == "sorted":
+            return self._grid_candidates(center_point, expansion, theta_step_deg, radial_bins, radial_spacing, seed=seed)[0]
+        raise ValueError("mode must be 'random' or 'sorted'")
+
+    # -- astar.py:839-841, 1348-1370 ---------------------------------------------------------------------------------------
+    def pose_eval(self, poses, *args):
+        return torch.ones((poses.shape[0],)), poses
+
+    def generate_random_gaussians(self, candidate_pos):
+        """ Generate Random Gaussians from candidate positions: the reference's distribution, drawn by torch on the device """
+        if candidate_pos is None:
+            return None
+        dev = self.occ_map.device
+        position = torch.as_tensor(np.asarray(candidate_pos)).float().to(dev)
+        n, per = position.shape[0], self.GAUSSIAN_PER_GRID
+        xz_offset = torch.rand((1, per, 2), device=dev) * self.cell_size
+        y_offset = (self.cam_height - 1.0) + torch.rand((n, per, 1), device=dev)
+        new_p3t = torch.cat([position[:, None, :] + xz_offset, y_offset], dim=-1).reshape(-1, 3)[:, [0, 2, 1]]          # x-y-z order
+        m = new_p3t.shape[0]
+        new_rotations = torch.zeros((m, 4), device=dev)
+        new_rotations[:, 0] = 1.
+        return dict(means3D=new_p3t, scales=torch.rand((m, 3), device=dev).clamp_(min=1e-3) * self.cell_size * 0.05, rotations=new_rotations,
+                    opacity=torch.rand((m, 1), device=dev).clamp_(min=1e-3), shs=torch.rand((m, 1, 3), device=dev))
+
+    # -- the shared second half of global_planning / global_object_planning ----------------------------------------------------
+    def _select_goals(self, candidate_pos, use_frontier, sample, agent_pose, free_space, expansion, evaluate):
+        """candidate centres -> poses in the eroded free space (widening by x 1.5 while none is left), the random poses when there is no
+        frontier, the evaluation, the top 20.  sample(centres, expansion, eroded) -> (c2w, keep): the filter rides in the launch."""
+        dev = self.occ_map.device
+        candidate_pose = []
+        if candidate_pos is not None:
+            if isinstance(candidate_pos, np.ndarray):
+                candidate_pos = torch.from_numpy(candidate_pos).to(dev)
+            if getattr(self, "centering", False):
+                candidate_pos = torch.mean(candidate_pos, dim=0, keepdim=True)
+            eroded = self._eroded_free(None, 10)                     # the free space build_frontiers just left on the device
+            widenings = 0
+            while len(candidate_pose) == 0:
+                if widenings == self.MAX_WIDENINGS:
+                    raise RuntimeError(f"no candidate pose in the free space after {widenings} widenings of the sampling radius")
+                c2w, keep = sample(candidate_pos, expansion, eroded)
+                candidate_pose = c2w[keep]
+                expansion *= 1.5
+                widenings += 1
+            self.last_widenings = widenings
+        if not use_frontier:
+            random_pose = self.sample_random_candidate(agent_pose, free_space, sample_range=2 * expansion, sample_size=int(400 * expansion))
+            candidate_pose = random_pose if len(candidate_pose) == 0 else torch.cat([candidate_pose, random_pose], dim=0)
+        scores, poses = evaluate(candidate_pose)
+        sort_index = torch.argsort(scores, descending=True)
+        poses = poses[sort_index[:self.TOPK].to(poses.device)]
+        scores = scores[sort_index[:self.TOPK]]
+        self.previous_candidates = poses
+        return poses, scores, candidate_pos
+
+    # -- astar.py:843-1000 -----------------------------------------------------------------------------------------------
+    def global_planning(self, pose_evaluation_fn=None, gaussian_points=None, goal_proposal_fn=None, expansion=1, visualize=True, agent_pose=None,
+                        last_goal=None, slam=None):
+        """ Global Planning for next target goal: (poses [<= 20, 4, 4], scores, random_gaussian_params), or (None, None, None) in frontier
+        mode without a frontier.  visualize writes nothing; last_goal and slam are accepted and unused (the VLM frontier raises). """
+        if self.frontier_select_method == "vlm":
+            raise ValueError("frontier_select_method 'vlm' is not rebuilt (the VLM selection stays reference Python)")
+        candidate_pos, free_space = self.build_frontiers(gaussian_points)
+        use_frontier = candidate_pos is not None
+        if pose_evaluation_fn is None and not use_frontier:
+            return None, None, None
+        random_gaussian_params = self.generate_random_gaussians(candidate_pos) if getattr(self, "add_random_gaussians", False) else None
+        if candidate_pos is None and goal_proposal_fn is not None:
+            candidate_pos = goal_proposal_fn(self.K, self.cam_height)
+
+        def sample(centres, expansion, eroded):
+            return self._ring_candidates(centres, self.K, self.min_range, self.radius * expansion, eroded, 40)
+
+        def evaluate(candidate_pose):
+            return self.pose_eval(candidate_pose) if pose_evaluation_fn is None else pose_evaluation_fn(candidate_pose, random_gaussian_params)
+
+        poses, scores, _ = self._select_goals(candidate_pos, use_frontier, sample, agent_pose, free_space, expansion, evaluate)
+        return poses, scores, random_gaussian_params
+
+    # -- astar.py:1151-1346 ----------------------------------------------------------------------------------------------
+    def global_object_planning(self, pose_evaluation_fn=None, gaussian_points=None, gaussian_points_scene=None, goal_proposal_fn=None, expansion=1,
+                               visualize=True, agent_pose=None, criterion=None):
+        """ Global Planning for next target goal around the object: (poses [<= 20, 4, 4], scores, None, the candidate centres), or
+        (None, None, None) in frontier mode without object cells.  The third value is None whatever add_random_gaussians says: the
+        reference makes the random Gaussians and discards them (astar.py:1182), and so does this.  Without centering the object cells
+        go from fr_occ_object_cells to fr_occ_grid_candidates on the device. """
+        if self.frontier_select_method == "vlm":
+            raise ValueError("frontier_select_method 'vlm' is not rebuilt (the VLM selection stays reference Python)")
+        _, free_space = self.build_frontiers(gaussian_points_scene)
+        candidate_obj_pos = self.build_object_frontiers(gaussian_points)
+        use_frontier = candidate_obj_pos is not None
+        if pose_evaluation_fn is None and not use_frontier:
+            return None, None, None
+        if getattr(self, "add_random_gaussians", False):
+            self.generate_random_gaussians(candidate_obj_pos)
+        random_gaussian_params = None
+        cells_dev = self._object_cells_dev if use_frontier and not getattr(self, "centering", False) else None
+        if candidate_obj_pos is None and goal_proposal_fn is not None:
+            candidate_obj_pos = goal_proposal_fn(self.K_object, self.cam_height)
+
+        def sample(centres, expansion, eroded):
+            return self._grid_candidates(centres, expansion, eroded=eroded, min_free=40, cells_dev=cells_dev)
+
+        def evaluate(candidate_pose):
+            if pose_evaluation_fn is None:
+                return self.pose_eval(candidate_pose)
+            return pose_evaluation_fn(candidate_pose, random_gaussian_params, criterion=criterion)
+
+        poses, scores, candidate_obj_pos = self._select_goals(candidate_obj_pos, use_frontier, sample, agent_pose, free_space, expansion, evaluate)
+        return poses, scores, random_gaussian_params, candidate_obj_pos
+
+    @classmethod
+    def install(cls, planner_cls):
+        """Graft goal selection onto the reference's AstarPlanner class (after OccupancyOps.install, whose methods it uses)."""
+        for name in ("build_object_frontiers", "generate_candidate_adv_object", "global_planning", "global_object_planning", "generate_random_gaussians",
+                     "_grid_candidates", "_n_theta", "_select_goals", "TOPK", "MAX_WIDENINGS", "GAUSSIAN_PER_GRID"):
+            setattr(planner_cls, name, cls.__dict__[name])
+        if not hasattr(planner_cls, "pose_eval"):
+            planner_cls.pose_eval = cls.__dict__["pose_eval"]
+        return planner_cls
+
+
 class LocalizationError(Exception):
     """raised by setup_start when all 8 neighbours of the start are occupied in the dilated map (astar.py:481-482)"""
 
 
-class AstarPlanner(OccupancyOps, PathPlanOps):
+class AstarPlanner(OccupancyOps, PathPlanOps, GoalSelectOps):
     """Standalone object with the reference constructor's configuration keys (astar.py:23-60)."""
 
     def __init__(self, slam_config=None, eval_dir=None, device=torch.device("cuda:0"), **kw):
@@ -593,3 +874,6 @@ class AstarPlanner(OccupancyOps, PathPlanOps):
         self.cam_pos = None
         self.frame_idx = 0
         self.shortcut_path = kw.get("shortcut_path", ex.get("shortcut_path", True))
+        self.centering = kw.get("centering", ex.get("centering", False))
+        self.add_random_gaussians = kw.get("add_random_gaussians", ex.get("add_random_gaussians", False))
+        self.previous_candidates = None

@@ -15,6 +15,13 @@
  *   fr_occ_ring_candidates <- AstarPlanner.generate_candidate / generate_candidate_object planning/astar.py:1383-1430, 1432-1469
  *                           fused with the free-space filter of the candidate loop planning/astar.py:1387-1401
  *   fr_occ_free_candidates <- AstarPlanner.sample_random_candidate   planning/astar.py:782-837
+ *   fr_occ_object_cells  <- AstarPlanner.build_object_frontiers    planning/astar.py:686-734
+ *                           (torch.unique(dim=0, return_counts=True) over every object Gaussian's cell, count > 3, a host mask
+ *                            painted and read back with np.where)
+ *   fr_occ_grid_candidates <- AstarPlanner.generate_candidate_adv_object(mode="sorted") planning/astar.py:1471-1588
+ *                           (the ordered grid of rings and angles), fused with the free-space filter planning/astar.py:1387-1401
+ *   fr_plan_actions_object <- NavTester.action_planning_object_adv   tester_gaussians_navigation.py:2403-2496
+ *                           (waypoint pruning near the goal, orientation-only mode, waypoint skipping, up to 200 actions)
  *
  * Conventions are fisher_rast.h's: device pointers unless noted, explicit stream, no allocation, no device
  * synchronisation, 0 or an FR_E* code, message through fr_last_error().
@@ -93,6 +100,38 @@ int fr_occ_free_candidates(const fr_occ_cfg* cfg, const uint8_t* eroded_free, fl
                            float* c2w, int32_t max_out, int32_t* counts, void* workspace, size_t workspace_bytes,
                            fr_stream_t stream);
 
+/* build_object_frontiers (astar.py:686-734): the map cells that hold more than min_count (the reference: 3) of the Gaussians
+ * points [n_points][3], as (col, row) in raster order -- np.where order.  A point's cell is fr_occ_cells_of's: discretize_coords,
+ * clamped to the grid, so a Gaussian outside the map counts in the border cell, as in the reference.  A point whose x or z is not
+ * finite is NOT binned (the reference's cast is undefined there).  Integer atomics: the answer does not depend on the order.
+ *   cells   int32 [max_cells][2] out; with more cells than max_cells nothing is written past it
+ *   counts  int32 [2] (device) = {cells with count > min_count -- the true number, also beyond max_cells --, points binned}
+ * n_points = 0 is legal (points may be null) and gives {0, 0}.  Workspace: fr_occ_workspace_bytes(), 16-byte aligned. */
+int fr_occ_object_cells(const fr_occ_cfg* cfg, const float* points, int32_t n_points, int32_t min_count, int32_t* cells,
+                        int32_t max_cells, int32_t* counts, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+
+/* generate_candidate_adv_object(mode="sorted") (astar.py:1514-1588): K poses on an ordered grid of rings and angles.
+ *   n_theta      max(1, round(2 pi / deg2rad(theta_step_deg))), taken by the caller on the host as the reference does.  The angles
+ *                are the first max(1, n_theta - 1) points of linspace(0, 2 pi, n_theta): the reference drops the closing angle, so
+ *                a step of 15 degrees gives 23 angles, not 24.
+ *   radial_bins  the radii are linspace(min_range, radius, radial_bins), or sqrt(linspace(min_range^2, radius^2)) with sqrt_area
+ *                != 0 and more than one bin.  Both tables are taken in binary64 and rounded once to binary32.
+ * Pose k takes grid entry k mod (radial_bins * angles), the ring index the slow one (meshgrid(indexing='ij'), then slice or
+ * repeat); its centre is drawn with replacement by fr_occ_ring_candidates' generator (index = floor(u2 n), keyed by (seed, k));
+ * position = centre + r (sin t, 0, cos t) at height cam_height, orientation = yaw (t + pi) with columns 0 and 1 negated; keep is
+ * fr_occ_ring_candidates' eroded-free-space rule (keep may be null).  The centres come from ONE of
+ *   centers      float32 [n_centers][2] = (x, z), n_centers > 0, or
+ *   cells        int32 [n_centers][2] = (col, row) as fr_occ_object_cells leaves them, of which min(*n_cells_dev, n_centers) are
+ *                there (n_cells_dev: device int32, e.g. fr_occ_object_cells' counts; n_centers: the rows `cells` has room for):
+ *                object cells -> candidates -> filter run back to back without a host read.  A cell's world position is
+ *                (cell - grid_dim // 2) * cell_size + map_center, as build_frontiers gives it.  With no cell on the device every
+ *                pose is a zero matrix with keep 0.
+ * c2w: float32 [K][16] row-major, out.  K = 0 returns FR_OK without a launch. */
+int fr_occ_grid_candidates(const fr_occ_cfg* cfg, const float* centers, int32_t n_centers, const int32_t* cells, const int32_t* n_cells_dev,
+                           int32_t K, float min_range, float radius, int32_t n_theta, int32_t radial_bins, int32_t sqrt_area,
+                           float cam_height, uint32_t seed, const uint8_t* eroded_free, int32_t min_free, float* c2w, uint8_t* keep,
+                           fr_stream_t stream);
+
 /* ---- path planning: one cost field from the start, paths to all goals ------------------------------------------------------
  * Replaces AstarPlanner.setup_start + planning (planning/astar.py:449-538, 1591-1777): the reference runs a best-first search
  * per goal on the host; these calls build the single-source shortest-path field of the same cost model (csrc/fr_plan_math.h)
@@ -169,6 +208,26 @@ int fr_plan_actions(const fr_occ_cfg* cfg, const int32_t* paths, int32_t max_len
 
 int fr_rollout_actions(const double* start_c2w, const uint8_t* actions, const int32_t* n_actions, int32_t n_lists, int32_t queue_size,
                        double forward_step_size, double turn_angle, float* w2c, double* c2w, fr_stream_t stream);
+
+/* ---- the object round's follower ---------------------------------------------------------------------------------------------
+ * Replaces the loop of NavTester.action_planning_object_adv (tester_gaussians_navigation.py:2403-2496): per goal the path is padded
+ * (a path of one point), pruned near the goal, and walked with early stop, orientation-only mode near the goal and waypoint
+ * skipping, for up to FR_ACTION_OBJECT_MAX actions (the reference's SAFETY_CAP; the planning queue does not cut these lists).
+ * Binary64 arithmetic (csrc/fr_action_object_math.h, which states every rule), quirks kept.  Inputs as fr_plan_actions'; the
+ * pruning measures against the agent's own height agent_c2w[1][3], the walk starts at cam_height.  Outputs (device):
+ *   actions    uint8 [n_goals][200]           n_actions  int32 [n_goals], -1 where lengths[g] <= 0: the goal has no path
+ *   keep       uint8 [n_goals]                1 where the list is not empty and no earlier goal made the same list (an empty list
+ *                                             is dropped, unlike fr_plan_actions')
+ *   w2c        float32 [n_goals][200][16]     c2w_xz  float64 [n_goals][200][2]     map_xz  int32 [n_goals][200][2]
+ *   pruned     int32 [n_goals][max_len + 1][2] the pruned path (x, z), what the reference returns as paths_arr
+ *   pruned_len int32 [n_goals]                its points: at least 2 with a path, 0 without
+ * Zeros past every list and every pruned path.  Two launches; n_goals = 0 returns FR_OK without one. */
+#define FR_ACTION_OBJECT_MAX 200
+
+int fr_plan_actions_object(const fr_occ_cfg* cfg, const int32_t* paths, int32_t max_len, const int32_t* lengths, const int32_t* goals,
+                           const float* goals_c2w, int32_t n_goals, const double* agent_c2w, double cam_height, double forward_step_size,
+                           double turn_angle, double cell_size, uint8_t* actions, int32_t* n_actions, uint8_t* keep, float* w2c,
+                           double* c2w_xz, int32_t* map_xz, int32_t* pruned, int32_t* pruned_len, fr_stream_t stream);
 
 #ifdef __cplusplus
 }
