@@ -18,6 +18,23 @@ index in range), and a `call(ctx, buffers) -> {name: tensor}`.  `run_case`:
 A launch, memset or copy on another stream than the caller's reads `decoy` (or writes an output before the caller's stream fills
 it); a side-stream launch in front of its wait does the same; a join that is missing lets the clones run ahead of the side stream.
 
+Coverage.  Every case lists in `covers` the C entry points its call drives.  tests/test_stream_cases_cpu.py holds the union of the
+lists against the exports that take a stream (every export of fisher_rast._lib.EXPORTS whose declaration has an fr_stream_t), so an
+entry point added without a case fails there; test_stream_order wraps those exports of the loaded library in a recorder for the
+stream-ordered run and holds each list against what was called, so a list cannot claim more, or less, than the call does.
+
+Memsets.  A hipMemsetAsync that clears an accumulator, a histogram or a status word on another stream than the caller's runs EARLY,
+while the blocker holds the kernels back: on a workspace that nothing has touched since the reference runs it clears what it should,
+only too soon, and the result is right.  A case with `repeat` therefore makes the call twice behind the blocker and compares the
+second: the second call's early memset then runs before the first call's kernels have dirtied the workspace (the one kept per index
+or per stream, or the block that the caching allocator hands out again), and the second call's kernels find it dirty.
+What is shown and what is not: tests/test_gpu_streams.py holds the mechanism against a torch stand-in with a workspace of its own whose
+clear goes to the null stream -- nothing patches a real unit's memset, so no test proves that a unit's second call meets a dirty
+workspace.  For DBSCAN, the loss mask and the cloud search (fresh torch.empty blocks per call, a fresh index per call) that rests on
+the caching allocator handing the freed block of the first call to the second, which is its usual behaviour and a supposition
+here; the view metrics, the background penalty, the roll-out and the grid candidates issue no memset at all, `repeat` there only
+makes a second call re-use what the first left.  `repeat` narrows the gap for the units that clear with memsets; it does not close it.
+
 `run_case(..., null_stream=patch)` is the committed mutation check: `patch` makes the layer's stream helper return the null stream,
 the default stream is synchronised before the clones are enqueued, and the clones must then equal `want_decoy` exactly.
 
@@ -29,10 +46,17 @@ runs, milliseconds:
     single-view front end 0.15, knn 0.10, spatial order 0.10, image loss forward + backward 0.10, fused adam 0.08,
     rendervar forward + backward 0.14, keyframe pixels + overlap 0.19, frame ingest select + emit 0.31, map edit apply + split 0.13,
     densify statistics + masks + prune 0.11, POp-GS criterion 0.09, occupancy update + free space + candidates 0.26
-The slowest is 0.31 ms, ten times that 3.1 ms: the floor applies, BLOCKER_MS = 20 (the cap would be 250).  rasterize_forward, the
+and of the cases added with the `covers` column (a `repeat` case: both calls):
+    forward_features 0.30, fr_backward through the C ABI 0.20, fr_backward_pair 0.24,
+    cloud build + search 0.17 (twice), cloud build + query_depth 0.21 (twice), dbscan_raw 0.13 (twice),
+    view metrics + summary float 0.13 (twice), uint8 0.10 (twice), loss mask one launch 0.09 (twice), five launches 0.11 (twice),
+    background penalty forward + backward through autograd 0.52 (twice), roll-out 0.07 (twice), grid candidates from device centres 0.09 (twice)
+The slowest is 0.52 ms, ten times that 5.2 ms: the floor applies, BLOCKER_MS = 20 (the cap would be 250).  rasterize_forward, the
 map edit's plan and setup_start / plan_paths read a status word or a result (the reference's own host synchronisations), so those
 cases wait for the blocker inside the call (20.2 to 20.6 ms): their figure is the blocker's, not the host's, and is left out of
-the maximum.  One torch.cuda._sleep cycle was 0.417 ns there (2.40e6 cycles per ms).
+the maximum.  The same holds for build_frontiers + sample_random_candidate (20.5), select_target (20.4), get_gaussians_outside_mask
+(20.3), setup_start + plan_actions (21.3), + plan_actions_object (21.4) and build_object_frontiers + grid candidates (20.5).
+One torch.cuda._sleep cycle was 0.417 ns there (2.40e6 cycles per ms).
 """
 import ctypes
 import time
@@ -58,7 +82,12 @@ class Case(NamedTuple):
     same: tuple = ()                # inputs kept equal between real and decoy (small host-like values, fixed parameters)
     setup: Optional[Callable] = None      # setup(buffers, dev) -> ctx, once per buffer set (a scorer over the buffers, ...)
     prepare: Optional[Callable] = None    # prepare(buffers, dev) -> {name: tensor or host value}: inputs the device derives (a forward's buffers)
-    sync_free: bool = False         # the suite runs this entry point under set_sync_debug_mode("error")
+    sync_free: bool = False         # nothing is read back inside the call (the suite runs the entry point under set_sync_debug_mode("error"), or
+                                    # its layer documents no host read): the call must return while the blocker is still running
+    covers: tuple = ()              # the C entry points (names of fisher_rast._lib.EXPORTS) that `call` drives: all of them, and no other
+    images: tuple = ()              # uint8 inputs that hold image bytes (0 .. 255), not a mask or a flag
+    repeat: bool = False            # the stream-ordered run makes the call twice back to back and compares the second (a call that reads nothing
+                                    # back and writes none of its inputs): see "Memsets" in the module's docstring
 
 
 # ---- the harness ----------------------------------------------------------------------------------------------------------------------
@@ -235,6 +264,8 @@ def enqueue(case, ref, dev, stream=None, blocker_ms=BLOCKER_MS, null_stream=Fals
         t0 = time.perf_counter()
         _fill(work, ref.real)
         before = gate.query()
+        if case.repeat:
+            case.call(ref.ctx, work)                                     # dropped: its workspaces and outputs go back to the allocator, dirty
         out = case.call(ref.ctx, work)
         t1 = time.perf_counter()
         after = gate.query()
@@ -264,12 +295,63 @@ def stream_run(case, ref, dev, stream=None, blocker_ms=BLOCKER_MS, null_stream=F
     return finish(enqueue(case, ref, dev, stream, blocker_ms, null_stream))
 
 
-def run_case(case, dev, blocker_ms=BLOCKER_MS):
-    """the whole procedure for one case; raises AssertionError with the outputs that missed"""
+def declared_exports():
+    """{name: parameter list} of every function that include/fisher_rast.h and include/fisher_occ.h declare, comments taken out"""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    found = {}
+    for header in ("fisher_rast.h", "fisher_occ.h"):
+        with open(os.path.join(root, "include", header)) as f:
+            text = f.read()
+        text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+        text = re.sub(r"//[^\n]*", " ", text)
+        for m in re.finditer(r"\b(fr_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", text):
+            found[m.group(1)] = m.group(2)
+    return found
+
+
+def stream_exports():
+    """the exports that take a stream: those whose declaration has an fr_stream_t parameter (tests/test_stream_cases_cpu.py holds the
+    declarations against fisher_rast._lib.EXPORTS and the others against a list written out by name)"""
+    return tuple(n for n, params in declared_exports().items() if "fr_stream_t" in params)
+
+
+class recorded_calls:
+    """`with recorded_calls() as called:` -- every stream-taking export of the loaded library is wrapped for the length of the block
+    (an attribute set on the CDLL object shadows the function the Python layers look up at every call); `called` is the set of the
+    names that were called.  The wrappers come off on exit."""
+
+    def __enter__(self):
+        from fisher_rast import _lib
+        self.lib, self.called, self.saved = _lib.load(), set(), {}
+        for name in stream_exports():
+            fn = getattr(self.lib, name)
+            self.saved[name] = fn
+
+            def wrapper(*args, _fn=fn, _name=name):
+                self.called.add(_name)
+                return _fn(*args)
+            setattr(self.lib, name, wrapper)
+        return self.called
+
+    def __exit__(self, *exc):
+        for name, fn in self.saved.items():
+            setattr(self.lib, name, fn)
+        return False
+
+
+def run_case(case, dev, blocker_ms=BLOCKER_MS, check_covers=False):
+    """the whole procedure for one case; raises AssertionError with the outputs that missed.  check_covers: the stream-ordered run
+    called every entry point of `case.covers` and no other stream-taking export."""
     ref = reference(case, dev)
-    got = stream_run(case, ref, dev, blocker_ms=blocker_ms)
+    with recorded_calls() as called:
+        got = stream_run(case, ref, dev, blocker_ms=blocker_ms)
     bad = mismatches(case, got, ref.want)
     assert not bad, f"{case.name}: the stream-ordered run does not give the default-stream result: {bad}"
+    if check_covers:
+        assert called == set(case.covers), (f"{case.name}: covers lists {sorted(set(case.covers) - called)} that the call did not drive, "
+                                            f"and leaves out {sorted(called - set(case.covers))} that it did")
     return ref, got
 
 
@@ -337,7 +419,7 @@ def _forward_case(n, features=False):
     # (n = 1500 faint Gaussians do not bring any pixel to the median's half transmittance: the depth image is the same for both sets)
     return Case(name=f"forward{'_pair' if features else ''}_n{n}", make=lambda which: _sort_scene(n, which, features), call=call,
                 exact=("color", "keys") + (("depth",) if n >= 5000 else ()) + (("feature_image",) if features else ()),
-                same=CAMERA_NAMES + ("opacity", "scales", "rotations"))
+                same=CAMERA_NAMES + ("opacity", "scales", "rotations"), covers=("fr_forward_pair" if features else "fr_forward",))
 
 
 def _prepare_forward(features):
@@ -365,7 +447,7 @@ def _backward_case(n, power, segmented):
                 call=call, prepare=_prepare_forward(False),
                 close={k: rule for k in ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D")},
                 close_from="test_gpu_rasterizer_parity.py::test_backward_parity (1e-4, atol_frac 2e-5)",
-                same=CAMERA_NAMES + ("opacity", "scales", "rotations"))
+                same=CAMERA_NAMES + ("opacity", "scales", "rotations"), covers=("fr_backward_ws",))
 
 
 PAIR_GRADS = ("dL_dmeans2D", "dL_dmeans2D_features", "dL_dcolors", "dL_dfeatures", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D",
@@ -387,7 +469,7 @@ def _backward_pair_case(n):
                 prepare=_prepare_forward(True),
                 close={k: rule for k in ("dL_dmeans2D", "dL_dmeans2D_features", "dL_dcolors", "dL_dfeatures", "dL_dopacity", "dL_dmeans3D")},
                 close_from="test_gpu_rasterizer_parity.py::test_fused_rgb_depth_silhouette_pair (1e-4, atol_frac 1e-6)",
-                same=CAMERA_NAMES + ("opacity", "scales", "rotations"))
+                same=CAMERA_NAMES + ("opacity", "scales", "rotations"), covers=("fr_backward_pair_ws",))
 
 
 def _mark_visible_case():
@@ -401,7 +483,7 @@ def _mark_visible_case():
         from fisher_rast import ops
         import torch
         return dict(present=ops.mark_visible(b["means3D"], b["view"], b["proj"]).view(torch.uint8))
-    return Case(name="mark_visible", make=make, call=call, exact=("present",), same=("view", "proj"))
+    return Case(name="mark_visible", make=make, call=call, exact=("present",), same=("view", "proj"), covers=("fr_mark_visible",))
 
 
 # -- the scorer: the sort-sizes scene under 8 poses near the identity ----------------------------------------------------------------------
@@ -463,16 +545,18 @@ def _scorer_cases():
     return [
         # packed lists with V >= 8: the multi-view configuration that forks the 1024-thread sort tier onto side stream [0] (want_fork)
         Case(name="scorer_launch_hinv_packed", make=mk(4), call=launch_hinv, setup=_scorer_setup(4, tile_capacity=0), exact=("scores",),
-             same=SCORER_SAME, sync_free=True),
+             same=SCORER_SAME, sync_free=True, covers=("fr_fisher_views",)),
         Case(name="scorer_launch_outH_11", make=mk(11), call=launch_outh, setup=_scorer_setup(11), close={"out_H": (1e-4, 1e-7)},
-             close_from="test_gpu_fisher_parity.py::test_per_view_hessian_and_scores (1e-4, atol_frac 1e-7)", same=SCORER_SAME, sync_free=True),
-        Case(name="scorer_pose_launch", make=mk(4), call=pose, setup=_scorer_setup(4), exact=("pose_H",), same=SCORER_SAME, sync_free=True),
+             close_from="test_gpu_fisher_parity.py::test_per_view_hessian_and_scores (1e-4, atol_frac 1e-7)", same=SCORER_SAME, sync_free=True,
+             covers=("fr_fisher_views",)),
+        Case(name="scorer_pose_launch", make=mk(4), call=pose, setup=_scorer_setup(4), exact=("pose_H",), same=SCORER_SAME, sync_free=True,
+             covers=("fr_fisher_pose_views",)),
         Case(name="scorer_render_launch", make=mk(4), call=render, setup=_scorer_setup(4),
-             exact=("render", "depth_sil", "median_depth", "final_T"), same=SCORER_SAME, sync_free=True),
+             exact=("render", "depth_sil", "median_depth", "final_T"), same=SCORER_SAME, sync_free=True, covers=("fr_render_views",)),
         Case(name="scorer_point_launch", make=mk(4), call=point, setup=_scorer_setup(4), exact=("scores",),
              close={"point_scores": (1e-4, 1e-7)},
              close_from="test_gpu_point_scores.py::test_point_scores_against_the_oracle (the flat part of its rule: 1e-4 |want| + 1e-7 max|want|)",
-             same=SCORER_SAME, sync_free=True),
+             same=SCORER_SAME, sync_free=True, covers=("fr_fisher_point_views",)),
     ]
 
 
@@ -496,7 +580,7 @@ def _single_view_front_end_case():
         r = sc.launch(b["w2c"], H_inv=b["H_inv"])
         return dict(scores=r["scores"], _status=r["status"])
     return Case(name="scorer_single_view_front_end", make=make, call=call, setup=_scorer_setup(4, SV_W, SV_H), exact=("scores",),
-                sync_free=True)
+                sync_free=True, covers=("fr_fisher_views",))
 
 
 # -- knn and the spatial order: one key past an LDS chunk of the bitonic network -----------------------------------------------------------
@@ -513,14 +597,14 @@ def _knn_case():
     def call(ctx, b):
         from simple_knn._C import distCUDA2
         return dict(dist2=distCUDA2(b["points"]))
-    return Case(name="knn_dist2", make=_points, call=call, exact=("dist2",))
+    return Case(name="knn_dist2", make=_points, call=call, exact=("dist2",), covers=("fr_knn_dist2",))
 
 
 def _spatial_order_case():
     def call(ctx, b):
         from fisher_rast import ops
         return dict(order=ops.spatial_order_of(b["points"]))
-    return Case(name="spatial_order", make=_points, call=call, exact=("order",))
+    return Case(name="spatial_order", make=_points, call=call, exact=("order",), covers=("fr_spatial_order",))
 
 
 # -- one case each from the tables of the other families -------------------------------------------------------------------------------------
@@ -541,7 +625,8 @@ def _image_loss_case():
                                                          want_channels=True)
         grad = il.backward_raw(b["img"], b["gt"], m, saved, cfg, b["upstream"])
         return dict(out4=out4, channel_ssim=chan, ssim_map=smap, grad=grad)
-    return Case(name="image_loss", make=make, call=call, exact=("out4", "channel_ssim", "ssim_map", "grad"), sync_free=True)
+    return Case(name="image_loss", make=make, call=call, exact=("out4", "channel_ssim", "ssim_map", "grad"), sync_free=True,
+                covers=("fr_image_loss_forward", "fr_image_loss_backward"))
 
 
 ADAM_SIZES = (4099, 3, 1024)
@@ -564,7 +649,7 @@ def _adam_case():
         HipAdamBackend.step(entries)
         return {k: b[k] for k in b if k[0] in "pmv"}
     names = tuple(f"{c}{i}" for i in range(len(ADAM_SIZES)) for c in "pmv")
-    return Case(name="fused_adam", make=make, call=call, exact=names, sync_free=True)
+    return Case(name="fused_adam", make=make, call=call, exact=names, sync_free=True, covers=("fr_adam_step",))
 
 
 RV_P = 257
@@ -588,7 +673,8 @@ def _rendervar_case():
                      g_cam_unnorm_rots=new(1, 4, rc.T_FRAMES), g_cam_trans=new(1, 3, rc.T_FRAMES))
         ops.rendervar_backward(RV_P, 3, 2, rc.T_FRAMES, {**inputs, **{k: b[k] for k in rc.UPSTREAM}, **grads})
         return {**out, **grads}
-    return Case(name="rendervar", make=make, call=call, exact=rc.OUTPUTS + rc.GRADS, sync_free=True)
+    return Case(name="rendervar", make=make, call=call, exact=rc.OUTPUTS + rc.GRADS, sync_free=True,
+                covers=("fr_rendervar_forward", "fr_rendervar_backward"))
 
 
 KF_N_VALID = 2048                    # the prefix of the valid-pixel list the draws index: below both cases' counts
@@ -615,7 +701,7 @@ def _keyframe_case():
                                  kf_masks=masks, edge=4, want_pts=True)
         return dict(idx_head=idx[:KF_N_VALID], n_valid=status[:1], counts=r["counts"], valid=r["valid"], pts=r["pts"])
     return Case(name="keyframe", make=make, call=call, exact=("idx_head", "n_valid", "counts", "pts"), bounds={"draws": (0, KF_N_VALID)},
-                same=("K", "w2c"), sync_free=True)
+                same=("K", "w2c"), sync_free=True, covers=("fr_keyframe_valid_pixels", "fr_keyframe_overlap"))
 
 
 INGEST_SHAPE = (48, 64, 4)           # H, W, downsample
@@ -654,7 +740,7 @@ def _ingest_case():
         return dict(status=status, means3D=out["means3D"], rgb_colors=out["rgb_colors"], log_scales=out["log_scales"],
                     mean3_sq_dist=out["mean3_sq_dist"])
     return Case(name="frame_ingest", make=make, call=call, exact=("status", "means3D", "rgb_colors", "log_scales", "mean3_sq_dist"),
-                same=("K",), sync_free=True)
+                same=("K",), sync_free=True, covers=("fr_frame_ingest_select", "fr_frame_ingest_emit"))
 
 
 # -- map edit: plan (one host read inside), apply and split children -----------------------------------------------------------------------
@@ -702,9 +788,11 @@ def _map_edit_cases():
     def apply_only(ctx, b):
         from models.SLAM.utils.slam_external import MapEditPlan
         return _edit_apply(MapEditPlan(EDIT_P, EDIT_P - EDIT_SPLIT, EDIT_CLONE, EDIT_SPLIT, EDIT_INTO, b["handle"]), b)
-    return [Case(name="map_edit_plan_apply_split", make=_edit_inputs, call=whole, exact=EDIT_OUT),
+    return [Case(name="map_edit_plan_apply_split", make=_edit_inputs, call=whole, exact=EDIT_OUT,
+                 covers=("fr_map_edit_plan", "fr_map_edit_apply", "fr_map_edit_split_children")),
             # the plan made beforehand, its index lists an input like any other: apply and split children behind the blocker
-            Case(name="map_edit_apply_split", make=_edit_inputs, call=apply_only, prepare=prepare, exact=EDIT_OUT)]
+            Case(name="map_edit_apply_split", make=_edit_inputs, call=apply_only, prepare=prepare, exact=EDIT_OUT,
+                 covers=("fr_map_edit_apply", "fr_map_edit_split_children"))]
 
 
 # -- densify statistics, densify masks, prune mask -------------------------------------------------------------------------------------------
@@ -734,7 +822,8 @@ def _densify_case():
         return dict(means2D_gradient_accum=b["means2D_gradient_accum"], denom=b["denom"], max_2D_radius=b["max_2D_radius"],
                     seen=u8(variables["seen"]), to_clone=u8(to_clone), to_split=u8(to_split), to_remove=u8(to_remove))
     return Case(name="densify_stats_masks_prune", make=make, call=call, bounds={"radii": (0, 40)},
-                exact=("means2D_gradient_accum", "denom", "max_2D_radius", "seen", "to_clone", "to_split", "to_remove"))
+                exact=("means2D_gradient_accum", "denom", "max_2D_radius", "seen", "to_clone", "to_split", "to_remove"),
+                covers=("fr_densify_stats", "fr_densify_masks", "fr_prune_mask"))
 
 
 # -- occupancy and planning through planning/astar.py ---------------------------------------------------------------------------------------
@@ -779,7 +868,11 @@ def _occupancy_case():
         eroded = p._eroded_free(None, 3)
         c2w, keep = p._ring_candidates(b["centre"], 16, p.min_range, p.radius, eroded, 40, seed=5)
         return dict(occ_map=b["occ_map"], free=free, eroded=eroded, c2w=c2w, keep=keep.view(torch.uint8))
-    return Case(name="occupancy_update_freespace_candidates", make=make, call=call, setup=setup, exact=("occ_map", "free", "eroded", "c2w"))
+    return Case(name="occupancy_update_freespace_candidates", make=make, call=call, setup=setup, exact=("occ_map", "free", "eroded", "c2w"),
+                covers=("fr_occ_update", "fr_occ_freespace", "fr_occ_erode", "fr_occ_ring_candidates"))
+
+
+PLAN_COVERS = ("fr_plan_grid", "fr_occ_freespace", "fr_plan_tiers", "fr_plan_field", "fr_plan_paths")      # setup_start + plan_paths
 
 
 def _path_plan_case():
@@ -799,7 +892,8 @@ def _path_plan_case():
         flat = np.concatenate([np.asarray(q, np.int64).reshape(-1) for q in paths] + [np.array([len(q) for q in paths], np.int64)])
         plan = p._plan
         return dict(occ_plan=plan["occ_plan"], free=plan["free"], tiers=plan["tiers"], field=plan["field"], paths=torch.from_numpy(flat))
-    return Case(name="path_plan_grid_field_paths", make=make, call=call, setup=setup, exact=("occ_plan", "free", "field", "paths"))
+    return Case(name="path_plan_grid_field_paths", make=make, call=call, setup=setup, exact=("occ_plan", "free", "field", "paths"),
+                covers=PLAN_COVERS)
 
 
 POPGS_V, POPGS_K, POPGS_E = 5, 3, 1027
@@ -817,7 +911,445 @@ def _popgs_case():
         out = torch.zeros((POPGS_V, POPGS_E), dtype=torch.float32, device=b["rows"].device)
         s = ops.popgs_diag_criterion(b["rows"], b["prior"], 1e-6, "dopt", prior_out=out, accumulate=b["accumulate"], vis_count=b["vis"])
         return dict(scores=s, prior_out=out)
-    return Case(name="popgs_criterion", make=make, call=call, exact=("scores", "prior_out"), bounds={"vis": (1, 100)}, same=("accumulate",))
+    return Case(name="popgs_criterion", make=make, call=call, exact=("scores", "prior_out"), bounds={"vis": (1, 100)}, same=("accumulate",),
+                covers=("fr_popgs_diag_criterion",))
+
+
+# -- entry points from before the table had a `covers` column, found by the completeness check ---------------------------------------------
+
+def _forward_features_case(n):
+    """fr_forward_features over the geometry a forward binned beforehand (the buffers are inputs like any other)"""
+    def call(ctx, b):
+        from fisher_rast import ops
+        cam = _camera(SORT_W, SORT_H)
+        P = int(b["means3D"].shape[0])
+        args = (P, SORT_H, SORT_W, cam.tanfovx, cam.tanfovy, 1.0, b["bg"], b["view"], b["proj"], b["campos"])
+        return dict(feature_image=ops.rasterize_forward_features(b["features"], args, b["geom"], b["binning"], b["img"]))
+    return Case(name=f"forward_features_n{n}", make=lambda which: _sort_scene(n, which, features=True), call=call, prepare=_prepare_forward(False),
+                exact=("feature_image",), same=CAMERA_NAMES + ("opacity", "scales", "rotations"), covers=("fr_forward_features",))
+
+
+def _backward_abi_case(n, power):
+    """fr_backward, the entry point without a scratch buffer, through the C ABI (no Python layer calls it): the arguments of
+    ops.rasterize_backward, the same outputs by the same rule"""
+    def call(ctx, b):
+        import torch
+        from fisher_rast import _lib, ops
+        dev = b["means3D"].device
+        cam = _camera(SORT_W, SORT_H)
+        P = int(b["means3D"].shape[0])
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = dict(dL_dmeans2D=new(P, 3), dL_dcolors=new(P, 3), dL_dopacity=new(P, 1), dL_dmeans3D=new(P, 3), dL_dcov3D=new(P, 6),
+                   dL_dscales=new(P, 3), dL_drotations=new(P, 4), dL_dconic=new(P, 2, 2))
+        cfg = ops._raster_cfg(P, SORT_H, SORT_W, cam.tanfovx, cam.tanfovy, 1.0, 0, 0, False, b["bg"], b["view"], b["proj"], b["campos"])
+        g = ops._gaussians(b["means3D"], b["colors"], None, None, b["scales"], b["rotations"], None)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().fr_backward(ctypes.byref(cfg), ctypes.byref(g), b["radii"].data_ptr(), b["geom"].data_ptr(),
+                                               b["binning"].data_ptr(), b["img"].data_ptr(), b["dL"].data_ptr(), power,
+                                               *(out[k].data_ptr() for k in ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D")),
+                                               None, out["dL_dscales"].data_ptr(), out["dL_drotations"].data_ptr(), out["dL_dconic"].data_ptr(),
+                                               ops._stream(dev)), "fr_backward")
+        return out
+    rule = (1e-4, 2e-5)
+    return Case(name=f"backward_abi_p{power}_n{n}", make=lambda which: _sort_scene(n, which, dL=True), call=call, prepare=_prepare_forward(False),
+                close={k: rule for k in ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D")},
+                close_from="test_gpu_rasterizer_parity.py::test_backward_parity (1e-4, atol_frac 2e-5)",
+                same=CAMERA_NAMES + ("opacity", "scales", "rotations"), covers=("fr_backward",))
+
+
+def _backward_pair_abi_case(n):
+    """fr_backward_pair, likewise: the arguments of ops.rasterize_backward_pair without the scratch buffer"""
+    def call(ctx, b):
+        import torch
+        from fisher_rast import _lib, ops
+        dev = b["means3D"].device
+        cam = _camera(SORT_W, SORT_H)
+        P = int(b["means3D"].shape[0])
+        new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        shapes = dict(dL_dmeans2D=(P, 3), dL_dmeans2D_features=(P, 3), dL_dcolors=(P, 3), dL_dfeatures=(P, 3), dL_dopacity=(P, 1), dL_dmeans3D=(P, 3),
+                      dL_dcov3D=(P, 6), dL_dscales=(P, 3), dL_drotations=(P, 4), dL_dconic=(P, 2, 2))
+        out = {k: new(*s) for k, s in shapes.items()}
+        cfg = ops._raster_cfg(P, SORT_H, SORT_W, cam.tanfovx, cam.tanfovy, 1.0, 0, 0, False, b["bg"], b["view"], b["proj"], b["campos"])
+        g = ops._gaussians(b["means3D"], b["colors"], None, None, b["scales"], b["rotations"], None)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().fr_backward_pair(ctypes.byref(cfg), ctypes.byref(g), b["radii"].data_ptr(), b["geom"].data_ptr(),
+                                                    b["binning"].data_ptr(), b["img"].data_ptr(), b["dL"].data_ptr(), b["features"].data_ptr(),
+                                                    b["dLf"].data_ptr(), *(out[k].data_ptr() for k in shapes), ops._stream(dev)), "fr_backward_pair")
+        return out
+    rule = (1e-4, 1e-6)
+    return Case(name=f"backward_pair_abi_n{n}", make=lambda which: _sort_scene(n, which, features=True, dL=True), call=call,
+                prepare=_prepare_forward(True),
+                close={k: rule for k in ("dL_dmeans2D", "dL_dmeans2D_features", "dL_dcolors", "dL_dfeatures", "dL_dopacity", "dL_dmeans3D")},
+                close_from="test_gpu_rasterizer_parity.py::test_fused_rgb_depth_silhouette_pair (1e-4, atol_frac 1e-6)",
+                same=CAMERA_NAMES + ("opacity", "scales", "rotations"), covers=("fr_backward_pair",))
+
+
+FRONTIER_XYZ = 1027
+
+
+def _frontier_map(which):
+    """the door map with a block of unknown cells on its far side: the right-hand columns (real) or the bottom rows of the right-hand
+    room (decoy), so that the free space has a frontier"""
+    occ = _plan_map(which)["occ_map"].copy()
+    block = (slice(None), slice(44, None)) if which == 0 else (slice(36, None), slice(27, None))
+    occ[0][block], occ[1][block], occ[2][block] = 1.0, 0.0, 0.0
+    return occ
+
+
+def _frontier_case():
+    """build_frontiers (free space, fr_occ_frontiers, host reads), sample_random_candidate on the free space it left (erode,
+    fr_occ_free_candidates, a host read) and cells_of (fr_occ_cells_of)"""
+    def make(which):
+        rng = np.random.default_rng([which, 79])
+        return dict(occ_map=_frontier_map(which), xyz=rng.uniform(-1.6, 1.6, (FRONTIER_XYZ, 3)).astype(F))
+
+    def setup(b, dev):
+        p = _planner(_plan_map(0), dev)
+        p.occ_map = b["occ_map"]
+        p.cam_pos = np.array(_plan_map(0)["start"])
+        p.frontier_select_method = "largest"
+        return p
+
+    def call(p, b):
+        import torch
+        # an out-of-range point (far above the height window) makes build_frontiers return the whole cell list, not the one FBE pick
+        probe = torch.tensor([[0.0, 100.0, 0.0]], device=b["occ_map"].device)
+        pts, free = p.build_frontiers(probe)
+        assert pts is not None and len(pts) >= 10, "the map has no frontier: the case proves nothing"
+        poses = p.sample_random_candidate(np.array([0.0, 0.4, 0.0]), None, seed=41)
+        cells = p.cells_of(b["xyz"])
+        return dict(frontier=torch.from_numpy(p.frontier), target=torch.from_numpy(p.target_frontier), selected=torch.from_numpy(pts),
+                    free=torch.from_numpy(free), poses=poses, cells=cells)
+    return Case(name="occupancy_frontiers_free_candidates_cells", make=make, call=call, setup=setup,
+                exact=("frontier", "target", "selected", "free", "poses", "cells"),
+                covers=("fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_free_candidates", "fr_occ_cells_of"))
+
+
+# -- nearest point of another cloud (fisher_rast/cloud.py) ---------------------------------------------------------------------------------
+
+CLOUD_N, CLOUD_M = 1500, 700         # two 1024-point boxes, a ragged last 64-point sub-box (1500 = 23 * 64 + 28)
+CLOUD_DEPTH_HW, CLOUD_DEPTH_STRIDE = (24, 32), 2
+
+
+def _cloud_points_case():
+    def make(which):
+        import cloud_cases as cc
+        t, q = cc.make_case("clusters", CLOUD_N, CLOUD_M, seed=which)
+        return dict(points=t, queries=q)
+
+    def call(ctx, b):
+        from fisher_rast.cloud import CloudIndex
+        return CloudIndex(b["points"]).search(b["queries"], 0.05, dist=True, index=True, flag=True, stats=True)      # the build is on the stream too
+    return Case(name="cloud_build_search", make=make, call=call, exact=("dist", "index", "flag", "stats"), sync_free=True, repeat=True,
+                covers=("fr_cloud_index_build", "fr_cloud_query"))
+
+
+def _cloud_depth_case():
+    def make(which):
+        import cloud_cases as cc
+        c = cc.make_depth_case(*CLOUD_DEPTH_HW, "object", "-Z", seed=which)
+        depth = np.where(np.isfinite(c["depth"]), c["depth"], F(0.0)).astype(F)        # (the table's inputs are finite: inf and NaN pixels become "no depth")
+        return dict(env=c["env"], depth=depth, kinv=np.ascontiguousarray(cc.depth_kinv(c), F), c2w=c["c2w"])
+
+    def call(ctx, b):
+        from fisher_rast.cloud import CloudIndex
+        mask, stats, dist = CloudIndex(b["env"]).query_depth(b["depth"], b["kinv"], b["c2w"], stride=CLOUD_DEPTH_STRIDE, flip_z=True, dist_th=0.05,
+                                                            want_dist=True)
+        return dict(mask=mask, stats=stats, dist=dist)
+    return Case(name="cloud_query_depth", make=make, call=call, exact=("mask", "stats", "dist"), same=("kinv",), sync_free=True, repeat=True,
+                covers=("fr_cloud_index_build", "fr_cloud_query"))
+
+
+# -- DBSCAN and the target selection (fisher_rast/cluster.py) -------------------------------------------------------------------------------
+
+CLUSTER_N = 1500
+SELECT_BAND = (-0.6, 0.6)            # wider than cluster_cases' band: more than 256 of the 1500 rows lie in it (held in test_stream_cases_cpu.py)
+
+
+def _dbscan_case():
+    def make(which):
+        import cluster_cases as cl
+        return dict(points=cl.make_case("blobs", CLUSTER_N, seed=which))
+
+    def call(ctx, b):
+        import cluster_cases as cl
+        from fisher_rast import cluster
+        labels, status = cluster.dbscan_raw(b["points"], cl.EPS, cl.MIN_SAMPLES)
+        return dict(labels=labels, status=status)
+    return Case(name="dbscan_raw", make=make, call=call, exact=("labels", "status"), sync_free=True, repeat=True, covers=("fr_dbscan",))
+
+
+def _select_inputs(which):
+    import cluster_cases as cl
+    means, scores = cl.make_select_case(CLUSTER_N, seed=which)
+    return dict(means3D=means, scores=scores)
+
+
+def _select_target_case():
+    def call(ctx, b):
+        import torch
+        import cluster_cases as cl
+        from fisher_rast import cluster
+        r = cluster.select_target(b["means3D"], b["scores"], SELECT_BAND[0], SELECT_BAND[1], cl.Q, cl.EPS, cl.MIN_SAMPLES)        # one host read inside
+        assert not r.nan_scores
+        return dict(band=r.points_index_range, above=r.points_index, labels=r.labels, selected=r.selected_points_index, threshold=r.threshold.reshape(1),
+                    counts=torch.tensor([r.n_band, r.n_above, r.n_clusters, r.max_label, r.n_selected, r.argmax], dtype=torch.int64))
+    return Case(name="select_target", make=_select_inputs, call=call, exact=("band", "above", "labels", "selected", "threshold", "counts"),
+                covers=("fr_target_select",))
+
+
+# -- render-quality evaluation (ops.view_metrics) ----------------------------------------------------------------------------------------------
+
+EVAL_SHAPE = (3, 24, 40)             # the 11-tap SSIM window fits
+
+
+EVAL_FAMILIES = (("noise", "smooth", "step"), ("smooth", "out_of_range", "noise"))      # per view: real, decoy
+
+
+def _eval_batch(which):
+    """Three views of eval_cases' families with a half mask and a garbage fourth byte.  The decoy is other content, not the real set
+    rearranged: other families per view, every view, mask and alpha from other seeds (a mirrored or permuted batch would give the same
+    sums, hence the same rows up to rounding).  tests/test_stream_cases_cpu.py holds every column of every row apart."""
+    import eval_cases as ec
+    V, H, W = EVAL_SHAPE
+    views = [ec.make_view((H, W), family, v + 10 * which) for v, family in enumerate(EVAL_FAMILIES[which])]
+    rng = np.random.default_rng([which, 107])
+    gt_u8 = np.stack([t[1] for t in views])
+    alpha = rng.integers(0, 256, (V, H, W, 1), dtype=np.uint8)
+    d = dict(render=np.stack([t[0] for t in views]), gt_f32=ec.u8_to_f32(gt_u8), gt_u8x4=np.concatenate((gt_u8, alpha), axis=-1),
+             depth=np.stack([t[2] for t in views]), gt_depth=np.stack([t[3] for t in views]),
+             mask=(rng.uniform(size=(V, H, W)) < 0.5).astype(np.uint8))
+    return {k: np.ascontiguousarray(v) for k, v in d.items()}
+
+
+def _view_metrics_cases():
+    def make_f32(which):
+        d = _eval_batch(which)
+        return {k: d[k] for k in ("render", "gt_f32", "depth", "gt_depth", "mask")}
+
+    def make_u8(which):
+        d = _eval_batch(which)
+        return {k: d[k] for k in ("render", "gt_u8x4")}
+
+    def call_f32(ctx, b):
+        from fisher_rast import ops
+        # (depth_valid_only: the depth count of a row is then the view's number of measured pixels, not H W for every view)
+        r = ops.view_metrics(b["render"], b["gt_f32"], b["depth"], b["gt_depth"], b["mask"], depth_valid_only=True)
+        return dict(rows=r["rows"], summary=r["summary"], summary_of_rows=ops.view_metrics_summary(r["rows"]))
+
+    def call_u8(ctx, b):
+        from fisher_rast import ops
+        r = ops.view_metrics(b["render"], b["gt_u8x4"])
+        return dict(rows=r["rows"], summary=r["summary"], summary_of_rows=ops.view_metrics_summary(r["rows"]))
+    covers = ("fr_view_metrics", "fr_view_metrics_summary")
+    out = ("rows", "summary", "summary_of_rows")
+    return [Case(name="view_metrics_f32_depth_mask", make=make_f32, call=call_f32, exact=out, sync_free=True, repeat=True, covers=covers),
+            Case(name="view_metrics_u8x4", make=make_u8, call=call_u8, exact=out, sync_free=True, repeat=True, covers=covers, images=("gt_u8x4",))]
+
+
+# -- the object-aware training step (fisher_rast/object_loss.py, slam_external.get_gaussians_outside_mask) ------------------------------------
+
+OBJLOSS_SHAPE = (24, 32)
+OUTSIDE_P, OUTSIDE_MASK = 2000, (48, 64)
+
+
+def _loss_mask_case(reject):
+    """loss_pixel_mask with the object mask ANDed in: one launch, or -- reject_outliers -- five, the radix-select median between them"""
+    def make(which):
+        import objloss_cases as oc
+        ds, gt = oc.make_mask_case(OBJLOSS_SHAPE, ("neg_zero_gt", "mostly_unmeasured")[which])
+        return dict(depth_sil=ds, gt_depth=gt, obj=oc.make_obj(OBJLOSS_SHAPE, "half", seed=which))
+
+    def call(ctx, b):
+        import torch
+        import objloss_cases as oc
+        from fisher_rast import object_loss
+        depth, mask = object_loss.loss_pixel_mask(b["depth_sil"], b["gt_depth"], oc.SIL_THRES, reject, True, b["obj"])
+        return dict(mask=mask.view(torch.uint8))
+    return Case(name=f"loss_mask{'_reject_outliers' if reject else ''}", make=make, call=call, exact=("mask",), sync_free=True, repeat=True,
+                covers=("fr_loss_mask",))
+
+
+def _bg_penalty_case():
+    def make(which):
+        import objloss_cases as oc
+        im, ds, obj = oc.make_penalty_case(OBJLOSS_SHAPE, ("plain", "sil_edges")[which], "half")
+        return dict(im=im, depth_sil=ds, obj=obj, upstream=np.array([(0.37, 1.9)[which]], F))
+
+    def call(ctx, b):
+        import torch
+        import objloss_cases as oc
+        from fisher_rast import object_loss
+        im, ds = b["im"].detach().requires_grad_(True), b["depth_sil"].detach().requires_grad_(True)          # leaves over the work buffers
+        penalty = object_loss.background_penalty(im, ds, b["obj"], oc.LAMBDA, oc.LAMBDA)
+        g_im, g_ds = torch.autograd.grad(penalty, (im, ds), grad_outputs=b["upstream"].reshape(()))
+        return dict(penalty=penalty.detach().reshape(1), g_im=g_im, g_depth_sil=g_ds)
+    return Case(name="background_penalty", make=make, call=call, exact=("penalty", "g_im", "g_depth_sil"), same=("obj",), sync_free=True, repeat=True,
+                covers=("fr_bg_penalty_forward", "fr_bg_penalty_backward"))
+
+
+def _outside_mask_case():
+    def make(which):
+        import objloss_cases as oc
+        c = oc.make_outside_case(OUTSIDE_P, OUTSIDE_MASK, 3, "general", seed=which)
+        p = oc.trajectory_params(c)
+        return dict(means3D=c["means"], log_scales=c["logs"], cam_unnorm_rots=p["cam_unnorm_rots"].numpy(), cam_trans=p["cam_trans"].numpy(),
+                    K=c["K"], obj=c["obj"])
+
+    def call(ctx, b):
+        import torch
+        from models.SLAM.utils import slam_external as se
+        params = {k: b[k] for k in ("means3D", "log_scales", "cam_unnorm_rots", "cam_trans")}
+        outside, stats = se.get_gaussians_outside_mask(params, dict(id=1, intrinsics=b["K"]), b["obj"])       # one host read inside
+        ranges = torch.tensor([stats[k] for k in ("inside_scale_min", "inside_scale_max", "outside_scale_min", "outside_scale_max")], dtype=torch.float64)
+        return dict(outside=outside.view(torch.uint8), idx_in=stats["idx_in"], idx_out=stats["idx_out"], ranges=ranges)
+    return Case(name="outside_mask", make=make, call=call, exact=("outside", "idx_in", "idx_out", "ranges"), same=("K", "cam_trans"),
+                covers=("fr_outside_mask",))
+
+
+# -- action planning and the roll-out (planning/astar.py: plan_actions, plan_actions_object; fr_rollout_actions) ---------------------------
+
+ACTION_STEP = dict(forward_step_size=0.065, turn_angle=10.)
+ACTION_QUEUE = 30
+ROLLOUT_LISTS = 70
+
+
+def _action_poses(c, pose_of):
+    """(the agent's pose on the start cell, the goal poses [G, 4, 4] float32 in the middle of the map's goal cells): host values, the same
+    for both door maps.  A cell (row, col) has its middle at ((col, row) - grid_dim // 2 + 0.5) * cell + centre (convert_to_map)."""
+    rng = np.random.default_rng(83)
+    half = np.array([c["W"] // 2, c["H"] // 2])
+    world = lambda row, col: (np.array([col, row]) - half + 0.5) * c["cell"] + np.asarray(c["center"])
+    x, z = world(*c["start"])
+    agent = pose_of(0.3, x, c["cam_height"], z)
+    goals = np.zeros((len(c["goals"]), 4, 4), np.float32)
+    for g, (row, col) in enumerate(c["goals"]):
+        x, z = world(row, col)
+        goals[g] = pose_of(rng.uniform(-np.pi, np.pi), x, rng.uniform(0.2, 1.5), z, np.float32)
+    return agent, goals
+
+
+def _plan_tensors(plan):
+    import torch
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    return dict(n_actions=t(plan.n_actions), keep=t(plan.keep), actions=t(plan.actions), cells=t(plan.map_xz), xz=t(plan.c2w_xz), w2c=plan.w2c)
+
+
+PLAN_OUT = ("n_actions", "keep", "actions", "cells", "xz", "w2c")
+
+
+def _plan_actions_cases():
+    def make(which):
+        return dict(occ_map=_plan_map(which)["occ_map"])
+
+    def setup(b, dev):
+        p = _planner(_plan_map(0), dev)
+        p.occ_map = b["occ_map"]
+        return p
+
+    def call(p, b):
+        import action_cases as ac
+        c = _plan_map(0)
+        agent, goals = _action_poses(c, ac.yaw_pose)
+        p.setup_start(np.array(c["start"]))
+        return _plan_tensors(p.plan_actions(goals, agent, queue_size=ACTION_QUEUE, **ACTION_STEP))
+
+    def call_object(p, b):
+        import torch
+        import goal_cases as gc
+        c = _plan_map(0)
+        agent, goals = _action_poses(c, gc.cam_pose)
+        p.setup_start(np.array(c["start"]))
+        plan = p.plan_actions_object(goals, agent, **ACTION_STEP)
+        flat = np.concatenate([np.asarray(q, np.int64).reshape(-1) for q in plan.pruned] + [np.array([len(q) for q in plan.pruned], np.int64)])
+        return dict(pruned=torch.from_numpy(flat), **_plan_tensors(plan))
+    return [Case(name="plan_actions", make=make, call=call, setup=setup, exact=PLAN_OUT, covers=PLAN_COVERS + ("fr_plan_actions",)),
+            Case(name="plan_actions_object", make=make, call=call_object, setup=setup, exact=PLAN_OUT + ("pruned",),
+                 covers=PLAN_COVERS + ("fr_plan_actions_object",))]
+
+
+def _rollout_case():
+    """fr_rollout_actions through the C ABI (fisher_rast.path_eval.rollout_device takes host lists only): the action lists and their
+    lengths are device buffers"""
+    def make(which):
+        rng = np.random.default_rng([which, 89])
+        return dict(actions=rng.integers(1, 4, (ROLLOUT_LISTS, ACTION_QUEUE)).astype(np.uint8),
+                    lengths=rng.integers(0, ACTION_QUEUE + 1, ROLLOUT_LISTS).astype(np.int32))
+
+    def call(ctx, b):
+        import torch
+        import action_cases as ac
+        from fisher_rast import _lib
+        dev = b["actions"].device
+        w2c = torch.empty((ROLLOUT_LISTS, ACTION_QUEUE, 4, 4), dtype=torch.float32, device=dev)
+        c2w = torch.empty((ROLLOUT_LISTS, ACTION_QUEUE, 4, 4), dtype=torch.float64, device=dev)
+        start = (ctypes.c_double * 16)(*[float(v) for v in ac.yaw_pose(0.3, 0.1, 0.5, -0.2).reshape(-1)])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().fr_rollout_actions(start, b["actions"].data_ptr(), b["lengths"].data_ptr(), ROLLOUT_LISTS, ACTION_QUEUE,
+                                                      ACTION_STEP["forward_step_size"], ACTION_STEP["turn_angle"], w2c.data_ptr(), c2w.data_ptr(),
+                                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "fr_rollout_actions")
+        return dict(w2c=w2c, c2w=c2w)
+    return Case(name="rollout_actions", make=make, call=call, exact=("w2c", "c2w"), bounds={"actions": (1, 4), "lengths": (0, ACTION_QUEUE + 1)},
+                sync_free=True, repeat=True, covers=("fr_rollout_actions",))
+
+
+# -- goal selection of the object round (planning/astar.py: build_object_frontiers, _grid_candidates) ------------------------------------------
+
+OBJECT_BLOCK = 24                    # the object's Gaussians fall into a block of 24 x 24 cells
+OBJECT_COUNTS = (3, 4, 5, 6, 4, 5)   # per cell, in equal shares: a sixth of the cells has exactly 3 (not "more than 3"), 480 cells have more
+GRID_CENTRES = 300
+
+
+def object_points(which):
+    """[N, 3] object Gaussians and the (col, row) of the cells that hold more than 3 of them: a block of cells of the 52 x 46 map, each
+    with 3 to 6 points near its middle (the same total for both input sets)"""
+    c = _plan_map(0)
+    rng = np.random.default_rng([which, 97])
+    col0, row0 = ((10, 10), (22, 14))[which]
+    cols, rows = np.meshgrid(np.arange(col0, col0 + OBJECT_BLOCK), np.arange(row0, row0 + OBJECT_BLOCK))
+    cells = np.stack([cols.ravel(), rows.ravel()], axis=1)
+    counts = rng.permutation(np.resize(np.array(OBJECT_COUNTS), len(cells)))
+    rep = np.repeat(cells, counts, axis=0)
+    mid = (rep - (np.array([c["W"], c["H"]]) - 1) // 2 + 0.5) * c["cell"] + np.asarray(c["center"])        # fr_occ_object_cells' own rule
+    xz = mid + rng.uniform(-0.015, 0.015, mid.shape)
+    pts = np.stack([xz[:, 0], rng.uniform(-0.3, 0.3, len(xz)), xz[:, 1]], axis=1).astype(F)
+    return pts[rng.permutation(len(pts))], cells[counts > 3]
+
+
+def _goal_planner(b, dev):
+    p = _planner(_plan_map(0), dev)
+    p.occ_map = b["occ_map"]
+    p.K_object, p.radius_object, p.min_range_object = 138, 0.9, 0.3
+    return p
+
+
+def _object_goal_cases():
+    def make(which):
+        c = _plan_map(which)
+        return dict(occ_map=c["occ_map"], free=c["free"], points=object_points(which)[0])
+
+    def call(p, b):
+        import torch
+        centres = p.build_object_frontiers(b["points"])                  # reads the number of cells back
+        eroded = p._eroded_free(b["free"], 3)
+        c2w, keep = p._grid_candidates(None, 1, eroded=eroded, min_free=40, seed=11, cells_dev=p._object_cells_dev)
+        return dict(centres=torch.from_numpy(centres), eroded=eroded, c2w=c2w, keep=keep.view(torch.uint8))
+
+    def make_single(which):
+        rng = np.random.default_rng([which, 101])
+        eroded = _plan_map(which)["free"].copy()
+        eroded[:, :4 + 3 * which] = 0
+        return dict(occ_map=_plan_map(which)["occ_map"], centres=rng.uniform(-0.8, 0.8, (GRID_CENTRES, 2)).astype(F), eroded=eroded)
+
+    def call_single(p, b):
+        import torch
+        c2w, keep = p._grid_candidates(b["centres"], 1, eroded=b["eroded"], min_free=40, seed=11)
+        return dict(c2w=c2w, keep=keep.view(torch.uint8))
+    return [Case(name="object_cells_grid_candidates", make=make, call=call, setup=_goal_planner, exact=("centres", "eroded", "c2w", "keep"),
+                 covers=("fr_occ_object_cells", "fr_occ_erode", "fr_occ_grid_candidates")),
+            Case(name="grid_candidates_device_centres", make=make_single, call=call_single, setup=_goal_planner, exact=("c2w", "keep"),
+                 sync_free=True, repeat=True,
+                 covers=("fr_occ_grid_candidates",))]
 
 
 _TABLE = None
@@ -833,6 +1365,10 @@ def cases():
             _mark_visible_case(), *_scorer_cases(), _single_view_front_end_case(), _knn_case(), _spatial_order_case(),
             _image_loss_case(), _adam_case(), _rendervar_case(), _keyframe_case(), _ingest_case(), *_map_edit_cases(), _densify_case(), _popgs_case(),
             _occupancy_case(), _path_plan_case(),
+            _forward_features_case(n), _backward_abi_case(n, 1), _backward_pair_abi_case(n), _frontier_case(),
+            _cloud_points_case(), _cloud_depth_case(), _dbscan_case(), _select_target_case(), *_view_metrics_cases(),
+            _loss_mask_case(False), _loss_mask_case(True), _bg_penalty_case(), _outside_mask_case(),
+            *_plan_actions_cases(), _rollout_case(), *_object_goal_cases(),
         ]
     return _TABLE
 
