@@ -749,7 +749,9 @@ def spatial_order_of(means3D: torch.Tensor) -> torch.Tensor:
     dev = means3D.device
     lib = _lib.load()
     pts = _prep(means3D.detach(), dev)
-    P = int(pts.shape[0])
+    P = int(pts.shape[0]) if pts is not None else 0
+    if P == 0:
+        return torch.zeros((0,), dtype=torch.int32, device=dev)
     order = torch.empty((P,), dtype=torch.int32, device=dev)
     ws = torch.empty((max(int(lib.fr_spatial_order_workspace_bytes(P)), 1),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):

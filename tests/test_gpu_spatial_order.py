@@ -8,26 +8,10 @@ import numpy as np
 import pytest
 import torch
 
+from knn_cases import morton_np as _morton_np          # k_knn_morton restated (test_early_frustum_bound_cpu imports it from here)
 from scenes import rel_err
 
 pytestmark = pytest.mark.gpu
-
-
-def _morton_np(m):
-    """k_knn_morton restated: 10 bits per axis over the bounding box, x lowest"""
-    m = m.astype(np.float32)
-    lo, hi = m.min(0), m.max(0)
-    ext = (hi - lo).astype(np.float32)
-    u = np.where(ext > 0, (m - lo) / np.where(ext > 0, ext, 1), 0).astype(np.float32)
-    q = (np.clip(u, 0, 1) * np.float32(1023.0)).astype(np.uint32).astype(np.uint64)
-
-    def spread(x):
-        x = (x | (x << 16)) & 0x030000FF
-        x = (x | (x << 8)) & 0x0300F00F
-        x = (x | (x << 4)) & 0x030C30C3
-        x = (x | (x << 2)) & 0x09249249
-        return x
-    return spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2)
 
 
 @pytest.mark.parametrize("P", [1, 2, 255, 256, 257, 5000, 70001])
