@@ -19,7 +19,7 @@
 //                                           cub::DeviceRadixSort (rasterizer_impl.cu:304-309).  Keys are unique, so the
 //                                           result equals the reference's stable (tile, depth) order with ties by index.
 //   k_render_forward_walk<3|6>  (T, V)      alpha compositing, median depth, wave-private strips, per-lane walk (forward.cu:261-393)
-//   k_backward_lin_walk / k_backward_lin_tile<pair> + k_backward_finish   grad_power 1 (training): per-splat sums of the screen-space
+//   k_backward_lin_walk / k_backward_lin_tile (two images) + k_backward_finish   grad_power 1 (training): per-splat sums of the screen-space
 //                                           gradients, Jacobian chain once per Gaussian    (backward.cu:850-1140, 276-583)
 //   k_backward_sq_rows + k_backward_sq_walk grad_power 2 through the rasteriser API
 //   k_backward_tile      (T, 1)             generic fused backward, any grad_power, SH colours
@@ -62,22 +62,10 @@
 #include <vector>
 #include <utility>
 static thread_local char g_err[512] = "";
-// The PRODUCT build (__graft_entry__.build()) reads no environment variable and holds only kernels a default call can reach.
-// -DFR_AB (tools/build_variant.sh -> tools/_build/, loaded through FISHER_RAST_SO by tools/ab.sh, loopstats.py, fe_ablate.py) is the
-// experiment rig: FR_DEBUG_MODE / FR_GV / FR_VC / FR_GROUPS / FR_TILE_PRIO and the kernel generations only those switches select.
-#if defined(FR_ABLATE) || defined(FR_LOOPSTATS)
-#ifndef FR_AB
-#define FR_AB
-#endif
-#endif
-#ifdef FR_AB
-#define FR_AB_ONLY(x) x
-static int fr_debug_mode();
-static int fr_env_int(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
-#else
-#define FR_AB_ONLY(x)
-static constexpr int fr_debug_mode() { return 0; }
-#endif
+// The PRODUCT build (__graft_entry__.build()) reads no environment variable.  The experiment rig (-DFR_AB, -DFR_LOOPSTATS,
+// -DFR_ABLATE, -DFR_FWD_STATS: tools/build_variant.sh, loopstats.py, fe_ablate.py, fwd_walk_stats.py) lives in fr_rig.inc; every
+// hook of it below (FR_AB_ONLY, FR_ABL, FR_STATS*, FR_FWD*) expands to nothing here.
+#include "fr_rig.inc"
 // measurement only: HIP events recorded around the dominant kernel on the stream it is launched on
 static bool g_prof_on = false;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_events;
@@ -142,15 +130,9 @@ struct FrParams {
 	                             // the projection kernel itself (k_preprocess_views_c<.., true>): no scan dependency, no scatter kernel
 	uint32_t small_max;          // lists of up to this many keys are sorted by k_sort_tiles, longer ones are listed for the other sort kernels
 	const uint32_t* order;       // [P] or null (fr_fisher_cfg.order): position -> the caller's Gaussian index; records modes of the multi-view front end only
-	int legacy_sort;             // FR_DEBUG_MODE=6: the LDS-resident sort network of round 1 (A/B runs)
 	int prefiltered;             // GaussianRasterizationSettings.prefiltered (single-view API): a near-plane-culled point raises status[3]
-	int ablate;                  // -DFR_ABLATE builds only (tools/fe_ablate.py): FR_DEBUG_MODE 30..34 drop parts of the direct key scatter
+	FR_ABL(int ablate;)          // -DFR_ABLATE builds only (tools/fe_ablate.py): FR_ABLATE_MODE, 30..37 drop parts of the front end
 };
-#ifdef FR_ABLATE
-#define FR_ABL(x) x
-#else
-#define FR_ABL(x)
-#endif
 
 __device__ __forceinline__ float wave_sum(float v)
 {
@@ -672,20 +654,14 @@ __device__ __forceinline__ void fr_fisher_record_general(const FrParams& p, cons
 //            32-byte splat record, the per-(view, tile) LDS histogram, and one 16-byte entry per VISIBLE pair in
 //            this workgroup's compact list, which is all k_scatter_vis reads (no radii array, no idle lanes).
 // The arithmetic per pair is fr_preprocess_one's, so radii / rects / depths are bit-identical to k_preprocess.
-//   phase C  (RC != 0: score-only mode) the workgroup walks the compact lists it has just written and turns every visible
-//            (view, Gaussian) into the scorer's record (fr_fisher_record_one) while the splat records are still in L2.
-template <int RC, bool PHASE_C>
+// This is the record-less form (no scorer plan); the records modes go to k_preprocess_views_c below.  (`ra` is not read.)
 __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrRecordArgs ra)
 {
-	extern __shared__ uint32_t fr_dyn_lds[];     // hist[VC][T] | pairs[FR_THREADS * VC] | wm[VC][12] | visible bitmap[VC][8 G] | its prefix popcounts[VC][8 G]
+	extern __shared__ uint32_t fr_dyn_lds[];     // hist[VC][T] | pairs[FR_THREADS * VC] | wm[VC][12]
 	const int VC = p.VC;
 	uint32_t* hist = fr_dyn_lds;
 	uint32_t* pairs = hist + (size_t)VC * p.T;
 	float* s_wm = (float*)(pairs + FR_THREADS * VC);
-	const int W32 = 8 * p.G;                     // 32-bit words of a view's visibility bitmap over the workgroup's 256 G Gaussians
-	uint32_t* s_bm = (uint32_t*)(s_wm + 12 * VC);
-	uint32_t* s_pf = s_bm + VC * W32;
-	const bool compact = RC != 0 && ra.comp != nullptr;
 	__shared__ uint32_t s_np;
 	__shared__ uint32_t s_n[FR_VC_MAX];
 	__shared__ uint32_t s_ref[FR_VC_MAX];        // tile instances by the reference's rule (radius rectangle), per view
@@ -699,7 +675,6 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 	if (has_w2c) for (int t = tid; t < nv * 12; t += FR_THREADS) s_wm[t] = p.w2c[16 * (size_t)(v0 + t / 12) + (t % 12)];
 	if (tid < FR_VC_MAX) { s_n[tid] = 0; s_ref[tid] = 0; }
 	if (tid == 0) s_np = 0;
-	if (compact) for (int t = tid; t < nv * W32; t += FR_THREADS) s_bm[t] = 0u;
 	float vm[16], pm[16];
 #pragma unroll
 	for (int k = 0; k < 16; k++) { vm[k] = p.view[k]; pm[k] = p.proj[k]; }
@@ -714,42 +689,11 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 			const bool live = i < p.P;
 			fr_f3 pw = { 0.f, 0.f, 0.f };
 			if (live) pw = fr_f3{ p.means3D[3 * (size_t)i], p.means3D[3 * (size_t)i + 1], p.means3D[3 * (size_t)i + 2] };
-			// Early frustum test (records modes): about half of the splats in front of the camera end with an empty tile rectangle
-			// (forward.cu:233-236) -- after the whole cov2D chain.  radius = ceil(3 sqrt(lambda1)) and
-			//   lambda1 <= lambda_max(cov2D) + 0.3 + sqrt(0.1),   lambda_max(cov2D) <= |J|_F^2 lambda_max(cov3D),
-			//   |J|_F^2 = (fx^2 (1 + jx^2) + fy^2 (1 + jy^2)) / z^2,  jx = min(|x / z|, 1.3 tan_fovx) (the clamp of forward.cu:80-84),
-			// times |W|_2^2 of the view matrix's 3 x 3, and lambda_max(cov3D) <= trace(cov3D) (k_pack_static), so a centre further than
-			// that bound (+ 2 % and 2 px for rounding) outside the tile grid cannot touch it.  NaNs keep the pair.
-			const bool early = RC != 0 && ra.early != 0 && ra.mt != nullptr;
-			float tr = 0.f;
-			if (early && live) tr = ra.mt[i].w;
-			const float lx = 1.3f * p.tanfovx, ly = 1.3f * p.tanfovy;
-			// |W|_2^2 <= |W|_1 |W|_inf for the 3 x 3 of the view matrix (1 for the identity the scorer's camera has)
-			float wn;
-			{
-				const float c0 = fabsf(vm[0]) + fabsf(vm[1]) + fabsf(vm[2]), c1 = fabsf(vm[4]) + fabsf(vm[5]) + fabsf(vm[6]), c2 = fabsf(vm[8]) + fabsf(vm[9]) + fabsf(vm[10]);
-				const float r0 = fabsf(vm[0]) + fabsf(vm[4]) + fabsf(vm[8]), r1 = fabsf(vm[1]) + fabsf(vm[5]) + fabsf(vm[9]), r2 = fabsf(vm[2]) + fabsf(vm[6]) + fabsf(vm[10]);
-				wn = fmaxf(c0, fmaxf(c1, c2)) * fmaxf(r0, fmaxf(r1, r2));
-			}
-			const float fx2 = 1.02f * wn * p.focal_x * p.focal_x, fy2 = 1.02f * wn * p.focal_y * p.focal_y;
-			const float xmax = (float)(p.gx * FR_BLOCK_X + FR_BLOCK_X), ymax = (float)(p.gy * FR_BLOCK_Y + FR_BLOCK_Y);
 			for (int vv = 0; vv < nv; vv++)
 			{
 				const fr_f3 po = has_w2c ? fr_world_to_cam(pw, s_wm + 12 * vv) : pw;
 				const fr_f3 p_view = fr_xform4x3(po, vm);
-				bool keep = live && !(p_view.z <= 0.001f);
-				if (early)
-				{
-					const fr_f4 ph = fr_xform4x4(po, pm);
-					const float p_w = 1.0f / (ph.w + 0.0000001f);
-					const float px = ((ph.x * p_w + 1.0f) * (float)p.W - 1.0f) * 0.5f, py = ((ph.y * p_w + 1.0f) * (float)p.H - 1.0f) * 0.5f;   // ndc2pix in float: the slack covers it
-					const float iz = 1.0f / p_view.z;
-					const float jx = fminf(fabsf(p_view.x * iz) * 1.001f, lx), jy = fminf(fabsf(p_view.y * iz) * 1.001f, ly);
-					const float kc = fx2 * (1.0f + jx * jx) + fy2 * (1.0f + jy * jy);
-					const float rb = 3.0f * sqrtf(kc * tr * (iz * iz) + 0.7f) + 2.0f;
-					const bool outside = (px + rb < 0.f) || (px - rb > xmax) || (py + rb < 0.f) || (py - rb > ymax);
-					keep = keep && !outside;
-				}
+				const bool keep = live && !(p_view.z <= 0.001f);
 				const unsigned long long m = __ballot(keep);
 				if (m)
 				{
@@ -769,26 +713,10 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 			const int i = i0 + (int)(pr & 255u);
 			const int vv = (int)(pr >> 8);
 			const int v = v0 + vv;
-			// mean, cov3D and colour of the Gaussian: three 16-byte loads of its packed static record when there is one (records
-			// modes), thirteen scattered dwords otherwise -- the same values either way
-			fr_f3 pw;
+			const fr_f3 pw = fr_f3{ p.means3D[3 * (size_t)i], p.means3D[3 * (size_t)i + 1], p.means3D[3 * (size_t)i + 2] };
 			float c3[6];
-			float cg = 0.f;
-			if constexpr (RC != 0)
-			{
-				constexpr int PSB = FrPackSize<(RC < 0 ? -RC : RC)>::value;
-				const float4* pk = (const float4*)(ra.packed + (size_t)i * PSB);
-				const float4 t0 = pk[0], t1 = pk[1], t2 = pk[2];
-				pw = fr_f3{ t0.x, t0.y, t0.z };
-				c3[0] = t0.w; c3[1] = t1.x; c3[2] = t1.y; c3[3] = t1.z; c3[4] = t1.w; c3[5] = t2.x;
-				cg = t2.y + t2.z + t2.w;
-			}
-			else
-			{
-				pw = fr_f3{ p.means3D[3 * (size_t)i], p.means3D[3 * (size_t)i + 1], p.means3D[3 * (size_t)i + 2] };
 #pragma unroll
-				for (int k = 0; k < 6; k++) c3[k] = p.cov3D[6 * (size_t)i + k];
-			}
+			for (int k = 0; k < 6; k++) c3[k] = p.cov3D[6 * (size_t)i + k];
 			float wm[12];
 			if (has_w2c)
 			{
@@ -803,25 +731,8 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 				const uint32_t ext = fr_alpha_extent(s.conx, s.cony, s.conz, o);
 				const uint32_t slot = atomicAdd(&s_n[vv], 1u);          // position in this workgroup's list of the view
 				float4* dst = (float4*)(p.splat + (size_t)v * p.P + i);
-				if (compact)
-				{
-					// {recA, recB} wait beside the list entry (the [V][P] splat region serves as [V][workgroup][256 G] here) until
-					// phase C knows the Gaussian's rank among the workgroup's visible ones
-					dst = (float4*)(p.splat + ((size_t)v * nblk + blockIdx.x) * cap + slot);
-					const uint32_t local = (uint32_t)(i - (int)(blockIdx.x * cap));
-					atomicOr(&s_bm[vv * W32 + (int)(local >> 5)], 1u << (local & 31u));
-				}
-				if constexpr (RC != 0)
-				{
-					// score-only mode: the scorer's {recA, recB} form straight away (see k_fisher_tile_v3)
-					dst[0] = make_float4(s.px, s.py, __uint_as_float(ext), __builtin_amdgcn_logf(o));
-					dst[1] = make_float4(-0.5f * s.conx, -s.cony, -0.5f * s.conz, cg);
-				}
-				else
-				{
-					dst[0] = make_float4(s.px, s.py, s.conx, s.cony);
-					dst[1] = make_float4(s.conz, o, s.depth, __uint_as_float(ext));
-				}
+				dst[0] = make_float4(s.px, s.py, s.conx, s.cony);
+				dst[1] = make_float4(s.conz, o, s.depth, __uint_as_float(ext));
 				// The reference lists the splat in every tile of its radius rectangle (rasterizer_impl.cu:70-111).  The scorer
 				// only ever uses a list entry where alpha can reach 1/255, so the rectangle is cut down to the tiles that the
 				// conservative alpha footprint (ext: half extents, rounded up) touches -- 16 % fewer keys to scatter, sort and
@@ -875,56 +786,13 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 		if (p.vis_count && s_n[tid]) atomicAdd(&p.vis_count[v], (int)s_n[tid]);
 		if (p.num_rendered && s_ref[tid]) atomicAdd(&p.num_rendered[v], (int)s_ref[tid]);
 	}
-	if constexpr (RC != 0 && PHASE_C)
-	{
-		// ---- phase C: the entries and splat records were written by this workgroup (same CU, same L1): visible after a barrier
-		__syncthreads();
-		if (compact)
-		{
-			// exclusive prefix popcounts of the bitmaps: rank of a Gaussian = prefix of its word + popcount of the lower bits
-			for (int t = tid; t < nv * W32; t += FR_THREADS)
-			{
-				const int vv = t / W32, w = t - vv * W32;
-				uint32_t acc = 0;
-				for (int u = 0; u < w; u++) acc += (uint32_t)__popc(s_bm[vv * W32 + u]);
-				s_pf[t] = acc;
-			}
-			__syncthreads();
-		}
-		const size_t PV = (size_t)nblk * cap;
-		for (int vv = 0; vv < nv; vv++)
-		{
-			const int v = v0 + vv;
-			const uint32_t n = s_n[vv];
-			FrVisEntry* list = p.vis_list + ((size_t)v * nblk + blockIdx.x) * cap;
-			float wm[12];
-#pragma unroll
-			for (int k = 0; k < 12; k++) wm[k] = has_w2c ? s_wm[12 * vv + k] : 0.f;
-			for (uint32_t e = tid; e < n; e += FR_THREADS)
-			{
-				const uint32_t idx = list[e].idx;
-				if (compact)
-				{
-					const uint32_t local = idx - blockIdx.x * cap;
-					const uint32_t rank = s_pf[vv * W32 + (int)(local >> 5)] + (uint32_t)__popc(s_bm[vv * W32 + (int)(local >> 5)] & ((1u << (local & 31u)) - 1u));
-					const uint32_t slot = blockIdx.x * cap + rank;
-					const float4* tmp = (const float4*)(p.splat + ((size_t)v * nblk + blockIdx.x) * cap + e);
-					fr_fisher_record_one<(RC < 0 ? -RC : RC), false, (RC < 0)>(p, ra.H_inv, ra.hinv_stride, ra.packed, ra.recq, v, idx, vm, pm, wm, has_w2c,
-					                                                           ra.comp + ((size_t)v * PV + slot) * 6, tmp);
-					list[e].idx = slot;                                  // the keys carry the slot from here on
-					if constexpr (RC < 0) ra.slot_idx[(size_t)v * PV + slot] = idx;   // (only k_fisher_tile_v3h goes back to the index)
-				}
-				else fr_fisher_record_one<(RC < 0 ? -RC : RC), false, (RC < 0)>(p, ra.H_inv, ra.hinv_stride, ra.packed, ra.recq, v, idx, vm, pm, wm, has_w2c);
-			}
-		}
-	}
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // The same front end with the compact scorer records written ONCE, in their final place (the product path of the score-only and
-// out_H record modes).  k_preprocess_views<RC, true> parks every visible splat's {recA, recB} in global memory until its phase C
-// knows the splat's slot, reads them back, and rewrites the list entry: 1.7x the bytes the records need
-// (profiles/r02_n_pmc_all.txt: WRITE_SIZE 1.46 GB against 0.86 GB of records per 64-view step).  Here a batch of 256 survivors is
+// out_H record modes).  (Round 2's form parked every visible splat's {recA, recB} in global memory until a phase C of its own
+// knew the splat's slot, read them back, and rewrote the list entry: 1.7x the bytes the records need, profiles/r02_n_pmc_all.txt:
+// WRITE_SIZE 1.46 GB against 0.86 GB of records per 64-view step.)  Here a batch of 256 survivors is
 //   B   projected (the same arithmetic: fr_preprocess_one), and the visible ones are RANKED IN ORDER with wave ballots: the
 //       survivor list of a workgroup is grouped by view and ascending in the Gaussian index inside a view, so a visible pair's
 //       rank among its view's visible splats -- its slot, monotone in the index -- is the view's running count + the visible
@@ -933,7 +801,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_preprocess_views(FrParams p, FrR
 //   C   thread r takes the r-th visible pair of the batch at full lane occupancy: Jacobian rows / polynomial
 //       (fr_fisher_record_one), and writes the 96-byte record to its slot and the 16-byte list entry beside it -- consecutive
 //       threads, consecutive records.
-// No bitmaps, no prefix popcounts, no second pass over the lists.  Records, lists and counts are identical to the other form's.
+// No bitmaps, no prefix popcounts, no second pass over the lists.
 // DK (direct keys, FrParams::tile_cap > 0): every (view, tile) owns a fixed segment of the key buffer, so a workgroup needs no
 // scan of the tile counts to place its keys: once its histogram is complete it claims its ranges (the same one atomic per
 // non-empty (view, tile) that the other form uses for blk_base) and scatters the keys of its own visible lists right away,
@@ -1894,16 +1762,6 @@ __device__ __forceinline__ void fr_sort_short_list(const FrParams& p, uint64_t* 
 	const uint32_t n = p.tile_cnt[vt];
 	if (n < 2 || n > p.small_max) return;
 	uint64_t* gk = p.keys + p.tile_off[vt];
-#ifdef FR_AB
-	if (p.legacy_sort)
-	{
-		for (uint32_t i = tid; i < n; i += FR_THREADS) skeys[i] = gk[i];
-		__syncthreads();
-		fr_bitonic(skeys, n, tid, FR_THREADS);
-		for (uint32_t i = tid; i < n; i += FR_THREADS) gk[i] = skeys[i];
-		return;
-	}
-#endif
 	if (n <= 512u)
 	{
 		if (tid >= 64) return;
@@ -2096,16 +1954,6 @@ __global__ __launch_bounds__(FR_THREADS) void k_sort_mid_tiles(FrParams p, uint3
 		if (n > (uint32_t)FR_SORT_MID_KEYS || n <= part_max) continue;        // (n <= part_max: k_sort_split's list)
 		uint64_t* gk = p.keys + p.tile_off[vt];
 		__syncthreads();
-#ifdef FR_AB
-		if (p.legacy_sort)
-		{
-			for (uint32_t i = tid; i < n; i += FR_THREADS) skeys[i] = gk[i];
-			__syncthreads();
-			fr_bitonic(skeys, n, tid, FR_THREADS);
-			for (uint32_t i = tid; i < n; i += FR_THREADS) gk[i] = skeys[i];
-		}
-		else
-#endif
 		fr_sort_wg_segment<16, 4>(skeys, gk, n, tid);
 	}
 }
@@ -2124,15 +1972,6 @@ __global__ __launch_bounds__(1024) void k_sort_big_tiles(FrParams p, uint32_t pa
 		uint64_t* gk = p.keys + p.tile_off[vt];
 		__syncthreads();
 		if (n > (uint32_t)FR_SORT_BIG_KEYS) fr_bitonic(gk, n, tid, 1024);
-#ifdef FR_AB
-		else if (p.legacy_sort)
-		{
-			for (uint32_t i = tid; i < n; i += 1024) skeys[i] = gk[i];
-			__syncthreads();
-			fr_bitonic(skeys, n, tid, 1024);
-			for (uint32_t i = tid; i < n; i += 1024) gk[i] = skeys[i];
-		}
-#endif
 		else if (n <= 8192u) fr_sort_wg_segment<8, 16>(skeys, gk, n, tid);
 		else fr_sort_wg_segment<16, 16>(skeys, gk, n, tid);
 	}
@@ -2152,131 +1991,6 @@ __device__ __forceinline__ bool fr_pair_alpha(float xyx, float xyy, float pfx, f
 	alpha = fminf(0.99f, o * G);
 	if (alpha < 1.0f / 255.0f) return false;
 	return true;
-}
-
-// Forward compositing (forward.cu:261-393), wave-private: a wave owns the 16x4 strip of rows 4w..4w+3, streams the tile's sorted
-// keys 64 at a time, keeps the splats whose conservative alpha footprint meets its strip (one ballot) and walks the set bits in
-// order with v_readlane broadcasts -- no LDS staging, no barrier, and a wave only evaluates the ~1/3 of the tile's splats that
-// can reach its pixels.  A skipped splat is one whose alpha is below 1/255 on every pixel of the strip, i.e. one the reference
-// skips pixel by pixel, so colour, depth, final_T and n_contrib are unchanged (bit-identical to the oracle).
-// NCH = 6: a second [P,3] feature array composited in the same pass (fr_forward_pair).
-template <int NCH>
-__global__ __launch_bounds__(FR_THREADS) void k_render_forward(FrParams p, const float* __restrict__ feat, int feat_view_stride,
-                                                               float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
-                                                               float* __restrict__ out_color, float* __restrict__ out_depth,
-                                                               const float* __restrict__ feat2, float* __restrict__ out_color2)
-{
-	if (p.status[1]) return;
-	const int tid = threadIdx.x, lane = tid & 63;
-	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const int v = blockIdx.y;
-	const uint32_t tile = blockIdx.x;
-	const uint32_t tx = tile % p.gx, ty = tile / p.gx;
-	const uint32_t pxx = tx * FR_BLOCK_X + (tid & 15), pxy = ty * FR_BLOCK_Y + (tid >> 4);
-	const bool inside = pxx < (uint32_t)p.W && pxy < (uint32_t)p.H;
-	const float pfx = (float)pxx, pfy = (float)pxy;
-	const size_t vt = (size_t)v * p.T + tile;
-	const size_t vP = (size_t)v * p.P;
-	const uint32_t n = p.tile_cnt[vt];
-	const uint64_t* gk = p.keys + p.tile_off[vt];
-	const float4* splat = (const float4*)(p.splat + vP);
-	const float* fv = feat + (size_t)v * feat_view_stride;
-
-	unsigned long long done_m = __builtin_amdgcn_ballot_w64(!inside);
-	float T = 1.0f;
-	uint32_t last_contributor = 0;
-	float C[NCH];
-#pragma unroll
-	for (int c = 0; c < NCH; c++) C[c] = 0.f;
-	float D = 15.0f;
-	const float strip_lo = (float)(ty * FR_BLOCK_Y + 4u * (uint32_t)wave), strip_hi = strip_lo + 3.0f;
-	const float tile_x0 = (float)(tx * FR_BLOCK_X), tile_x1 = tile_x0 + 15.0f;
-
-	uint64_t kn = ((uint32_t)lane < n) ? gk[lane] : 0ull;
-	for (uint32_t base = 0; base < n; base += 64)
-	{
-		const uint64_t key = kn;
-		if (base + 64 + lane < n) kn = gk[base + 64 + lane];
-		const bool valid = base + lane < n;
-		const uint32_t id = (uint32_t)key;
-		float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f), q1 = q0;
-		if (valid) { q0 = splat[2 * (size_t)id]; q1 = splat[2 * (size_t)id + 1]; }
-		const uint32_t eb = __float_as_uint(q1.w);
-		const float hx = __half2float(__ushort_as_half((unsigned short)(eb & 0xffffu)));
-		const float hy = __half2float(__ushort_as_half((unsigned short)(eb >> 16)));
-		const bool ov = valid && hx >= 0.f && (q0.y + hy >= strip_lo) && (q0.y - hy <= strip_hi) && (q0.x + hx >= tile_x0) && (q0.x - hx <= tile_x1);
-		unsigned long long todo = __ballot(ov);
-		if (todo == 0ull) continue;
-		const float thr_l = fr_power_threshold(q1.y);
-		const float dep_l = fr_as_f32((uint32_t)(key >> 32));
-		float fl[NCH];
-#pragma unroll
-		for (int c = 0; c < NCH; c++) fl[c] = 0.f;
-		if (ov)
-		{
-			fl[0] = fv[3 * (size_t)id]; fl[1] = fv[3 * (size_t)id + 1]; fl[2] = fv[3 * (size_t)id + 2];
-			if constexpr (NCH == 6) { fl[3] = feat2[3 * (size_t)id]; fl[4] = feat2[3 * (size_t)id + 1]; fl[5] = feat2[3 * (size_t)id + 2]; }
-		}
-		while (todo)
-		{
-			const int j = __builtin_ctzll(todo);
-			todo &= todo - 1ull;
-			const float x = fr_readlane_f(q0.x, j), y = fr_readlane_f(q0.y, j);
-			const float cx = fr_readlane_f(q0.z, j), cy = fr_readlane_f(q0.w, j), cz = fr_readlane_f(q1.x, j);
-			const float o = fr_readlane_f(q1.y, j), thr = fr_readlane_f(thr_l, j);
-			const float dx = x - pfx, dy = y - pfy;
-			const float power = -0.5f * (cx * dx * dx + cz * dy * dy) - cy * dx * dy;
-			// forward.cu:338-357; NaN falls through both tests as it does there
-			const unsigned long long skip_m = __builtin_amdgcn_fcmpf(power, 0.0f, 2 /* ogt */) | __builtin_amdgcn_fcmpf(power, thr, 4 /* olt */);
-			const unsigned long long pass_m = ~(skip_m | done_m);
-			if (pass_m)
-			{
-				const float G = fr_expf(power);
-				const float alpha = fminf(0.99f, o * G);
-				const unsigned long long ok_m = pass_m & ~__builtin_amdgcn_fcmpf(alpha, 1.0f / 255.0f, 4 /* olt */);
-				const float test_T = T * (1 - alpha);
-				const unsigned long long kill_m = ok_m & __builtin_amdgcn_fcmpf(test_T, 0.0001f, 4 /* olt */);
-				const unsigned long long contrib_m = ok_m & ~kill_m;
-				done_m |= kill_m;
-				if (contrib_m)
-				{
-					const bool contrib = __builtin_amdgcn_inverse_ballot_w64(contrib_m);
-#pragma unroll
-					for (int c = 0; c < NCH; c++)
-					{
-						const float fc = fr_readlane_f(fl[c], j);
-						const float add = fc * alpha * T;
-						C[c] = contrib ? C[c] + add : C[c];
-					}
-					const float dj = fr_readlane_f(dep_l, j);
-					D = (contrib && T > 0.5f && test_T < 0.5f) ? dj : D;
-					T = contrib ? test_T : T;
-					last_contributor = contrib ? (base + (uint32_t)j + 1u) : last_contributor;
-				}
-			}
-		}
-		if (done_m == ~0ull) break;
-	}
-	if (inside)
-	{
-		const size_t HW = (size_t)p.H * p.W;
-		const size_t pix = (size_t)p.W * pxy + pxx;
-		final_T[v * HW + pix] = T;
-		n_contrib[v * HW + pix] = last_contributor;
-		if (out_color)
-		{
-			out_color[(v * 3 + 0) * HW + pix] = C[0] + T * p.bg[0];
-			out_color[(v * 3 + 1) * HW + pix] = C[1] + T * p.bg[1];
-			out_color[(v * 3 + 2) * HW + pix] = C[2] + T * p.bg[2];
-		}
-		if constexpr (NCH == 6)
-		{
-			out_color2[(v * 3 + 0) * HW + pix] = C[3] + T * p.bg[0];
-			out_color2[(v * 3 + 1) * HW + pix] = C[4] + T * p.bg[1];
-			out_color2[(v * 3 + 2) * HW + pix] = C[5] + T * p.bg[2];
-		}
-		if (out_depth) out_depth[v * HW + pix] = D;
-	}
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2387,12 +2101,12 @@ struct FrFisherArgs {
 	float dL;                    // constant upstream gradient
 	const float* dL_img;         // or per view an upstream-gradient image [V][3][H][W] (out_H modes only), stride in floats
 	long long dL_stride;
-	float* full_out[8];          // k_fisher_tile_v2<25>: dL_dmeans3D, dL_dopacity, dL_dscales, dL_drotations, dL_dcolors, dL_dmeans2D, dL_dcov3D, dL_dconic
+	float* full_out[8];          // (no kernel reads these any more; they keep the layout of the kernel argument)
 	const float* H_inv; long long hinv_stride;
 	float* out_H; long long outH_stride;
 	float* tile_scores;          // [V][T] partial sums, reduced in fixed order by k_reduce_scores
 	const uint8_t* only_flagged; // [V][T] or null: when set, k_fisher_tile handles only the flagged tiles
-	int debug_mode;              // FR_DEBUG_MODE env (timing ablations only): 1 = k_fisher_tile_v2 stops after pass 1
+	FR_AB_ONLY(int debug_mode;)  // -DFR_AB builds only: FR_DEBUG_MODE, 1 = k_fisher_tile_v2 stops after pass 1
 	int key_shift;               // 0: keys = depth | index; 4: keys = depth | slot << 4 | strips (fixed key segments: k_preprocess_views_c<.., true>)
 	// the scorer's records as k_fisher_tile_v3 / _v3h address them: record r of view v has {recA, recB} at recA[v * ab_view + r * ab_stride]
 	// (+ 1) and its four recQ float4 at recQ[v * q_view + r * q_stride + k] -- two dense [V][P] arrays (strides 2 and 4), or the
@@ -2400,6 +2114,8 @@ struct FrFisherArgs {
 	const float4* recA; long long ab_view; int ab_stride;
 	const float4* recQ; long long q_view; int q_stride;
 	const uint32_t* slot_idx; long long slot_view;
+	FR_STATS(int stat_mode;)     // -DFR_LOOPSTATS builds only (tools/loopstats.py): FR_LOOPSTATS_MODE, the counter a tile kernel returns in place of its score
+	FR_ABL(int ablate;)          // -DFR_ABLATE builds only (tools/fe_ablate.py --outh / --point): FR_ABLATE_MODE 28 / 29
 };
 
 template <int C, bool HAS_HINV, bool HAS_OUTH>
@@ -2685,13 +2401,10 @@ __global__ __launch_bounds__(FR_THREADS) void k_pack_static(FrParams p, const fl
 			for (int k = 0; k < 4; k++) b[15 + k] = p.rots[4 * src + k];
 			o = 19;
 		}
-		if constexpr (C <= 11)
+		if (H_inv)
 		{
-			if (H_inv)
-			{
 #pragma unroll
-				for (int c = 0; c < C; c++) b[o + c] = H_inv[src * C + c];
-			}
+			for (int c = 0; c < C; c++) b[o + c] = H_inv[src * C + c];
 		}
 		float4* dst = (float4*)(packed + (size_t)i * PS);
 #pragma unroll
@@ -2767,20 +2480,13 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 	// QFORM (score only): the weighted sum of squared leaves is a quadratic form in u',
 	//   sum_c H_inv[c] (M_c . u')^2 = u'^T Q u',  Q = sum_c H_inv[c] M_c^T M_c  (5 x 5 symmetric, 15 numbers),
 	// so the walk fetches rgb[3], Q[15], k3 instead of 51 values per entry, whatever the number of columns.
-	// C = 25 (FULL): every leaf of the rasteriser's power-2 backward (backward.cu:1095-1137) for one view -- camera-frame mean 3,
-	// opacity 1, scale 3, rotation 4, colour 3, mean2D 2, cov3D 6, conic 3 -- summed per Gaussian into the gradient tensors
-	// of fr_backward (f.full_out); the per-entry record then also carries B' = -1/2 d(dL_dcov3D)/d(dL_dconic) (18 numbers).
 	constexpr bool SR = C >= 11;
-	constexpr bool FULL = C == 25;
-	static_assert(!FULL || (HAS_OUTH && !HAS_HINV), "the all-leaves mode has no weights");
 	constexpr bool QFORM = HAS_HINV && !HAS_OUTH;
-	constexpr int KO = QFORM ? 18 : (FULL ? 57 : (SR ? 39 : 18));   // offset of k3 = 1/opacity^2 (times H_inv[3] when only the score is wanted)
+	constexpr int KO = QFORM ? 18 : (SR ? 39 : 18);   // offset of k3 = 1/opacity^2 (times H_inv[3] when only the score is wanted)
 	constexpr int HO = KO + 1;                    // offset of the H_inv columns
 	constexpr bool FOLD3 = HAS_HINV && !HAS_OUTH; // H_inv[3] folded into k3
 	constexpr int NB = QFORM ? 19 : HO + (HAS_HINV ? C : 0);
-	// per-wave contributor list; the all-leaves mode trades 256 entries of it for a second resident workgroup (its 25 double
-	// accumulators per candidate take 50 KiB: 80 KiB in all)
-	constexpr int WCAP = FULL ? FR_WCAP - 256 : FR_WCAP;
+	constexpr int WCAP = FR_WCAP;                 // per-wave contributor list
 	__shared__ uint16_t s_wl[4][WCAP];
 	__shared__ float s_red[4];
 	__shared__ int s_ovf;
@@ -2820,12 +2526,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 	float T = 1.0f;
 	int last = 0;
 	int wcnt = 0;                                  // wave-uniform
-#ifdef FR_LOOPSTATS
-	int dbg_p1 = 0, dbg_chunks = 0, dbg_steps = 0, dbg_hits = 0, dbg_p1any = 0, dbg_p1con = 0;   // -DFR_LOOPSTATS + FR_DEBUG_MODE >= 2: loop-trip counters
-#define FR_STAT(x) x
-#else
-#define FR_STAT(x)
-#endif
+	FR_STATS_DECLARE
 	const float strip_lo = (float)(ty * FR_BLOCK_Y + 4u * (uint32_t)wave), strip_hi = strip_lo + 3.0f;
 	const float tile_x0 = (float)(tx * FR_BLOCK_X), tile_x1 = tile_x0 + 15.0f;
 	float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0;
@@ -2853,7 +2554,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 		{
 			const int j = __builtin_ctzll(todo);
 			todo &= todo - 1ull;
-			FR_STAT(dbg_p1++;)
+			FR_STATS(ls.cand++;)
 			const float x = fr_readlane_f(q0.x, j), y = fr_readlane_f(q0.y, j);
 			const float hcx = fr_readlane_f(hcx_l, j), ncy = fr_readlane_f(ncy_l, j), hcz = fr_readlane_f(hcz_l, j);
 			const float lo = fr_readlane_f(lo_l, j);
@@ -2865,7 +2566,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 			const unsigned long long pass_m = ~(skip_m | done_m);
 			if (pass_m)
 			{
-				FR_STAT(dbg_p1any++;)
+				FR_STATS(ls.p1any++;)
 				const float alpha = fminf(0.99f, __builtin_amdgcn_exp2f(e));
 				const float test_T = T * (1 - alpha);
 				const unsigned long long kill_m = pass_m & __builtin_amdgcn_fcmpf(test_T, 0.0001f, 4 /* olt */);
@@ -2873,7 +2574,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 				done_m |= kill_m;
 				if (contrib_m)
 				{
-					FR_STAT(dbg_p1con++;)
+					FR_STATS(ls.p1con++;)
 					const bool contrib = __builtin_amdgcn_inverse_ballot_w64(contrib_m);
 					T = contrib ? test_T : T;
 					last = contrib ? (wcnt + 1) : last;      // 1 + index in THIS wave's list of the pixel's last contributor
@@ -2934,7 +2635,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 	for (int hi = wcnt; hi > 0; hi -= 64)
 	{
 		const int m = min(64, hi);
-		FR_STAT(dbg_chunks++;)
+		FR_STATS(ls.chunks++;)
 		// lane l owns list entry hi-1-l (descending position => bit order == back-to-front order)
 		int kk = -1;                  // unused lanes sort behind every real position (positions are descending in the lane index)
 		float ax = 0.f, ay = 0.f, acx = 0.f, acy = 0.f, acz = 0.f, alo = 0.f, athr = INFINITY, ahx = -1.f, ahy = -1.f;
@@ -3047,13 +2748,6 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 #pragma unroll
 						for (int c = 0; c < 3; c++) b[18 + r * 3 + c] = Cp[r][c];
 				}
-				if constexpr (FULL)
-				{
-#pragma unroll
-					for (int r = 0; r < 6; r++)
-#pragma unroll
-						for (int c = 0; c < 3; c++) b[39 + r * 3 + c] = -0.5f * B[r][c];
-				}
 				if constexpr (HAS_HINV)
 				{
 #pragma unroll
@@ -3114,7 +2808,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 		while (fr_any(mask != 0ull))
 		{
 			bool has = mask != 0ull;
-			FR_STAT(dbg_steps++;)
+			FR_STATS(ls.steps++;)
 			const int j = has ? (__ffsll((long long)mask) - 1) : 0;
 			mask &= mask - 1ull;
 			const float x = fr_bperm_f(ax, j), y = fr_bperm_f(ay, j);
@@ -3127,7 +2821,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 			float power;
 			const float e = fr_scorer_exponent(hcx, ncy, hcz, dx, dy, lo, power);     // bit-identical to pass 1's
 			has = has && !(power > 0.0f) && !(e < FR_E255);
-			FR_STAT(dbg_hits += (int)__popcll(__ballot(has));)
+			FR_STATS(ls.hits += (int)__popcll(__ballot(has));)
 			const float a_un = __builtin_amdgcn_exp2f(e);                              // opacity * G
 			// A lane without a contributor at this step runs the recurrences with alpha = 0, which leaves them unchanged
 			// (T / 1, and the colour recurrence folds a zero-alpha layer away exactly): one select instead of nine.
@@ -3184,20 +2878,6 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 							leaf2[4 + q] = l * l;
 						}
 					}
-					if constexpr (FULL)
-					{
-						// colour: dL_dcolor_c = alpha T dL_dpix_c (not a multiple of w: pre-divided by w2, which multiplies every column below)
-						const float wc = alpha * st.T, iw2 = has ? __builtin_amdgcn_rcpf(w2) : 0.f;
-						leaf2[11] = (wc * g0) * (wc * g0) * iw2; leaf2[12] = (wc * g1) * (wc * g1) * iw2; leaf2[13] = (wc * g2) * (wc * g2) * iw2;
-						leaf2[14] = (u[0] * ddelx_dx) * (u[0] * ddelx_dx); leaf2[15] = (u[1] * ddely_dy) * (u[1] * ddely_dy);
-#pragma unroll
-						for (int q = 0; q < 6; q++)
-						{
-							const float l = r[39 + q * 3 + 0] * u[2] + r[39 + q * 3 + 1] * u[3] + r[39 + q * 3 + 2] * u[4];
-							leaf2[16 + q] = l * l;
-						}
-						leaf2[22] = 0.25f * u[2] * u[2]; leaf2[23] = 0.25f * u[3] * u[3]; leaf2[24] = 0.25f * u[4] * u[4];
-					}
 					if constexpr (HAS_HINV)
 					{
 						float add = FOLD3 ? leaf2[3] : leaf2[3] * r[HO + 3];
@@ -3224,7 +2904,7 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 			__builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
 			// Flush with consecutive lanes on consecutive columns of one entry: an atomic instruction then touches 64 / C rows
 			// of out_H (C contiguous floats each) instead of 64 -- the L2 sees a quarter (C = 4) of the requests.
-			float* dst = FULL ? nullptr : f.out_H + (size_t)v * f.outH_stride;
+			float* dst = f.out_H + (size_t)v * f.outH_stride;
 #pragma unroll
 			for (int i = 0; i < C; i++)
 			{
@@ -3232,29 +2912,13 @@ __global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(C ==
 				const int e = flat / C, c = flat - e * C;
 				const uint32_t id_e = (uint32_t)__builtin_amdgcn_ds_bpermute(e << 2, (int)my_id);
 				const float a = (e < m) ? (float)s_acc[wave][c][e] : 0.f;
-				if constexpr (FULL)
-				{
-					// column -> (gradient tensor, row stride, offset): means3D 0-2, opacity 3, scales 4-6, rotations 7-10, colours 11-13,
-					// means2D 14-15 (z unused), cov3D 16-21, conic 22-24 (entries 0, 1, 3 of the 2x2)
-					const int arr = c < 3 ? 0 : c < 4 ? 1 : c < 7 ? 2 : c < 11 ? 3 : c < 14 ? 4 : c < 16 ? 5 : c < 22 ? 6 : 7;
-					const int first = arr == 0 ? 0 : arr == 1 ? 3 : arr == 2 ? 4 : arr == 3 ? 7 : arr == 4 ? 11 : arr == 5 ? 14 : arr == 6 ? 16 : 22;
-					const int stride = arr == 1 ? 1 : (arr == 3 || arr == 7) ? 4 : arr == 6 ? 6 : 3;
-					const int off = (c == 24) ? 3 : c - first;
-					if (a != 0.f) atomicAdd(f.full_out[arr] + (size_t)id_e * stride + off, a);
-				}
-				else
-				{
-					if (a != 0.f) atomicAdd(dst + (size_t)id_e * C + c, a);
-				}
+				if (a != 0.f) atomicAdd(dst + (size_t)id_e * C + c, a);
 			}
 		}
 	}
 	if constexpr (!HAS_HINV) { (void)score; return; }
 	float ws = wave_sum(score);
-#ifdef FR_LOOPSTATS
-	if (f.debug_mode >= 2)
-		ws = f.debug_mode == 2 ? (float)dbg_p1 : f.debug_mode == 3 ? (float)dbg_chunks : f.debug_mode == 4 ? (float)dbg_steps : f.debug_mode == 5 ? (float)dbg_hits : f.debug_mode == 7 ? (float)dbg_p1any : f.debug_mode == 8 ? (float)dbg_p1con : (float)wcnt;
-#endif
+	FR_STATS_RESULT_V2(ws, wcnt)
 	if (lane == 0) s_red[wave] = ws;
 	__syncthreads();
 	if (tid == 0) f.tile_scores[vt] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
@@ -3542,20 +3206,17 @@ __device__ __forceinline__ bool fr_walk_update(const FrWalkGeom& g, bool live, f
 //  walk     every pixel-lane walks its own set bits front to back: five ds_read_b128 of the candidate's record, the pair
 //           test, the transmittance / colour prefix recurrences and the three sums.  A finished pixel clears its masks;
 //           a wave whose 64 pixels are finished leaves.
-// BW x BH = the 64 pixels of a wave inside the 16 x 16 tile: 16 x 4 strips (used), or 8 x 8 blocks (5 % slower on MI355X).
-// MK: the keys carry, in their low four bits, the strips of the tile their splat's footprint reaches (fixed key segments; the
-// front end has made the stream step's test once per (splat, tile)): a wave keeps the keys with ITS bit -- no recA gather per key.
-// Waves per SIMD: 5 with the gathering stream step (6 and 7 measured no faster in round 2); the MK form needs 69 registers and
-// runs 7 (0.745-0.755 ms against 0.785 at 5: the walk is a chain of dependent LDS reads and arithmetic, more waves hide more of it).
-template <int BW, int BH, bool MK = false>
+// The 64 pixels of a wave inside the 16 x 16 tile are a 16 x 4 strip (8 x 8 blocks measured 5 % slower on MI355X).
+// This is the form for packed lists and dense records: the keys carry the Gaussian index, and the stream step gathers recA per key.
+// (Fixed key segments go to k_fisher_tile_v4, whose keys carry the strips their splat reaches.)
+// Waves per SIMD: 5 (6 and 7 measured no faster in round 2).
 #ifndef FR_V3_WAVES
 #define FR_V3_WAVES 5
 #endif
-__global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(4, MK ? 7 : FR_V3_WAVES)))
+__global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(4, FR_V3_WAVES)))
 void k_fisher_tile_v3(FrParams p, FrFisherArgs f, const float4* __restrict__ recq)
 {
-	static_assert(!MK || (BW == 16 && BH == 4), "the keys' strip bits are those of 16 x 4 strips");
-	static_assert(BW * BH == 64 && 16 % BW == 0, "a wave owns 64 pixels of the tile");
+	constexpr int BW = 16, BH = 4;                 // the wave's strip
 	__shared__ uint32_t s_q[4][FR_QCAP];
 	__shared__ float4 s_ent[4][64][FR_ENT3_F4];
 	__shared__ float s_red[4];
@@ -3565,16 +3226,14 @@ void k_fisher_tile_v3(FrParams p, FrFisherArgs f, const float4* __restrict__ rec
 	uint32_t tile; int v;
 	fr_tile_of_block(p, tile, v);
 	const uint32_t tx = tile % p.gx, ty = tile / p.gx;
-	constexpr int WPR = 16 / BW;                   // waves per tile row
-	const uint32_t bx0 = tx * FR_BLOCK_X + (uint32_t)(wave % WPR) * BW, by0 = ty * FR_BLOCK_Y + (uint32_t)(wave / WPR) * BH;
+	const uint32_t bx0 = tx * FR_BLOCK_X, by0 = ty * FR_BLOCK_Y + (uint32_t)wave * BH;
 	const uint32_t pxx = bx0 + (uint32_t)(lane % BW), pxy = by0 + (uint32_t)(lane / BW);
 	const bool inside = pxx < (uint32_t)p.W && pxy < (uint32_t)p.H;
 	const float pfx = (float)pxx, pfy = (float)pxy;
 	const size_t vt = (size_t)v * p.T + tile;
-	const size_t vP = (size_t)v * p.P;
 	const uint32_t n = p.tile_cnt[vt];
 	const uint64_t* gk = p.keys + p.tile_off[vt];
-	(void)vP; (void)recq;
+	(void)recq;
 	const float4* rec = f.recA + (size_t)v * f.ab_view;
 	const float4* rq = f.recQ + (size_t)v * f.q_view;
 	const size_t rsA = (size_t)f.ab_stride, rsQ = (size_t)f.q_stride;
@@ -3589,45 +3248,33 @@ void k_fisher_tile_v3(FrParams p, FrFisherArgs f, const float4* __restrict__ rec
 	float T = 1.0f, Cg = 0.f, Xt = 0.f, sA = 0.f, sB = 0.f, sD = 0.f;
 	bool done = !inside;
 	uint32_t qh = 0, qn = 0;                       // ring head / fill, wave-uniform
-#ifdef FR_LOOPSTATS
-	int dbg_cand = 0, dbg_chunks = 0, dbg_steps = 0, dbg_hits = 0, dbg_wsteps = 0, dbg_cs = 0, dbg_empty = 0;
-	long long dbg_t0 = 0, dbg_ts = 0, dbg_tc = 0, dbg_tw = 0;     // s_memtime sums: stream / chunk set-up / walk
-#endif
+	FR_STATS_DECLARE
 
 	// software pipeline of the key stream: id1 / r1 = indices and recA of the chunk at `base`, id2 = indices of the next one
 	uint32_t id1 = 0, id2 = 0;
 	float4 r1 = make_float4(0.f, 0.f, 0.f, 0.f);
-	if ((uint32_t)lane < n) { id1 = (uint32_t)FR_LDK(gk + lane); if constexpr (!MK) r1 = rec[rsA * id1]; }
+	if ((uint32_t)lane < n) { id1 = (uint32_t)FR_LDK(gk + lane); r1 = rec[rsA * id1]; }
 	if (64u + lane < n) id2 = (uint32_t)FR_LDK(gk + 64 + lane);
 	uint32_t base = 0;
 	// ---- stream: fill the queue up to one chunk
 	auto stream_fill = [&]() {
-#ifdef FR_LOOPSTATS
-		dbg_t0 = (long long)__builtin_amdgcn_s_memtime();
-#endif
+		FR_STATS_START
 		while (qn < 64u && base < n)
 		{
 			const uint32_t idc = id1; const float4 rc = r1;
 			id1 = id2;
-			if constexpr (!MK) { if (base + 64 + lane < n) r1 = rec[rsA * id2]; }
+			if (base + 64 + lane < n) r1 = rec[rsA * id2];
 			if (base + 128 + lane < n) id2 = (uint32_t)FR_LDK(gk + base + 128 + lane);
-			bool ov = base + lane < n;
-			if constexpr (MK) ov = ov && ((idc >> wave) & 1u);
-			else
-			{
-				const uint32_t eb = __float_as_uint(rc.z);
-				const float hx = __half2float(__ushort_as_half((unsigned short)(eb & 0xffffu)));
-				const float hy = __half2float(__ushort_as_half((unsigned short)(eb >> 16)));
-				ov = ov && hx >= 0.f && (rc.y + hy >= strip_lo) && (rc.y - hy <= strip_hi) && (rc.x + hx >= tile_x0) && (rc.x - hx <= tile_x1);
-			}
+			const uint32_t eb = __float_as_uint(rc.z);
+			const float hx = __half2float(__ushort_as_half((unsigned short)(eb & 0xffffu)));
+			const float hy = __half2float(__ushort_as_half((unsigned short)(eb >> 16)));
+			const bool ov = base + lane < n && hx >= 0.f && (rc.y + hy >= strip_lo) && (rc.y - hy <= strip_hi) && (rc.x + hx >= tile_x0) && (rc.x - hx <= tile_x1);
 			const unsigned long long om = __builtin_amdgcn_ballot_w64(ov);
-			if (ov) wq[(qh + qn + (uint32_t)__popcll(om & ((1ull << lane) - 1ull))) & (FR_QCAP - 1)] = MK ? (idc >> 4) : idc;
+			if (ov) wq[(qh + qn + (uint32_t)__popcll(om & ((1ull << lane) - 1ull))) & (FR_QCAP - 1)] = idc;
 			qn += (uint32_t)__popcll(om);
 			base += 64;
 		}
-#ifdef FR_LOOPSTATS
-		{ const long long t = (long long)__builtin_amdgcn_s_memtime(); dbg_ts += t - dbg_t0; dbg_t0 = t; }
-#endif
+		FR_STATS_STAMP(ts)
 	};
 	// ---- the next chunk's records, gathered into registers one chunk ahead (the gathers then fly during the walk of the
 	// current chunk instead of in front of it); up to 64 candidates, one per lane
@@ -3643,8 +3290,7 @@ void k_fisher_tile_v3(FrParams p, FrFisherArgs f, const float4* __restrict__ rec
 			const uint32_t id = wq[(qh + lane) & (FR_QCAP - 1)];
 			pa = rec[rsA * id]; pb = rec[rsA * id + 1];
 			pq0 = rq[rsQ * id]; pq1 = rq[rsQ * id + 1]; pq2 = rq[rsQ * id + 2];
-			if constexpr (MK) pk3 = pa.z;              // (the 80-byte record: k3 already sits where the walk wants it)
-			else pk3 = ((const float*)(rq + rsQ * id + 3))[0];
+			pk3 = ((const float*)(rq + rsQ * id + 3))[0];
 		}
 		qh = (qh + pm) & (FR_QCAP - 1); qn -= pm;
 	};
@@ -3655,10 +3301,8 @@ void k_fisher_tile_v3(FrParams p, FrFisherArgs f, const float4* __restrict__ rec
 	{
 		// ---- chunk: park the gathered records in LDS, rasterise the footprints
 		const uint32_t m = pm;
-#ifdef FR_LOOPSTATS
-		dbg_t0 = (long long)__builtin_amdgcn_s_memtime();
-		dbg_chunks++; dbg_cand += (int)m;
-#endif
+		FR_STATS_START
+		FR_STATS(ls.chunks++; ls.cand += (int)m;)
 		unsigned long long emask = 0ull;
 		if ((uint32_t)lane < m)
 		{
@@ -3667,16 +3311,14 @@ void k_fisher_tile_v3(FrParams p, FrFisherArgs f, const float4* __restrict__ rec
 			ent[lane][1] = b4; ent[lane][2] = pq0; ent[lane][3] = pq1; ent[lane][4] = pq2;
 			const float ax = a.x, ay = a.y;
 			const uint32_t eb = __float_as_uint(a.z);
-			// (MK: no extents in the record -- a listed splat's footprint rows come from the conic alone; a conic the quadratic
-			// cannot take covers the strip)
-			const float ahx = MK ? 1e30f : __half2float(__ushort_as_half((unsigned short)(eb & 0xffffu)));
-			const float ahy = MK ? 1e30f : __half2float(__ushort_as_half((unsigned short)(eb >> 16)));
+			const float ahx = __half2float(__ushort_as_half((unsigned short)(eb & 0xffffu)));
+			const float ahy = __half2float(__ushort_as_half((unsigned short)(eb >> 16)));
 			const float acx = -2.0f * b4.x, acy = -b4.y, acz = -2.0f * b4.z;
 			// conservative lower bound on `power` below which alpha < 1/255: -ln(255 opacity) - 0.01 (fr_power_threshold)
 			const float athr = -(5.541263545158426f + 0.6931471805599453f * a.w) - 0.01f;
 			// Row by row: power(dx, dy) >= thr  <=>  cx dx^2 + 2 cy dy dx + (cz dy^2 + 2 thr) <= 0, an interval in dx
 			// (d = mean - pixel).  Widened by 1 % + 0.01 px, so it stays a superset of the exact test done in the walk.
-			const bool quad_ok = acx > 0.f && athr <= 0.f && (MK || ahx < 1e30f);
+			const bool quad_ok = acx > 0.f && athr <= 0.f && ahx < 1e30f;
 			const float racx = __builtin_amdgcn_rcpf(acx);
 #pragma unroll
 			for (unsigned r = 0; r < (unsigned)BH; r++)
@@ -3703,25 +3345,17 @@ void k_fisher_tile_v3(FrParams p, FrFisherArgs f, const float4* __restrict__ rec
 				}
 			}
 		}
-#ifdef FR_LOOPSTATS
-		{ const long long t = (long long)__builtin_amdgcn_s_memtime(); dbg_tc += t - dbg_t0; }
-#endif
-#ifdef FR_LOOPSTATS
-		dbg_empty += (int)__popcll(__builtin_amdgcn_ballot_w64((uint32_t)lane < m && emask == 0ull));      // parked candidates whose footprint misses every pixel of the strip
-#endif
+		FR_STATS_STAMP(tc)
+		FR_STATS(ls.empty += (int)__popcll(__builtin_amdgcn_ballot_w64((uint32_t)lane < m && emask == 0ull));)      // parked candidates whose footprint misses every pixel of the strip
 		// ---- refill the queue and start the next chunk's gathers before the transpose and the walk of this one
 		stream_fill();
 		gather_next();
-#ifdef FR_LOOPSTATS
-		dbg_t0 = (long long)__builtin_amdgcn_s_memtime();
-#endif
+		FR_STATS_START
 		unsigned long long mask = fr_wave_transpose64(emask, lane);
 		if (done) mask = 0ull;
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 		__builtin_amdgcn_wave_barrier();
-#ifdef FR_LOOPSTATS
-		{ const long long t = (long long)__builtin_amdgcn_s_memtime(); dbg_tc += t - dbg_t0; dbg_t0 = t; }
-#endif
+		FR_STATS_STAMP(tc)
 		// ---- walk: every pixel-lane walks its own candidates front to back (the set bits of `mask`).  The candidate's 80-byte
 		// record comes back as five ds_read_b128 (hipcc splits plain float4 LDS loads into dword pairs here).
 		// The number of steps (set by the busiest lane of the chunk) times a per-step cost is what this loop costs; DESIGN.md
@@ -3738,62 +3372,45 @@ void k_fisher_tile_v3(FrParams p, FrFisherArgs f, const float4* __restrict__ rec
 				             "s_waitcnt lgkmcnt(0)"
 				             : "=&v"(r.a), "=&v"(r.b4), "=&v"(r.q0), "=&v"(r.q1), "=&v"(r.q2) : "v"(addr) : "memory");
 			}
-#ifdef FR_LOOPSTATS
-			dbg_steps++; dbg_cs++;
-#endif
+			FR_STATS(ls.steps++; ls.cs++;)
 			const FrWalkGeom g = fr_walk_geom(r, pfx, pfy);
 			const bool kill = fr_walk_update(g, g.ok, T, Cg, Xt, sA, sB, sD);
-#ifdef FR_LOOPSTATS
-			dbg_hits += (g.ok && !kill) ? 1 : 0;
-#endif
+			FR_STATS(ls.hits += (g.ok && !kill) ? 1 : 0;)
 			if (kill) { mask = 0ull; done = true; }
 		}
 		all_done = __builtin_amdgcn_ballot_w64(!done) == 0ull;
-#ifdef FR_LOOPSTATS
-		{ const long long t = (long long)__builtin_amdgcn_s_memtime(); dbg_tw += t - dbg_t0; dbg_t0 = t; }
-		dbg_wsteps += wave_max_i(dbg_cs); dbg_cs = 0;
-#endif
+		FR_STATS_STAMP(tw)
+		FR_STATS(ls.end_chunk();)
 	}
 	// X = Cg_final + T_final * sum(bg); pixel = A' - 2 (X - Xt) B' + (X - Xt)^2 D, times dL^2
 	const float X = Cg + T * (p.bg[0] + p.bg[1] + p.bg[2]);
 	const float dlt = X - Xt;
 	float score = inside ? (sA + dlt * (dlt * sD - 2.0f * sB)) : 0.f;
 	float ws = wave_sum(score);
-#ifdef FR_LOOPSTATS
-	if (f.debug_mode >= 2)
-	{
-		// 2: candidates, 3: chunks, 4: wave-level walk iterations, 5: contributing pairs, 6: lane-level walk steps, 7: steps of the busiest lane
-		// 10 / 11 / 12: the wave's s_memtime ticks (/ 64) in the key stream / the chunk set-up / the walk
-		if (f.debug_mode == 15) ws = (float)dbg_empty;                        // candidates parked with an empty footprint mask
-		else if (f.debug_mode == 13) ws = (float)(base < n ? base : n);            // keys this wave streamed before its 64 pixels were finished
-		else if (f.debug_mode == 14) ws = (float)n;                           // ... of the tile's n (both summed over the four waves)
-		else if (f.debug_mode >= 10) ws = (float)((f.debug_mode == 10 ? dbg_ts : f.debug_mode == 11 ? dbg_tc : dbg_tw) >> 6);
-		else
-		ws = f.debug_mode == 2 ? (float)dbg_cand : f.debug_mode == 3 ? (float)dbg_chunks : f.debug_mode == 4 ? (float)dbg_wsteps
-		   : f.debug_mode == 5 ? wave_sum((float)dbg_hits) : f.debug_mode == 7 ? (float)wave_max_i(dbg_steps) : wave_sum((float)dbg_steps);
-	}
-	else
-#endif
 	ws *= f.dL * f.dL;
+	FR_STATS_RESULT(ws, base, n)
 	if (lane == 0) s_red[wave] = ws;
 	__syncthreads();
 	if (tid == 0) f.tile_scores[vt] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// k_fisher_tile_v4: k_fisher_tile_v3<16, 4, MK> with ROLLING HALVES.  In k_fisher_tile_v3 the wave re-converges after every chunk
+// k_fisher_tile_v4: k_fisher_tile_v3 with ROLLING HALVES, on keys that carry their strips.  In k_fisher_tile_v3 the wave re-converges after every chunk
 // of 64 candidates, so a chunk costs as many walk iterations as its busiest pixel-lane has candidates: 44 % of the lane slots do
 // work (profiles/r03_m_loopstats.txt).  Here the 64 record slots / 64 mask bits are two halves of 32: the low word of a pixel's
 // mask is the OLDER half, the high word the younger one; a lane that has walked its bits of the older half goes straight on to the
 // younger half's (ffs over the 64 bits gives exactly that order), and the wave only re-converges when NO lane has a bit of the older
 // half left -- then the halves swap roles (mask >>= 32, the slot base flips: slot = bit ^ base) and the freed 32 slots take the next
 // 32 candidates.  A lane can thus run up to a whole half ahead of the slowest one at no cost per iteration but one v_xor (round 3's
-// window kernel, k_fisher_tile_v3w, paid 8 vector instructions and two scalar branches per iteration for the same freedom).
+// two-chunk window kernel paid 8 vector instructions and two scalar branches per iteration for the same freedom: DESIGN.md).
 // The set-up of a half uses all 64 lanes: lane = 32 h + c parks its part of candidate c's record (h = 0: three float4, h = 1: two),
 // rasterises rows 2h, 2h+1 of the candidate's footprint into a 32-bit word, and a 32 x 32 bit transpose inside each half-wave (five
 // DPP / permlane16 rounds on 32-bit words; the 64 x 64 one takes six on 64-bit words) hands every pixel-lane its 32 candidate bits.
 // Pairs, their order per pixel and their arithmetic are k_fisher_tile_v3's: the scores are bit-identical.
-// Fixed key segments only (the keys carry the strip bits; 80-byte records at stride 5).
+// Fixed key segments only: the keys carry, in their low four bits, the strips of the tile their splat's footprint reaches (the
+// front end has made the stream step's test once per (splat, tile)), so a wave keeps the keys with ITS bit -- no recA gather per
+// key; 80-byte records at stride 5.  69 registers, 7 waves per SIMD (0.745-0.755 ms against 0.785 at 5: the walk is a chain of
+// dependent LDS reads and arithmetic, more waves hide more of it).
 template <int SFT>
 __device__ __forceinline__ uint32_t fr_transpose_round32(uint32_t x, int lane)
 {
@@ -3888,14 +3505,8 @@ void k_fisher_tile_v4(FrParams p, FrFisherArgs f)
 	float T = 1.0f, Cg = 0.f, Xt = 0.f, sA = 0.f, sB = 0.f, sD = 0.f;
 	bool done = !inside;
 	uint32_t qh = 0, qn = 0;
-#ifdef FR_LOOPSTATS
-	int dbg_cand = 0, dbg_chunks = 0, dbg_steps = 0, dbg_hits = 0, dbg_wsteps = 0, dbg_cs = 0;
-	long long dbg_t0 = 0, dbg_ts = 0, dbg_tc = 0, dbg_tw = 0;
-#define FR_V4_STAMP(acc) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); acc += t_ - dbg_t0; dbg_t0 = t_; }
-#else
-#define FR_V4_STAMP(acc)
-#endif
-	// ---- key stream (k_fisher_tile_v3's, MK form): keep the keys that carry this wave's strip bit, append their slots to the ring
+	FR_STATS_DECLARE
+	// ---- key stream: keep the keys that carry this wave's strip bit, append their slots to the ring
 	uint32_t id1 = 0, id2 = 0;
 	if ((uint32_t)lane < n) id1 = (uint32_t)FR_LDK(gk + lane);
 	if (64u + lane < n) id2 = (uint32_t)FR_LDK(gk + 64 + lane);
@@ -3929,12 +3540,10 @@ void k_fisher_tile_v4(FrParams p, FrFisherArgs f)
 		}
 		qh = (qh + pm) & (FR_QCAP - 1); qn -= pm;
 	};
-#ifdef FR_LOOPSTATS
-	dbg_t0 = (long long)__builtin_amdgcn_s_memtime();
-#endif
+	FR_STATS_START
 	stream_fill();
 	gather_next();
-	FR_V4_STAMP(dbg_ts)
+	FR_STATS_STAMP(ts)
 	unsigned long long mask = 0ull;                  // low word: the older half's candidates of this pixel, high word: the younger half's
 	uint32_t base0 = 0;                              // slot of bit j = j ^ base0 (0 or 32, wave-uniform)
 	bool all_done = __builtin_amdgcn_ballot_w64(!done) == 0ull;
@@ -3950,20 +3559,18 @@ void k_fisher_tile_v4(FrParams p, FrFisherArgs f)
 			else { e[3] = g2; e[4] = g3; }
 			em = fr_footprint_rows2(ga, gb, rows_y0, tile_x0);
 		}
-#ifdef FR_LOOPSTATS
-		dbg_chunks++; dbg_cand += (int)m;
-#endif
-		FR_V4_STAMP(dbg_tc)
+		FR_STATS(ls.chunks++; ls.cand += (int)m;)
+		FR_STATS_STAMP(tc)
 		stream_fill();
 		gather_next();
-		FR_V4_STAMP(dbg_ts)
+		FR_STATS_STAMP(ts)
 		uint32_t nm = fr_half_transpose32(em, lane);
 		if (done) nm = 0u;
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 		__builtin_amdgcn_wave_barrier();
 		mask |= (unsigned long long)nm << 32;
 		if (m == 0u && __builtin_amdgcn_ballot_w64(mask != 0ull) == 0ull) break;     // nothing parked, nothing left to walk
-		FR_V4_STAMP(dbg_tc)
+		FR_STATS_STAMP(tc)
 		// ---- walk until no lane holds a bit of the older half
 		// (a divergent loop: a lane leaves when it has no bit left in either half -- it cannot get one before the next set-up -- and the
 		// lanes still inside leave together once none of them holds a bit of the older half: the vote only needs the active lanes)
@@ -3981,20 +3588,14 @@ void k_fisher_tile_v4(FrParams p, FrFisherArgs f)
 				             "s_waitcnt lgkmcnt(0)"
 				             : "=&v"(r.a), "=&v"(r.b4), "=&v"(r.q0), "=&v"(r.q1), "=&v"(r.q2) : "v"(addr) : "memory");
 			}
-#ifdef FR_LOOPSTATS
-			dbg_steps++; dbg_cs++;
-#endif
+			FR_STATS(ls.steps++; ls.cs++;)
 			const FrWalkGeom g = fr_walk_geom(r, pfx, pfy);
 			const bool kill = fr_walk_update(g, g.ok, T, Cg, Xt, sA, sB, sD);
-#ifdef FR_LOOPSTATS
-			dbg_hits += (g.ok && !kill) ? 1 : 0;
-#endif
+			FR_STATS(ls.hits += (g.ok && !kill) ? 1 : 0;)
 			if (kill) { mask = 0ull; done = true; }
 		}
-#ifdef FR_LOOPSTATS
-		dbg_wsteps += wave_max_i(dbg_cs); dbg_cs = 0;
-#endif
-		FR_V4_STAMP(dbg_tw)
+		FR_STATS(ls.end_chunk();)
+		FR_STATS_STAMP(tw)
 		// ---- the older half is finished by every lane: its slots are free, the younger half becomes the older one
 		mask >>= 32;
 		base0 ^= 32u;
@@ -4004,23 +3605,12 @@ void k_fisher_tile_v4(FrParams p, FrFisherArgs f)
 	const float dlt = X - Xt;
 	float score = inside ? (sA + dlt * (dlt * sD - 2.0f * sB)) : 0.f;
 	float ws = wave_sum(score);
-#ifdef FR_LOOPSTATS
-	if (f.debug_mode >= 2)
-	{
-		if (f.debug_mode == 13) ws = (float)(base < n ? base : n);
-		else if (f.debug_mode == 14) ws = (float)n;
-		else if (f.debug_mode >= 10) ws = (float)((f.debug_mode == 10 ? dbg_ts : f.debug_mode == 11 ? dbg_tc : dbg_tw) >> 6);
-		else ws = f.debug_mode == 2 ? (float)dbg_cand : f.debug_mode == 3 ? (float)dbg_chunks : f.debug_mode == 4 ? (float)dbg_wsteps
-		        : f.debug_mode == 5 ? wave_sum((float)dbg_hits) : f.debug_mode == 7 ? (float)wave_max_i(dbg_steps) : wave_sum((float)dbg_steps);
-	}
-	else
-#endif
 	ws *= f.dL * f.dL;
+	FR_STATS_RESULT(ws, base, n)
 	if (lane == 0) s_red[wave] = ws;
 	__syncthreads();
 	if (tid == 0) f.tile_scores[vt] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
-#undef FR_V4_STAMP
 
 // ---------------------------------------------------------------------------------------------------------
 // out_H mode of the third generation (no H_inv, constant upstream gradient, 4 columns: compute_Hessian / H_train of the
@@ -4143,213 +3733,16 @@ __device__ __forceinline__ unsigned long long fr_footprint_mask(const float4& a,
 	return emask;
 }
 
-#ifdef FR_AB
-// ---------------------------------------------------------------------------------------------------------
-// k_fisher_tile_v3 with a ROLLING WINDOW of two chunks (experiment, FR_DEBUG_MODE=24; NOT the default).  In k_fisher_tile_v3 the
-// wave re-converges after every chunk of 64 candidates, so every chunk costs as many walk iterations as its busiest pixel-lane has
-// candidates: 7.48 M wave-level iterations per 64-view step where an unsynchronised walk would need 4.5 M (45 % of the lane slots
-// do work).  Here two chunks of 48 candidates are resident in LDS (96 record slots = 32 KiB per workgroup: still five workgroups
-// per CU -- a 128-slot window costs 17 % for the occupancy it loses, measured by padding k_fisher_tile_v3's LDS); a lane that has
-// walked its bits of the older chunk goes straight on to the younger one, and the wave only waits until EVERY lane has left the
-// older chunk, whose slots then take the next 48 candidates.  Measured (profiles/r03_f_window_walk.txt): 5.69 M iterations
-// (-24 %, as a simulation on the oracle's contributor lists predicted), scores bit-identical -- and 1.07 ms against 0.99 ms: the
-// move to the younger chunk costs 8 vector instructions on most iterations (some lane leaves the older chunk nearly every
-// iteration), the loop has three scalar branches where the chunk-synchronous one has a single exec-masked back edge, and a
-// third more chunks are set up (48 instead of 64 candidates each).  Kept for A/B runs; what it shows is that the walk's
-// idle lanes cannot be bought back at this price per iteration.
-#ifndef FR_WCS
-#define FR_WCS 48                     // candidates per chunk of the windowed walk
-#endif
-__global__ __launch_bounds__(FR_THREADS) __attribute__((amdgpu_waves_per_eu(4, FR_V3_WAVES)))
-void k_fisher_tile_v3w(FrParams p, FrFisherArgs f)
-{
-	__shared__ uint32_t s_q[4][FR_QCAP];
-	__shared__ float4 s_ent[4][2 * FR_WCS][FR_ENT3_F4];
-	if (p.status[1]) return;
-	const int tid = threadIdx.x, lane = tid & 63;
-	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-	uint32_t tile; int v;
-	fr_tile_of_block(p, tile, v);
-	const uint32_t tx = tile % p.gx, ty = tile / p.gx;
-	const uint32_t bx0 = tx * FR_BLOCK_X, by0 = ty * FR_BLOCK_Y + (uint32_t)wave * 4u;
-	const uint32_t pxx = bx0 + (uint32_t)(lane & 15), pxy = by0 + (uint32_t)(lane >> 4);
-	const bool inside = pxx < (uint32_t)p.W && pxy < (uint32_t)p.H;
-	const float pfx = (float)pxx, pfy = (float)pxy;
-	const size_t vt = (size_t)v * p.T + tile;
-	const uint32_t n = p.tile_cnt[vt];
-	const uint64_t* gk = p.keys + p.tile_off[vt];
-	const float4* rec = f.recA + (size_t)v * f.ab_view;
-	const float4* rq = f.recQ + (size_t)v * f.q_view;
-	const size_t rsA = (size_t)f.ab_stride, rsQ = (size_t)f.q_stride;
-	uint32_t* wq = s_q[wave];
-	float4 (*ent)[FR_ENT3_F4] = s_ent[wave];
-	constexpr uint32_t HALF = FR_WCS * FR_ENT3_F4 * 16;          // bytes of one chunk's records
-	const uint32_t ent_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)&s_ent[wave][0][0];   // LDS byte address
-	uint32_t ent_lds_v;
-	asm volatile("v_mov_b32 %0, %1" : "=v"(ent_lds_v) : "s"(ent_lds));
-
-	const float strip_lo = (float)by0, strip_hi = strip_lo + 3.0f;
-	const float tile_x0 = (float)bx0, tile_x1 = tile_x0 + 15.0f;
-	float T = 1.0f, Cg = 0.f, Xt = 0.f, sA = 0.f, sB = 0.f, sD = 0.f;
-	bool done = !inside;
-	uint32_t qh = 0, qn = 0;
-#ifdef FR_LOOPSTATS
-	int dbg_cand = 0, dbg_chunks = 0, dbg_steps = 0, dbg_hits = 0, dbg_wsteps = 0;
-#endif
-
-	// key stream, as in k_fisher_tile_v3
-	uint32_t id1 = 0, id2 = 0;
-	float4 r1 = make_float4(0.f, 0.f, 0.f, 0.f);
-	if ((uint32_t)lane < n) { id1 = (uint32_t)gk[lane]; r1 = rec[rsA * id1]; }
-	if (64u + lane < n) id2 = (uint32_t)gk[64 + lane];
-	uint32_t base = 0;
-	auto stream_fill = [&]() {
-		while (qn < (uint32_t)FR_WCS && base < n)
-		{
-			const uint32_t idc = id1; const float4 rc = r1;
-			id1 = id2;
-			if (base + 64 + lane < n) r1 = rec[rsA * id2];
-			if (base + 128 + lane < n) id2 = (uint32_t)gk[base + 128 + lane];
-			const uint32_t eb = __float_as_uint(rc.z);
-			const float hx = __half2float(__ushort_as_half((unsigned short)(eb & 0xffffu)));
-			const float hy = __half2float(__ushort_as_half((unsigned short)(eb >> 16)));
-			const bool ov = (base + lane < n) && hx >= 0.f && (rc.y + hy >= strip_lo) && (rc.y - hy <= strip_hi)
-			                && (rc.x + hx >= tile_x0) && (rc.x - hx <= tile_x1);
-			const unsigned long long om = __builtin_amdgcn_ballot_w64(ov);
-			if (ov) wq[(qh + qn + (uint32_t)__popcll(om & ((1ull << lane) - 1ull))) & (FR_QCAP - 1)] = idc;
-			qn += (uint32_t)__popcll(om);
-			base += 64;
-		}
-	};
-	// the next chunk's records, gathered into registers one chunk ahead of their parking
-	float4 pa = make_float4(0.f, 0.f, 0.f, 0.f), pb = pa, pq0 = pa, pq1 = pa, pq2 = pa;
-	float pk3 = 0.f;
-	uint32_t pm = 0;
-	auto gather_next = [&]() {
-		pm = qn < (uint32_t)FR_WCS ? qn : (uint32_t)FR_WCS;
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		if ((uint32_t)lane < pm)
-		{
-			const uint32_t id = wq[(qh + lane) & (FR_QCAP - 1)];
-			pa = rec[rsA * id]; pb = rec[rsA * id + 1];
-			pq0 = rq[rsQ * id]; pq1 = rq[rsQ * id + 1]; pq2 = rq[rsQ * id + 2];
-			pk3 = ((const float*)(rq + rsQ * id + 3))[0];
-		}
-		qh = (qh + pm) & (FR_QCAP - 1); qn -= pm;
-	};
-	stream_fill();
-	gather_next();
-
-	unsigned long long cur = 0ull, nxt = 0ull;     // the lane's candidates in the chunk it is walking / in the chunk after it
-	uint32_t cbase = ent_lds_v;                      // LDS byte address of the chunk `cur` refers to
-	uint32_t oldest = 0, resident = 0;               // wave-uniform: half holding the older resident chunk, resident chunks (0..2)
-	bool all_done = __builtin_amdgcn_ballot_w64(!done) == 0ull;
-	while (!all_done)
-	{
-		// ---- park the gathered chunk(s) into the free half / halves
-		while (resident < 2u && pm != 0u)
-		{
-			const uint32_t h = (oldest + resident) & 1u;
-			const uint32_t m = pm;
-#ifdef FR_LOOPSTATS
-			dbg_chunks++; dbg_cand += (int)m;
-#endif
-			unsigned long long emask = 0ull;
-			if ((uint32_t)lane < m)
-			{
-				const float4 a = pa, b4 = pb;
-				float4* e = ent[h * FR_WCS + (uint32_t)lane];
-				e[0] = make_float4(a.x, a.y, pk3, a.w);               // k3 in the place of the footprint extents (only needed here)
-				e[1] = b4; e[2] = pq0; e[3] = pq1; e[4] = pq2;
-				emask = fr_footprint_mask<16, 4>(a, b4, strip_lo, tile_x0);
-			}
-			stream_fill();
-			gather_next();
-			unsigned long long mask = fr_wave_transpose64(emask, lane);
-			if (done) mask = 0ull;
-			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			if (resident == 0u) { cur = mask; cbase = ent_lds_v + h * HALF; }     // nothing was resident: every lane starts on this chunk
-			else nxt = mask;
-			resident++;
-		}
-		if (resident == 0u) break;
-		const uint32_t ybase = ent_lds + (oldest ^ 1u) * HALF;                   // the younger chunk's
-		// ---- walk until every lane has left the older chunk.  The votes are kept as 64-bit scalar masks (v_cmp writes them, s_and /
-		// s_andn2 combine them): `older` = the lanes still on the older chunk (all of them at the start of a round).
-		unsigned long long older = ~0ull;
-		while (true)
-		{
-			const unsigned long long c0 = __builtin_amdgcn_uicmpl(cur, 0ull, 32 /* eq */);
-			const unsigned long long nn = __builtin_amdgcn_uicmpl(nxt, 0ull, 33 /* ne */);
-			// a lane that has finished the older chunk moves on to the younger one (nxt != 0 only while the lane is on the older chunk)
-			const unsigned long long swm = c0 & nn;
-			if (swm != 0ull)
-			{
-				if (__builtin_amdgcn_inverse_ballot_w64(swm)) { cur = nxt; nxt = 0ull; cbase = ybase; }
-				older &= ~swm;
-			}
-			const unsigned long long livem = ~c0 | swm;
-			if ((livem & older) == 0ull) break;
-#ifdef FR_LOOPSTATS
-			dbg_wsteps++;
-#endif
-			if (__builtin_amdgcn_inverse_ballot_w64(livem))
-			{
-				const int j = __builtin_ctzll(cur);                  // (cur != 0 on every live lane)
-				cur &= cur - 1ull;
-				FrWalkRec3 r;
-				{
-					const uint32_t addr = cbase + (uint32_t)j * (FR_ENT3_F4 * 16);
-					asm volatile("ds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:16\n\tds_read_b128 %2, %5 offset:32\n\t"
-					             "ds_read_b128 %3, %5 offset:48\n\tds_read_b128 %4, %5 offset:64\n\t"
-					             "s_waitcnt lgkmcnt(0)"
-					             : "=&v"(r.a), "=&v"(r.b4), "=&v"(r.q0), "=&v"(r.q1), "=&v"(r.q2) : "v"(addr) : "memory");
-				}
-#ifdef FR_LOOPSTATS
-				dbg_steps++;
-#endif
-				const FrWalkGeom g = fr_walk_geom(r, pfx, pfy);
-				const bool kill = fr_walk_update(g, g.ok, T, Cg, Xt, sA, sB, sD);
-#ifdef FR_LOOPSTATS
-				dbg_hits += (g.ok && !kill) ? 1 : 0;
-#endif
-				if (kill) { cur = 0ull; nxt = 0ull; done = true; }
-			}
-		}
-		// ---- the older chunk is finished by every lane: its half is free, the younger chunk becomes the older one
-		cbase = ybase;                                   // (lanes that had not moved on hold cur == 0 and nxt == 0 here)
-		oldest ^= 1u; resident--;
-		all_done = __builtin_amdgcn_ballot_w64(!done) == 0ull;
-	}
-	const float X = Cg + T * (p.bg[0] + p.bg[1] + p.bg[2]);
-	const float dlt = X - Xt;
-	float score = inside ? (sA + dlt * (dlt * sD - 2.0f * sB)) : 0.f;
-	float ws = wave_sum(score);
-#ifdef FR_LOOPSTATS
-	if (f.debug_mode >= 2)
-		ws = f.debug_mode == 2 ? (float)dbg_cand : f.debug_mode == 3 ? (float)dbg_chunks : f.debug_mode == 4 ? (float)dbg_wsteps
-		   : f.debug_mode == 5 ? wave_sum((float)dbg_hits) : f.debug_mode == 7 ? (float)wave_max_i(dbg_steps) : wave_sum((float)dbg_steps);
-	else
-#endif
-	ws *= f.dL * f.dL;
-	// the four partial sums through the (now idle) queue memory: s_q[w][0] belongs to wave w alone until the barrier
-	__builtin_amdgcn_wave_barrier();
-	if (lane == 0) wq[0] = __float_as_uint(ws);
-	__syncthreads();
-	if (tid == 0) f.tile_scores[vt] = (__uint_as_float(s_q[0][0]) + __uint_as_float(s_q[1][0])) + (__uint_as_float(s_q[2][0]) + __uint_as_float(s_q[3][0]));
-}
-#endif   // FR_AB
-
 // ---------------------------------------------------------------------------------------------------------
 // Forward compositing with the scorer's walk (k_fisher_tile_v3): the wave streams the tile's keys, keeps the splats whose
 // alpha footprint box meets its strip in an LDS ring, and then takes 64 candidates at a time -- one per lane: the lane parks
 // the candidate's record in LDS and rasterises its footprint ellipse into a 64-bit mask over the strip's pixels; a 64 x 64 bit
 // transpose hands every pixel-lane the mask of candidates that may touch it, and the lane walks ITS set bits front to back.
-// k_render_forward evaluates every surviving candidate on all 64 lanes (wave-uniform loop, v_readlane broadcasts): about three
-// times the steps.  The arithmetic of a (pixel, splat) pair and the order of the pairs of a pixel are those of
-// k_render_forward, so colour, depth, final_T and n_contrib stay bit-identical to the oracle's.
+// (Round 1's kernel evaluated every surviving candidate on all 64 lanes -- a wave-uniform loop of v_readlane broadcasts: about
+// three times the steps.)  A skipped splat is one whose alpha is below 1/255 on every pixel of the strip, i.e. one the reference
+// (forward.cu:261-393) skips pixel by pixel; the arithmetic of a (pixel, splat) pair and the order of the pairs of a pixel are the
+// reference's, so colour, depth, final_T and n_contrib stay bit-identical to the oracle's.
+// NCH = 6: a second [P,3] feature array composited in the same pass (fr_forward_pair).
 template <int NCH>
 __global__ __launch_bounds__(FR_THREADS) void k_render_forward_walk(FrParams p, const float* __restrict__ feat, int feat_view_stride,
                                                                     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
@@ -4394,13 +3787,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_render_forward_walk(FrParams p, 
 	if (64u + lane < n) id2 = (uint32_t)gk[64 + lane];
 	uint32_t base = 0;
 	bool all_done = __builtin_amdgcn_ballot_w64(!done) == 0ull;
-#ifdef FR_FWD_STATS
-	long long st_t0 = (long long)__builtin_amdgcn_s_memtime(), st_stream = 0, st_setup = 0, st_walk = 0;
-	uint32_t st_chunks = 0, st_steps = 0, st_windows = 0;
-#define FR_FWD_STAMP(acc) { const long long t = (long long)__builtin_amdgcn_s_memtime(); acc += t - st_t0; st_t0 = t; }
-#else
-#define FR_FWD_STAMP(acc)
-#endif
+	FR_FWD_DECLARE
 	while (!all_done)
 	{
 		// ---- stream: fill the ring up to one chunk
@@ -4419,11 +3806,9 @@ __global__ __launch_bounds__(FR_THREADS) void k_render_forward_walk(FrParams p, 
 			if (ov) wq[(qh + qn + (uint32_t)__popcll(om & ((1ull << lane) - 1ull))) & (FR_QCAP - 1)] = make_uint2(idc, base + (uint32_t)lane);
 			qn += (uint32_t)__popcll(om);
 			base += 64;
-#ifdef FR_FWD_STATS
-			st_windows++;
-#endif
+			FR_FWD(fs.windows++;)
 		}
-		FR_FWD_STAMP(st_stream)
+		FR_FWD_STAMP(stream)
 		if (qn == 0) break;
 		// ---- chunk: up to 64 candidates, one per lane
 		const uint32_t m = qn < 64u ? qn : 64u;
@@ -4449,11 +3834,8 @@ __global__ __launch_bounds__(FR_THREADS) void k_render_forward_walk(FrParams p, 
 		if (done) mask = 0ull;
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 		__builtin_amdgcn_wave_barrier();
-		FR_FWD_STAMP(st_setup)
-#ifdef FR_FWD_STATS
-		st_chunks++;
-		{ uint32_t pc = (uint32_t)__popcll(mask); for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)pc, o, 64); pc = t > pc ? t : pc; } st_steps += pc; }
-#endif
+		FR_FWD_STAMP(setup)
+		FR_FWD(fs.chunk(mask);)
 		// ---- walk
 		while (mask != 0ull)
 		{
@@ -4480,16 +3862,9 @@ __global__ __launch_bounds__(FR_THREADS) void k_render_forward_walk(FrParams p, 
 			last_contributor = __float_as_uint(r2.w) + 1u;
 		}
 		all_done = __builtin_amdgcn_ballot_w64(!done) == 0ull;
-		FR_FWD_STAMP(st_walk)
+		FR_FWD_STAMP(walk)
 	}
-#ifdef FR_FWD_STATS
-	if (out_depth && inside && lane < 8)
-	{
-		// (rig: the wave's counters in place of the depth of its first eight pixels -- tools/fwd_walk_stats.py)
-		const float vals[8] = { (float)(st_stream >> 6), (float)(st_setup >> 6), (float)(st_walk >> 6), (float)st_chunks, (float)st_steps, (float)st_windows, (float)n, 0.f };
-		D = vals[lane];
-	}
-#endif
+	FR_FWD(if (out_depth && inside && lane < 8) D = fs.result(lane, n);)
 	if (inside)
 	{
 		const size_t HW = (size_t)p.H * p.W;
@@ -4777,7 +4152,7 @@ void k_fisher_tile_v3h(FrParams p, FrFisherArgs f, const float4* __restrict__ re
 				float h[4]; bool con;
 				const bool kill = pair(ent_lds + (uint32_t)j * (FR_ENT_F4 * 16), h[0], h[1], h[2], h[3], con);
 				const bool issue = fr_quad_combine<4>(con ? j : -1, h, lane);     // same-candidate neighbours of the quad add up first
-				FR_ABL(if (f.debug_mode != 29))                 // 29: ... and without the LDS atomics
+				FR_ABL(if (f.ablate != 29))                 // 29: ... and without the LDS atomics
 				if (issue)
 				{
 					atomicAdd(&acc[0][j], (double)h[0]); atomicAdd(&acc[1][j], (double)h[1]);
@@ -4797,7 +4172,7 @@ void k_fisher_tile_v3h(FrParams p, FrFisherArgs f, const float4* __restrict__ re
 				const int e = flat >> 2, c = flat & 3;
 				const uint32_t id_e = (uint32_t)__builtin_amdgcn_ds_bpermute(e << 2, (int)real_id);
 				const float a = ((uint32_t)e < m) ? (float)acc[c][e] * dL2 : 0.f;
-				FR_ABL(if (f.debug_mode != 28))                 // 28 (tools/fe_ablate.py --outh): the walk without its global atomics
+				FR_ABL(if (f.ablate != 28))                 // 28 (tools/fe_ablate.py --outh): the walk without its global atomics
 				if (a != 0.f) atomicAdd(dst + (size_t)id_e * 4 + c, a);
 			}
 			__builtin_amdgcn_wave_barrier();
@@ -5411,7 +4786,7 @@ void k_fisher_point_tile(FrParams p, FrFisherArgs f, float* __restrict__ slot_ac
 			}
 			lsum += (double)h[0];
 			const bool issue = fr_quad_combine<1>(con ? j : -1, h, lane);
-			FR_ABL(if (f.debug_mode != 29))
+			FR_ABL(if (f.ablate != 29))
 			if (issue) atomicAdd(&acc[j], (double)h[0]);
 			if (kill) { mask = 0ull; done = true; }
 		}
@@ -5420,7 +4795,7 @@ void k_fisher_point_tile(FrParams p, FrFisherArgs f, float* __restrict__ slot_ac
 		__builtin_amdgcn_wave_barrier();
 		// flush: one float atomic per (strip, candidate), to the candidate's slot
 		const float a = ((uint32_t)lane < m) ? (float)acc[lane] * dL2 : 0.f;
-		FR_ABL(if (f.debug_mode != 28))       // 28: the walk without its global atomics
+		FR_ABL(if (f.ablate != 28))       // 28: the walk without its global atomics
 		if (a != 0.f) atomicAdd(dst + my_id, a);
 		__builtin_amdgcn_wave_barrier();
 	};
@@ -5474,7 +4849,7 @@ struct FrBwdArgs {
 	float* dL_dmean2D; float* dL_dconic; float* dL_dopacity; float* dL_dcolors; float* dL_dmean3D;
 	float* dL_dcov3D; float* dL_dscale; float* dL_drot;
 	const float* dL_dmean2D_b;   // or null: screen-space gradient of a second feature image (fr_backward_pair), added in k_backward_finish
-	// second image of k_backward_lin_tile<true>
+	// second image of k_backward_lin_tile
 	const float* dL_dpix2; const float* colors2; float* dL_dcolors2; float* dL_dmean2D_2;
 };
 
@@ -5667,14 +5042,13 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_tile(FrParams p, FrBwdA
 // strip, then a back-to-front walk in which every lane follows its own pixel's contributors; the 9 sums of a 64-entry
 // chunk live in LDS (ds_add_f32) and leave as one global atomic per entry and component.
 // ---------------------------------------------------------------------------------------------------------
-// PAIR: two images on the same geometry in one pass (fr_backward_pair): channels 0-2 = b.colors / b.dL_dpix, channels 3-5 =
+// Two images on the same geometry in one pass (fr_backward_pair): channels 0-2 = b.colors / b.dL_dpix, channels 3-5 =
 // b.colors2 / b.dL_dpix2.  Every leaf sums both images, except the screen-space gradient (kept apart: the densifier reads the
-// colour image's only, gaussian.py:207) and the colour gradients.
-template <bool PAIR>
+// colour image's only, gaussian.py:207) and the colour gradients.  (A single image goes to k_backward_lin_walk.)
 __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_tile(FrParams p, FrBwdArgs b, uint8_t* __restrict__ fallback)
 {
-	constexpr int NCH = PAIR ? 6 : 3;
-	constexpr int NACC = PAIR ? 14 : 9;          // m2x, m2y, qx, qy, qw, dcolor[NCH], dopacity, (m2x, m2y of the second image)
+	constexpr int NCH = 6;
+	constexpr int NACC = 14;                     // m2x, m2y, qx, qy, qw, dcolor[NCH], dopacity, m2x, m2y of the second image
 	__shared__ uint16_t s_wl[4][FR_WCAP];
 	__shared__ double s_acc[4][NACC][64];        // double: ds_add_f64 is ~20x faster than ds_add_f32 on MI355X (tools/lds_atomic_rate.hip)
 	__shared__ int s_ovf;
@@ -5778,10 +5152,10 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_tile(FrParams p, Fr
 	if (inside)
 	{
 		g[0] = b.dL_dpix[pix]; g[1] = b.dL_dpix[HW + pix]; g[2] = b.dL_dpix[2 * HW + pix];
-		if constexpr (PAIR) { g[3] = b.dL_dpix2[pix]; g[4] = b.dL_dpix2[HW + pix]; g[5] = b.dL_dpix2[2 * HW + pix]; }
+		g[3] = b.dL_dpix2[pix]; g[4] = b.dL_dpix2[HW + pix]; g[5] = b.dL_dpix2[2 * HW + pix];
 	}
 	const float bg_dot_a = p.bg[0] * g[0] + p.bg[1] * g[1] + p.bg[2] * g[2];
-	const float bg_dot_b = PAIR ? (p.bg[0] * g[3] + p.bg[1] * g[4] + p.bg[2] * g[5]) : 0.f;
+	const float bg_dot_b = p.bg[0] * g[3] + p.bg[1] * g[4] + p.bg[2] * g[5];
 	const float ddelx_dx = (float)(0.5 * p.W), ddely_dy = (float)(0.5 * p.H);
 	const uint16_t* wl = s_wl[wave];
 
@@ -5806,7 +5180,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_tile(FrParams p, Fr
 			ahx = __half2float(__ushort_as_half((unsigned short)(eb & 0xffffu)));
 			ahy = __half2float(__ushort_as_half((unsigned short)(eb >> 16)));
 			col[0] = b.colors[3 * (size_t)my_id]; col[1] = b.colors[3 * (size_t)my_id + 1]; col[2] = b.colors[3 * (size_t)my_id + 2];
-			if constexpr (PAIR) { col[3] = b.colors2[3 * (size_t)my_id]; col[4] = b.colors2[3 * (size_t)my_id + 1]; col[5] = b.colors2[3 * (size_t)my_id + 2]; }
+			col[3] = b.colors2[3 * (size_t)my_id]; col[4] = b.colors2[3 * (size_t)my_id + 1]; col[5] = b.colors2[3 * (size_t)my_id + 2];
 		}
 		unsigned long long emask = 0ull;
 		if (lane < m && ahx >= 0.f)
@@ -5878,24 +5252,22 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_tile(FrParams p, Fr
 				last_alpha = alpha;
 				const float bgf = -T_final / (1.f - alpha);
 				if (bg_dot_a != 0.f) da += bgf * bg_dot_a;
-				if (PAIR && bg_dot_b != 0.f) db += bgf * bg_dot_b;
+				if (bg_dot_b != 0.f) db += bgf * bg_dot_b;
 				const float dL_dalpha = da + db;
 				const float dL_dG = o * dL_dalpha;
 				const float gdx = G * dx, gdy = G * dy;
 				const float dG_ddelx = -gdx * cx - gdy * cy, dG_ddely = -gdy * cz - gdx * cy;
-				// screen-space gradient of the first image (of the only image when !PAIR)
-				const float oa = PAIR ? o * da : dL_dG;
+				// screen-space gradient of the first image
+				const float oa = o * da;
 				atomicAdd(&s_acc[wave][0][j], (double)(oa * dG_ddelx * ddelx_dx)); atomicAdd(&s_acc[wave][1][j], (double)(oa * dG_ddely * ddely_dy));
 				atomicAdd(&s_acc[wave][2][j], (double)(-0.5f * gdx * dx * dL_dG)); atomicAdd(&s_acc[wave][3][j], (double)(-0.5f * gdx * dy * dL_dG));
 				atomicAdd(&s_acc[wave][4][j], (double)(-0.5f * gdy * dy * dL_dG));
 #pragma unroll
 				for (int c = 0; c < NCH; c++) atomicAdd(&s_acc[wave][5 + c][j], (double)(wcol * g[c]));
 				atomicAdd(&s_acc[wave][5 + NCH][j], (double)(G * dL_dalpha));
-				if constexpr (PAIR)
-				{
-					const float ob = o * db;
-					atomicAdd(&s_acc[wave][12][j], (double)(ob * dG_ddelx * ddelx_dx)); atomicAdd(&s_acc[wave][13][j], (double)(ob * dG_ddely * ddely_dy));
-				}
+				// ... and of the second
+				const float ob = o * db;
+				atomicAdd(&s_acc[wave][12][j], (double)(ob * dG_ddelx * ddelx_dx)); atomicAdd(&s_acc[wave][13][j], (double)(ob * dG_ddely * ddely_dy));
 			}
 		}
 		__builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's own ds_add instructions have retired
@@ -5911,14 +5283,11 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_tile(FrParams p, Fr
 			if ((a = (float)s_acc[wave][5][lane]) != 0.f) atomicAdd(b.dL_dcolors + 3 * id, a);
 			if ((a = (float)s_acc[wave][6][lane]) != 0.f) atomicAdd(b.dL_dcolors + 3 * id + 1, a);
 			if ((a = (float)s_acc[wave][7][lane]) != 0.f) atomicAdd(b.dL_dcolors + 3 * id + 2, a);
-			if constexpr (PAIR)
-			{
-				if ((a = (float)s_acc[wave][8][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id, a);
-				if ((a = (float)s_acc[wave][9][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id + 1, a);
-				if ((a = (float)s_acc[wave][10][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id + 2, a);
-				if ((a = (float)s_acc[wave][12][lane]) != 0.f) atomicAdd(b.dL_dmean2D_2 + 3 * id, a);
-				if ((a = (float)s_acc[wave][13][lane]) != 0.f) atomicAdd(b.dL_dmean2D_2 + 3 * id + 1, a);
-			}
+			if ((a = (float)s_acc[wave][8][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id, a);
+			if ((a = (float)s_acc[wave][9][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id + 1, a);
+			if ((a = (float)s_acc[wave][10][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id + 2, a);
+			if ((a = (float)s_acc[wave][12][lane]) != 0.f) atomicAdd(b.dL_dmean2D_2 + 3 * id, a);
+			if ((a = (float)s_acc[wave][13][lane]) != 0.f) atomicAdd(b.dL_dmean2D_2 + 3 * id + 1, a);
 			if ((a = (float)s_acc[wave][5 + NCH][lane]) != 0.f) atomicAdd(b.dL_dopacity + id, a);
 		}
 	}
@@ -5932,12 +5301,11 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_tile(FrParams p, Fr
 // old kernel ran this walk wave-uniformly with a dozen ds_bpermute per step, after a wave-uniform first pass that rebuilt
 // final_T and a per-wave contributor list in 30 KiB of LDS).  Per pair the arithmetic is k_backward_lin_tile's.
 // No list capacity, hence no fallback tiles.
-template <bool PAIR>
 __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_walk(FrParams p, FrBwdArgs b)
 {
-	constexpr int NCH = PAIR ? 6 : 3;
-	constexpr int NACC = PAIR ? 14 : 9;          // m2x, m2y, qx, qy, qw, dcolor[NCH], dopacity, (m2x, m2y of the second image)
-	constexpr int EF4 = PAIR ? 5 : 3;            // float4 per parked record (4 would repeat the LDS banks after four records)
+	constexpr int NCH = 3;
+	constexpr int NACC = 9;                      // m2x, m2y, qx, qy, qw, dcolor[NCH], dopacity
+	constexpr int EF4 = 3;                       // float4 per parked record (4 would repeat the LDS banks after four records)
 	__shared__ uint2 s_q[4][FR_QCAP];            // ring of {index, position in the tile's list}
 	__shared__ float4 s_ent[4][64][EF4];
 	__shared__ double s_acc[4][NACC][64];        // double: ds_add_f64 is ~20x faster than ds_add_f32 on MI355X (tools/lds_atomic_rate.hip)
@@ -5966,10 +5334,8 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_walk(FrParams p, Fr
 	if (inside)
 	{
 		g[0] = b.dL_dpix[pix]; g[1] = b.dL_dpix[HW + pix]; g[2] = b.dL_dpix[2 * HW + pix];
-		if constexpr (PAIR) { g[3] = b.dL_dpix2[pix]; g[4] = b.dL_dpix2[HW + pix]; g[5] = b.dL_dpix2[2 * HW + pix]; }
 	}
-	const float bg_dot_a = p.bg[0] * g[0] + p.bg[1] * g[1] + p.bg[2] * g[2];
-	const float bg_dot_b = PAIR ? (p.bg[0] * g[3] + p.bg[1] * g[4] + p.bg[2] * g[5]) : 0.f;
+	const float bg_dot = p.bg[0] * g[0] + p.bg[1] * g[1] + p.bg[2] * g[2];
 	const float ddelx_dx = (float)(0.5 * p.W), ddely_dy = (float)(0.5 * p.H);
 	const float strip_lo = (float)(ty * FR_BLOCK_Y + 4u * (uint32_t)wave), strip_hi = strip_lo + 3.0f;
 	const float tile_x0 = (float)(tx * FR_BLOCK_X), tile_x1 = tile_x0 + 15.0f;
@@ -6021,7 +5387,6 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_walk(FrParams p, Fr
 			ent[lane][0] = q0;
 			ent[lane][1] = make_float4(q1.x, q1.y, fr_power_threshold(q1.y), __uint_as_float(qe.y));
 			ent[lane][2] = make_float4(b.colors[3 * (size_t)my_id], b.colors[3 * (size_t)my_id + 1], b.colors[3 * (size_t)my_id + 2], 0.f);
-			if constexpr (PAIR) ent[lane][3] = make_float4(b.colors2[3 * (size_t)my_id], b.colors2[3 * (size_t)my_id + 1], b.colors2[3 * (size_t)my_id + 2], 0.f);
 			const float4 a = make_float4(q0.x, q0.y, q1.w, __builtin_amdgcn_logf(q1.y));
 			const float4 b4 = make_float4(-0.5f * q0.z, -q0.w, -0.5f * q1.x, 0.f);
 			emask = fr_footprint_mask<16, 4>(a, b4, strip_lo, tile_x0);
@@ -6040,7 +5405,6 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_walk(FrParams p, Fr
 			if (__float_as_uint(r1.w) >= ncontrib) continue;          // behind the pixel's last contributor (backward.cu:951-957)
 			float rc[NCH];
 			rc[0] = r2.x; rc[1] = r2.y; rc[2] = r2.z;
-			if constexpr (PAIR) { const float4 r3 = ent[j][3]; rc[3] = r3.x; rc[4] = r3.y; rc[5] = r3.z; }
 			const float cx = r0.z, cy = r0.w, cz = r1.x, o = r1.y;
 			const float dx = r0.x - pfx, dy = r0.y - pfy;
 			const float power = -0.5f * (cx * dx * dx + cz * dy * dy) - cy * dx * dy;
@@ -6048,40 +5412,33 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_walk(FrParams p, Fr
 			const float G = fr_expf_inrange(power);
 			const float alpha = fminf(0.99f, o * G);
 			if (alpha < 1.0f / 255.0f) continue;
-			// backward.cu:978-1038, per image: dL_dalpha = sum_ch (c_ch - accum_ch) dL_dpix_ch T  (- T_final / (1 - alpha) bg . dL_dpix)
+			// backward.cu:978-1038: dL_dalpha = sum_ch (c_ch - accum_ch) dL_dpix_ch T  (- T_final / (1 - alpha) bg . dL_dpix)
 			Tc = Tc / (1.f - alpha);
 			const float wcol = alpha * Tc;
-			float da = 0.f, db = 0.f;
+			float dL_dalpha = 0.f;
 #pragma unroll
 			for (int c = 0; c < NCH; c++)
 			{
 				accum[c] = last_alpha * lastc[c] + (1.f - last_alpha) * accum[c];
 				lastc[c] = rc[c];
-				const float t = (rc[c] - accum[c]) * g[c];
-				if (c < 3) da += t; else db += t;
+				dL_dalpha += (rc[c] - accum[c]) * g[c];
 			}
-			da *= Tc; db *= Tc;
+			dL_dalpha *= Tc;
 			last_alpha = alpha;
 			const float bgf = -T_final / (1.f - alpha);
-			if (bg_dot_a != 0.f) da += bgf * bg_dot_a;
-			if (PAIR && bg_dot_b != 0.f) db += bgf * bg_dot_b;
-			const float dL_dalpha = da + db;
+			if (bg_dot != 0.f) dL_dalpha += bgf * bg_dot;
+			// (what the two-image form of this walk left behind -- its second image's share, 0 * Tc: kept, because a NaN or an infinite
+			// Tc reaches the sums through it and this kernel is to compute bit for bit what it did)
+			dL_dalpha += 0.f * Tc;
 			const float dL_dG = o * dL_dalpha;
 			const float gdx = G * dx, gdy = G * dy;
 			const float dG_ddelx = -gdx * cx - gdy * cy, dG_ddely = -gdy * cz - gdx * cy;
-			// screen-space gradient of the first image (of the only image when !PAIR)
-			const float oa = PAIR ? o * da : dL_dG;
-			atomicAdd(&s_acc[wave][0][j], (double)(oa * dG_ddelx * ddelx_dx)); atomicAdd(&s_acc[wave][1][j], (double)(oa * dG_ddely * ddely_dy));
+			atomicAdd(&s_acc[wave][0][j], (double)(dL_dG * dG_ddelx * ddelx_dx)); atomicAdd(&s_acc[wave][1][j], (double)(dL_dG * dG_ddely * ddely_dy));
 			atomicAdd(&s_acc[wave][2][j], (double)(-0.5f * gdx * dx * dL_dG)); atomicAdd(&s_acc[wave][3][j], (double)(-0.5f * gdx * dy * dL_dG));
 			atomicAdd(&s_acc[wave][4][j], (double)(-0.5f * gdy * dy * dL_dG));
 #pragma unroll
 			for (int c = 0; c < NCH; c++) atomicAdd(&s_acc[wave][5 + c][j], (double)(wcol * g[c]));
 			atomicAdd(&s_acc[wave][5 + NCH][j], (double)(G * dL_dalpha));
-			if constexpr (PAIR)
-			{
-				const float ob = o * db;
-				atomicAdd(&s_acc[wave][12][j], (double)(ob * dG_ddelx * ddelx_dx)); atomicAdd(&s_acc[wave][13][j], (double)(ob * dG_ddely * ddely_dy));
-			}
 		}
 		__builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's own ds_add instructions have retired
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -6098,14 +5455,6 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_walk(FrParams p, Fr
 			if ((a = (float)s_acc[wave][5][lane]) != 0.f) atomicAdd(b.dL_dcolors + 3 * id, a);
 			if ((a = (float)s_acc[wave][6][lane]) != 0.f) atomicAdd(b.dL_dcolors + 3 * id + 1, a);
 			if ((a = (float)s_acc[wave][7][lane]) != 0.f) atomicAdd(b.dL_dcolors + 3 * id + 2, a);
-			if constexpr (PAIR)
-			{
-				if ((a = (float)s_acc[wave][8][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id, a);
-				if ((a = (float)s_acc[wave][9][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id + 1, a);
-				if ((a = (float)s_acc[wave][10][lane]) != 0.f) atomicAdd(b.dL_dcolors2 + 3 * id + 2, a);
-				if ((a = (float)s_acc[wave][12][lane]) != 0.f) atomicAdd(b.dL_dmean2D_2 + 3 * id, a);
-				if ((a = (float)s_acc[wave][13][lane]) != 0.f) atomicAdd(b.dL_dmean2D_2 + 3 * id + 1, a);
-			}
 			if ((a = (float)s_acc[wave][5 + NCH][lane]) != 0.f) atomicAdd(b.dL_dopacity + id, a);
 		}
 		__builtin_amdgcn_wave_barrier();
@@ -6116,7 +5465,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_backward_lin_walk(FrParams p, Fr
 // grad_power == 2 through the rasteriser API (the reference's own Fisher loop, gaussian.py:1536-1556: one view, autograd,
 // GaussianRasterizer(backward_power=2)): every leaf the reference accumulates is w = opacity G dL_dalpha times a per-Gaussian row
 // applied to gamma(u) = (ux, uy, ux^2, ux uy, uy^2), u = -conic d (fr_math.h).  k_backward_sq_rows builds the rows ONCE per
-// visible Gaussian (k_fisher_tile_v2<25> rebuilt them per (strip, list chunk): 256 VGPRs, 544 bytes of scratch); the tile
+// visible Gaussian (round 2's all-leaves two-pass kernel rebuilt them per (strip, list chunk): 256 VGPRs, 544 bytes of scratch); the tile
 // kernel is k_backward_lin_walk's walk -- back to front, final_T / n_contrib from the forward pass, the reference's recurrences
 // and the forward's exact arithmetic (fr_expf, IEEE division), no first pass, no list capacity -- with the rows parked beside the
 // candidate: per pair 54 multiply-adds give the 25 leaves, their squares go into per-candidate LDS accumulators (double).
@@ -7166,7 +6515,7 @@ static FrLayout fr_layout(int64_t P, int64_t W, int64_t H, int64_t V, int64_t ma
 	L.cov3D = o; o = fr_align(o + (size_t)P * 24);
 	L.rgb = o; o = fr_align(o + VP * 12);
 	L.clamped = o; o = fr_align(o + VP * 3);
-	L.packed = o; o = fr_align(o + (size_t)P * 256);     // per-Gaussian leaf rows of the power-2 backward (k_backward_sq_rows: 224 B; k_fisher_tile_v2<25>: 128 B), written by fr_backward
+	L.packed = o; o = fr_align(o + (size_t)P * 256);     // per-Gaussian leaf rows of the power-2 backward (k_backward_sq_rows: 224 B), written by fr_backward
 	L.geom_bytes = o > 0 ? o : 256;
 	o = 0;
 	L.tile_cnt = o; o = fr_align(o + (size_t)(V * T) * 4);
@@ -7256,8 +6605,7 @@ static void fr_fill_params(FrParams& p, const fr_raster_cfg* cfg, const fr_gauss
 	p.VC = 1;
 	p.small_max = FR_SORT_SMALL_KEYS;
 	p.order = nullptr;
-	p.legacy_sort = fr_debug_mode() == 6;
-	FR_ABL(p.ablate = fr_debug_mode();)
+	FR_ABL(p.ablate = fr_ablate_mode();)
 }
 
 // Launches cov3d, preprocess, scan, scatter, sort for V views.  p must carry the carved buffers.
@@ -7420,8 +6768,8 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 	FrJoinGuard joins(s);
 	if (multi)
 	{
-		// compact records: written once, in place, by k_preprocess_views_c (FR_DEBUG_MODE=20 keeps the parking form for A/B runs)
-		const bool once = plan && plan->ra.comp != nullptr && fr_debug_mode() != 20;
+		// compact records: written once, in place, by k_preprocess_views_c
+		const bool once = plan && plan->ra.comp != nullptr;
 		if (!once) p.tile_cap = 0;                       // fixed key segments are filled by k_preprocess_views_c only
 		const bool wanted_fixed = p.tile_cap != 0;
 		if (once) p.VC = fr_plan_views_c(p.T, p.VC, p.tile_cap);
@@ -7429,7 +6777,7 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 		if (once && wanted_fixed && !p.tile_cap) return fr_fail(FR_EINVAL, "fr_bin_pipeline: fixed key segments planned, but they do not fit the LDS");
 		auto lds_c_of = [&](int vc) { return fr_lds_views_c(vc, p.T, p.tile_cap != 0); };
 		dim3 gridV(gridP.x, (p.V + p.VC - 1) / p.VC);
-		const size_t lds = ((size_t)p.VC * p.T + (size_t)FR_THREADS * p.VC + 12 * (size_t)p.VC + 2 * (size_t)p.VC * 8 * (size_t)p.G) * 4;
+		const size_t lds = ((size_t)p.VC * p.T + (size_t)FR_THREADS * p.VC + 12 * (size_t)p.VC) * 4;
 		FrRecordArgs ra = plan ? plan->ra : FrRecordArgs{ nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 6 };
 		// The records are phase C of the projection kernel.  (Measured on MI355X, 500k Gaussians x 64 views: as a kernel of their
 		// own beside scan / scatter / sort -- on a second stream, also at the lowest stream priority -- the step takes 2.62 ms
@@ -7467,14 +6815,8 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 			}
 		}
 #undef FR_VIEWS_C
-		else if (!plan) hipLaunchKernelGGL((k_preprocess_views<0, false>), gridV, dim3(FR_THREADS), lds, s, p, ra);
-#ifdef FR_AB
-		else if (plan->form == FrRecForm::A) hipLaunchKernelGGL((k_preprocess_views<-4, true>), gridV, dim3(FR_THREADS), lds, s, p, ra);
-		else if (c4) hipLaunchKernelGGL((k_preprocess_views<4, true>), gridV, dim3(FR_THREADS), lds, s, p, ra);
-		else hipLaunchKernelGGL((k_preprocess_views<11, true>), gridV, dim3(FR_THREADS), lds, s, p, ra);
-#else
+		else if (!plan) hipLaunchKernelGGL(k_preprocess_views, gridV, dim3(FR_THREADS), lds, s, p, ra);
 		else return fr_fail(FR_EINVAL, "fr_bin_pipeline: a records plan of the multi-view front end needs compact records");
-#endif
 		if ((rc = fr_check_launch("k_preprocess_views"))) return rc;
 	}
 	else
@@ -7491,7 +6833,7 @@ static int fr_bin_pipeline(FrParams& p, const fr_gaussians* g, hipStream_t s, co
 	}
 	if (multi && p.tile_cap)
 		hipLaunchKernelGGL(k_tile_lists, dim3((p.V * p.T + 4 * FR_THREADS - 1) / (4 * FR_THREADS)), dim3(FR_THREADS), 0, s, p.tile_cnt, p.tile_off, p.V * p.T, p.T,
-		                   p.tile_cap, p.status, p.big_list, p.view_work, p.view_perm, p.ablate, p.small_max);
+		                   p.tile_cap, p.status, p.big_list, p.view_work, p.view_perm, FR_ABL_OR(p.ablate, 0), p.small_max);
 	else
 	hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, p.tile_cnt, p.tile_off, p.tile_fill, p.V * p.T, p.T, p.V,
 	                   p.key_capacity, p.status, multi ? (int*)nullptr : p.num_rendered, p.big_list, p.view_work, p.view_perm);
@@ -7614,17 +6956,11 @@ static int fr_forward_impl(const fr_raster_cfg* cfg, const fr_gaussians* g, cons
 	p.key_capacity = binning_capacity;
 	if ((rc = fr_bin_pipeline(p, g, s))) return rc;
 	const float* feat = g->colors_precomp ? g->colors_precomp : p.rgb;
-	FR_AB_ONLY(const bool bcast = fr_debug_mode() == 16;)        // FR_DEBUG_MODE=16: the wave-uniform compositing kernel of round 1 (A/B runs)
 	float* fT = (float*)((char*)image_ws + L.final_T);
 	uint32_t* nC = (uint32_t*)((char*)image_ws + L.n_contrib);
-#ifdef FR_AB
-	if (bcast && features2) hipLaunchKernelGGL((k_render_forward<6>), dim3(p.T, 1), dim3(FR_THREADS), 0, s, p, feat, 0, fT, nC, out_color, out_depth, features2, out_features2);
-	else if (bcast) hipLaunchKernelGGL((k_render_forward<3>), dim3(p.T, 1), dim3(FR_THREADS), 0, s, p, feat, 0, fT, nC, out_color, out_depth, (const float*)nullptr, (float*)nullptr);
-	else
-#endif
 	if (features2) hipLaunchKernelGGL((k_render_forward_walk<6>), dim3(p.T, 1), dim3(FR_THREADS), 0, s, p, feat, 0, fT, nC, out_color, out_depth, features2, out_features2);
 	else hipLaunchKernelGGL((k_render_forward_walk<3>), dim3(p.T, 1), dim3(FR_THREADS), 0, s, p, feat, 0, fT, nC, out_color, out_depth, (const float*)nullptr, (float*)nullptr);
-	if ((rc = fr_check_launch("k_render_forward"))) return rc;
+	if ((rc = fr_check_launch("k_render_forward_walk"))) return rc;
 	(void)hipMemcpyAsync(status, p.status, 16, hipMemcpyDeviceToDevice, s);
 	return FR_OK;
 }
@@ -7745,10 +7081,10 @@ extern "C" int fr_backward_ws(const fr_raster_cfg* cfg, const fr_gaussians* g, c
 	    !dL_dmeans3D || !dL_dcov3D || !dL_dscales || !dL_drotations || !dL_dconic)
 		return fr_fail(FR_EINVAL, "fr_backward: null pointer");
 	if (g->shs && !dL_dsh) return fr_fail(FR_EINVAL, "fr_backward: dL_dsh is null although SHs were given");
-	const bool sq_rows_path = power == 2 && g->scales && !g->shs && g->colors_precomp && !g->cov3D_precomp && fr_debug_mode() != 21;
+	const bool sq_rows_path = power == 2 && g->scales && !g->shs && g->colors_precomp && !g->cov3D_precomp;
 	const int64_t T_img = ((int64_t)(W + 15) / 16) * ((int64_t)(H + 15) / 16);
 	// few tiles and a scratch buffer: the chunked form (FR_DEBUG_MODE=33 in the rig: one workgroup per tile whatever the scratch)
-	const bool chunk_path = sq_rows_path || (power == 1 FR_AB_ONLY(&& fr_debug_mode() != 17));
+	const bool chunk_path = sq_rows_path || power == 1;
 	const size_t scratch_need = chunk_path ? fr_backward_scratch_bytes(P, W, H, power, num_rendered) : 0;
 	const bool segmented = chunk_path && scratch && scratch_need > 0 && scratch_bytes >= scratch_need FR_AB_ONLY(&& fr_debug_mode() != 33);
 	const FrSqScratch sq = fr_sq_scratch(T_img, segmented ? num_rendered : 1);
@@ -7783,26 +7119,8 @@ extern "C" int fr_backward_ws(const fr_raster_cfg* cfg, const fr_gaussians* g, c
 	b.dL_dmean2D_b = nullptr;
 	if (power == 1)
 	{
-		// gradients: sum u per splat in the tile kernel, Jacobian chain once per Gaussian; tiles that do not fit the LDS
-		// index are redone (u only) by the scan kernel.  The flag array borrows tile_fill, which is dead after binning.
-		// FR_DEBUG_MODE=17: the two-pass tile kernel of round 1 with its fallback pass (A/B runs); k_backward_lin_walk has no list
-		// capacity and therefore no fallback tiles
-#ifdef FR_AB
-		if (fr_debug_mode() == 17)
-		{
-			uint8_t* fallback = (uint8_t*)p.tile_fill;
-			hipLaunchKernelGGL((k_backward_lin_tile<false>), dim3(p.T), block, 0, s, p, b, fallback);
-			if ((rc = fr_check_launch("k_backward_lin_tile"))) return rc;
-			b.only_flagged = fallback;
-			b.u_only = 1;
-			if (sr && sh) hipLaunchKernelGGL((k_backward_tile<true, true>), grid, block, 0, s, p, b);
-			else if (sr) hipLaunchKernelGGL((k_backward_tile<true, false>), grid, block, 0, s, p, b);
-			else if (sh) hipLaunchKernelGGL((k_backward_tile<false, true>), grid, block, 0, s, p, b);
-			else hipLaunchKernelGGL((k_backward_tile<false, false>), grid, block, 0, s, p, b);
-			if ((rc = fr_check_launch("k_backward_tile(flagged)"))) return rc;
-		}
-		else
-#endif
+		// gradients: sum u per splat in the tile kernel, Jacobian chain once per Gaussian (k_backward_lin_walk has no list
+		// capacity and therefore no fallback tiles)
 		if (segmented)
 		{
 			if ((rc = fr_launch_chunked<3>(p, b, sq, scratch, nullptr, s))) return rc;
@@ -7810,7 +7128,7 @@ extern "C" int fr_backward_ws(const fr_raster_cfg* cfg, const fr_gaussians* g, c
 		}
 		else
 		{
-			hipLaunchKernelGGL((k_backward_lin_walk<false>), dim3(p.T), block, 0, s, p, b);
+			hipLaunchKernelGGL(k_backward_lin_walk, dim3(p.T), block, 0, s, p, b);
 			if ((rc = fr_check_launch("k_backward_lin_walk"))) return rc;
 			b.u_only = 1;
 		}
@@ -7825,7 +7143,6 @@ extern "C" int fr_backward_ws(const fr_raster_cfg* cfg, const fr_gaussians* g, c
 	{
 		// The diagonal Fisher proxy as the reference's own loop asks for it (gaussian.py:1536-1556: one view, autograd, power 2):
 		// the leaf rows once per visible Gaussian (k_backward_sq_rows), then the walking tile kernel (k_backward_sq_walk).
-		// FR_DEBUG_MODE=21 keeps round 2's all-leaves tile kernel (k_fisher_tile_v2<25>) for A/B runs.
 		float* rows = (float*)((char*)geom_ws + L.packed);           // [P] x 56 floats at 256-byte steps (FR_SQ_ROW_STRIDE) in the geometry buffer's per-Gaussian region
 		hipLaunchKernelGGL(k_backward_sq_rows, dim3((P + FR_THREADS - 1) / FR_THREADS), block, 0, s, p, rows);
 		if ((rc = fr_check_launch("k_backward_sq_rows"))) return rc;
@@ -7833,29 +7150,6 @@ extern "C" int fr_backward_ws(const fr_raster_cfg* cfg, const fr_gaussians* g, c
 		hipLaunchKernelGGL(k_backward_sq_walk, dim3(p.T), block, 0, s, p, b, (const float*)rows);
 		return fr_check_launch("k_backward_sq_walk");
 	}
-#ifdef FR_AB
-	if (power == 2 && sr && !sh && g->colors_precomp && !g->cov3D_precomp)
-	{
-		// The diagonal Fisher proxy as the reference's own loop asks for it (gaussian.py:1536-1556: one view, autograd, power 2):
-		// the wave-private two-pass kernel of the batched scorer with all 25 leaves, the upstream gradient as a per-pixel image;
-		// tiles that do not fit its LDS index are redone by the generic kernel below.
-		float* packed = (float*)((char*)geom_ws + L.packed);
-		uint8_t* fallback = (uint8_t*)p.tile_fill;
-		FrParams pp = p;
-		pp.colors = g->colors_precomp;
-		hipLaunchKernelGGL((k_pack_static<25>), dim3((P + FR_THREADS - 1) / FR_THREADS), block, 0, s, pp, (const float*)nullptr, packed, (float4*)nullptr, (float4*)nullptr);
-		FrFisherArgs f;
-		memset(&f, 0, sizeof(f));
-		f.dL_img = dL_dout_color; f.dL_stride = 0;
-		f.full_out[0] = dL_dmeans3D; f.full_out[1] = dL_dopacity; f.full_out[2] = dL_dscales; f.full_out[3] = dL_drotations;
-		f.full_out[4] = dL_dcolors; f.full_out[5] = dL_dmeans2D; f.full_out[6] = dL_dcov3D; f.full_out[7] = dL_dconic;
-		hipLaunchKernelGGL((k_fisher_tile_v2<25, false, true>), dim3(p.T), block, 0, s, pp, f, (const float*)packed, fallback);
-		if ((rc = fr_check_launch("k_fisher_tile_v2<25>"))) return rc;
-		b.only_flagged = fallback;
-		hipLaunchKernelGGL((k_backward_tile<true, false>), grid, block, 0, s, p, b);
-		return fr_check_launch("k_backward_tile(flagged)");
-	}
-#endif
 	if (sr && sh) hipLaunchKernelGGL((k_backward_tile<true, true>), grid, block, 0, s, p, b);
 	else if (sr) hipLaunchKernelGGL((k_backward_tile<true, false>), grid, block, 0, s, p, b);
 	else if (sh) hipLaunchKernelGGL((k_backward_tile<false, true>), grid, block, 0, s, p, b);
@@ -7891,17 +7185,10 @@ extern "C" int fr_forward_features(const fr_raster_cfg* cfg, const float* featur
 	FrParams p;
 	fr_fill_params(p, cfg, &g0, 1);
 	fr_carve_single(p, L, (char*)geom_ws, (char*)binning_ws, (char*)image_ws);
-#ifdef FR_AB
-	if (fr_debug_mode() == 16)
-		hipLaunchKernelGGL((k_render_forward<3>), dim3(p.T, 1), dim3(FR_THREADS), 0, s, p, features, 0,
-		                   (float*)((char*)image_ws + L.final_T), (uint32_t*)((char*)image_ws + L.n_contrib), out_features, (float*)nullptr,
-		                   (const float*)nullptr, (float*)nullptr);
-	else
-#endif
-		hipLaunchKernelGGL((k_render_forward_walk<3>), dim3(p.T, 1), dim3(FR_THREADS), 0, s, p, features, 0,
-		                   (float*)((char*)image_ws + L.final_T), (uint32_t*)((char*)image_ws + L.n_contrib), out_features, (float*)nullptr,
-		                   (const float*)nullptr, (float*)nullptr);
-	return fr_check_launch("k_render_forward(features)");
+	hipLaunchKernelGGL((k_render_forward_walk<3>), dim3(p.T, 1), dim3(FR_THREADS), 0, s, p, features, 0,
+	                   (float*)((char*)image_ws + L.final_T), (uint32_t*)((char*)image_ws + L.n_contrib), out_features, (float*)nullptr,
+	                   (const float*)nullptr, (float*)nullptr);
+	return fr_check_launch("k_render_forward_walk(features)");
 }
 
 extern "C" int fr_backward_pair(const fr_raster_cfg* cfg, const fr_gaussians* g, const int32_t* radii,
@@ -7937,7 +7224,7 @@ extern "C" int fr_backward_pair_ws(const fr_raster_cfg* cfg, const fr_gaussians*
 	// with a scratch buffer: the chunked form on six colour channels (FR_DEBUG_MODE=33 in the rig: never)
 	const int64_t T_img = ((int64_t)(W + 15) / 16) * ((int64_t)(H + 15) / 16);
 	const size_t scratch_need = fr_backward_pair_scratch_bytes(P, W, H, num_rendered);
-	const bool chunked = scratch && scratch_need > 0 && scratch_bytes >= scratch_need FR_AB_ONLY(&& fr_debug_mode() != 33 && fr_debug_mode() != 18);
+	const bool chunked = scratch && scratch_need > 0 && scratch_bytes >= scratch_need FR_AB_ONLY(&& fr_debug_mode() != 33);
 	const FrSqScratch sq = fr_sq_scratch(T_img, chunked ? num_rendered : 1, 6);
 	{
 		FrZeroer z;
@@ -7969,25 +7256,15 @@ extern "C" int fr_backward_pair_ws(const fr_raster_cfg* cfg, const fr_gaussians*
 	b.dL_dpix2 = dL_dout_features; b.colors2 = features; b.dL_dmean2D_2 = dL_dmeans2D_features; b.dL_dcolors2 = dL_dfeatures;
 	b.only_flagged = nullptr; b.u_only = 0;
 	// (the pair keeps the two-pass tile kernel: with fourteen accumulators per candidate the walk form measured 0.83 against
-	// 0.79 ms at 2M Gaussians / 512 x 512 -- the single image gains, 0.49 against 0.59; FR_DEBUG_MODE=18 forces the walk form)
-	const bool pair_walk = fr_debug_mode() == 18 || chunked;
+	// 0.79 ms at 2M Gaussians / 512 x 512 -- the single image gains, 0.49 against 0.59)
 	if (chunked)
 	{
 		if ((rc = fr_launch_chunked<6>(p, b, sq, scratch, nullptr, s))) return rc;
 	}
-	else
-#ifdef FR_AB
-	if (pair_walk)
-	{
-		hipLaunchKernelGGL((k_backward_lin_walk<true>), dim3(p.T), block, 0, s, p, b);
-		if ((rc = fr_check_launch("k_backward_lin_walk<pair>"))) return rc;
-	}
-	else
-#endif
-	hipLaunchKernelGGL((k_backward_lin_tile<true>), dim3(p.T), block, 0, s, p, b, fallback);
-	if ((rc = fr_check_launch("k_backward_lin_tile<pair>"))) return rc;
+	else hipLaunchKernelGGL(k_backward_lin_tile, dim3(p.T), block, 0, s, p, b, fallback);
+	if ((rc = fr_check_launch("k_backward_lin_tile"))) return rc;
 	// (two-pass kernel only) tiles whose lists do not fit the LDS index: the scan kernel, once per image
-	for (int pass = 0; pass < 2 && !pair_walk; pass++)
+	for (int pass = 0; pass < 2 && !chunked; pass++)
 	{
 		b.dL_dpix = pass ? dL_dout_features : dL_dout_color;
 		b.colors = pass ? features : g->colors_precomp;
@@ -8006,20 +7283,6 @@ extern "C" int fr_backward_pair_ws(const fr_raster_cfg* cfg, const fr_gaussians*
 	else hipLaunchKernelGGL((k_backward_finish<false, false>), gp, block, 0, s, p, b, (float*)nullptr);
 	return fr_check_launch("k_backward_finish");
 }
-
-// FR_DEBUG_MODE (timing ablations / loop statistics only), read once per process:
-//   1  k_fisher_tile_v2 stops after its first pass            6  the LDS-resident sort network of round 1
-//   7  every sort tier on the caller's stream (no fork)       8  8 x 8 pixel blocks per wave in k_fisher_tile_v3
-//   9  the second-generation two-pass kernels instead of k_fisher_tile_v3 / _v3h
-//   2-7, 10-12 in a -DFR_LOOPSTATS build: loop-trip counters and s_memtime shares (tools/loopstats.py)
-// FR_GV / FR_VC (read once as well): Gaussians per thread / views per workgroup of k_preprocess_views.
-#ifdef FR_AB
-static int fr_debug_mode()
-{
-	static const int mode = fr_env_int("FR_DEBUG_MODE");
-	return mode;
-}
-#endif
 
 #define FR_MAX_GROUPS 4              // view groups of one fr_fisher_views call (fr_pick_groups)
 struct FrFisherLayout {
@@ -8134,16 +7397,8 @@ struct FrProfSpan {
 static void fr_launch_fisher_v3(FrParams& p, FrFisherArgs f, float4* recq, hipStream_t s)
 {
 	FrProfSpan span(s);
-	// FR_DEBUG_MODE=8: 8 x 8 pixel blocks per wave instead of 16 x 4 strips (A/B runs; measured 5 % slower on MI355X);
-	// FR_DEBUG_MODE=24: the rolling two-chunk window (k_fisher_tile_v3w: 24 % fewer walk iterations, 8 % slower -- see there)
-#ifdef FR_AB
-	if (f.debug_mode == 8) hipLaunchKernelGGL((k_fisher_tile_v3<8, 8>), dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f, (const float4*)recq);
-	else if (f.debug_mode == 24) hipLaunchKernelGGL(k_fisher_tile_v3w, dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f);
-	else if (f.key_shift && f.debug_mode == 31) hipLaunchKernelGGL((k_fisher_tile_v3<16, 4, true>), dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f, (const float4*)recq);   // FR_DEBUG_MODE=31: the chunk-synchronous walk of round 3
-	else
-#endif
 	if (f.key_shift) hipLaunchKernelGGL(k_fisher_tile_v4, dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f);
-	else hipLaunchKernelGGL((k_fisher_tile_v3<16, 4>), dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f, (const float4*)recq);
+	else hipLaunchKernelGGL(k_fisher_tile_v3, dim3(p.T * p.V), dim3(FR_THREADS), 0, s, p, f, (const float4*)recq);
 }
 
 // out_H mode with 4 columns and a constant upstream gradient: two front-to-back passes over the records
@@ -8343,22 +7598,22 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	f.out_H = fc->out_H; f.outH_stride = fc->out_H_view_stride;
 	f.tile_scores = (float*)(ws + L.tile_scores);
 	f.only_flagged = nullptr;
-	f.debug_mode = fr_debug_mode();
+	FR_RIG_ARGS(f)
 	f.key_shift = 0;
+	const int dm = fr_debug_mode();
 	// score-only (H_inv, no out_H, constant upstream gradient): records + one front-to-back pass; FR_DEBUG_MODE=9 keeps
 	// the second-generation two-pass kernel for A/B runs
-	const bool v3 = fc->H_inv && !fc->out_H && !fc->dL_dpix_image && f.debug_mode != 1 && f.debug_mode != 9;
+	const bool v3 = fc->H_inv && !fc->out_H && !fc->dL_dpix_image && dm != 1 && dm != 9;
 	// the diagonal itself (out_H, no H_inv, 4 columns, constant upstream gradient): records + two front-to-back passes
-	const bool v3h = !fc->H_inv && fc->out_H && !fc->dL_dpix_image && fc->columns == 4 && f.debug_mode != 1 && f.debug_mode != 9;
+	const bool v3h = !fc->H_inv && fc->out_H && !fc->dL_dpix_image && fc->columns == 4 && dm != 1 && dm != 9;
 	// the other out_H modes (11 columns and / or a per-view upstream-gradient image: GaussianObjectSLAM, the POp-GS probes) on
 	// records too, through the multi-view front end; FR_DEBUG_MODE=22 keeps round 2's two-pass kernel (k_fisher_tile_v2) for A/B runs
 	const bool multi_fe = p.vis_list != nullptr && p.T <= FR_MAX_LDS_TILES;
-	const bool v3g = !fc->H_inv && fc->out_H && !v3h && multi_fe && !g->cov3D_precomp && f.debug_mode != 1 && f.debug_mode != 9 && f.debug_mode != 22 && f.debug_mode != 19;
+	const bool v3g = !fc->H_inv && fc->out_H && !v3h && multi_fe && !g->cov3D_precomp && dm != 1 && dm != 9 && dm != 22 && dm != 19;
 	// compact records with the multi-view front end (the same condition fr_bin_pipeline uses for it); FR_DEBUG_MODE=19: dense (A/B runs)
-	const bool compact = (v3 || v3h || v3g) && multi_fe && f.debug_mode != 19;
-	// fixed key segments are filled by the compact-record front end only (FR_DEBUG_MODE 8 / 24: tile kernels that do not read the keys'
-	// strip bits; 20: the parking form of the projection kernel, which fills packed lists only)
-	if (compact && f.debug_mode != 8 && f.debug_mode != 24 && f.debug_mode != 20) fr_plan_fixed_segments(p, fc->tile_capacity);
+	const bool compact = (v3 || v3h || v3g) && multi_fe && dm != 19;
+	// fixed key segments are filled by the compact-record front end only
+	if (compact) fr_plan_fixed_segments(p, fc->tile_capacity);
 	else p.tile_cap = 0;
 	// float4 per record: the general out_H forms 13 / 7, the score form 5 with fixed key segments (80 bytes: FrRecStride), else 6
 	const int rstride = v3g ? (fc->columns == 11 ? 13 : 7) : ((v3 && p.tile_cap) ? 5 : 6);
@@ -8370,7 +7625,7 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
 	plan.ra.H_inv = fc->H_inv; plan.ra.hinv_stride = fc->H_inv_view_stride;
 	// the early frustum test needs a positive semi-definite cov3D: the one k_cov3d builds, not a caller's precomputed one;
 	// FR_DEBUG_MODE=15 switches it off (A/B runs)
-	plan.ra.early = (g->cov3D_precomp || f.debug_mode == 15) ? 0 : 1;
+	plan.ra.early = (g->cov3D_precomp || dm == 15) ? 0 : 1;
 	if (!compact)
 	{
 		// dense records: [V][P] splat records and [V][P] x 64 B behind them
@@ -8684,7 +7939,7 @@ extern "C" int fr_fisher_point_views(const fr_raster_cfg* cfg, const fr_gaussian
 	memset(&f, 0, sizeof(f));
 	f.dL = fc->dL_dpix;
 	f.tile_scores = (float*)(ws + L.tile_scores);
-	f.debug_mode = fr_debug_mode();
+	FR_RIG_ARGS(f)
 	fr_wire_records(plan, f, L, ws, rstride, true);
 	plan.ra.H_inv = fc->H_inv; plan.ra.hinv_stride = fc->H_inv_view_stride;
 	plan.ra.slot_acc = slot_acc;

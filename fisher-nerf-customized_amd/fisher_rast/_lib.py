@@ -257,7 +257,7 @@ _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_action.hip", "fr_action_object.hip", "fr_goal.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_eval.hip", "fr_objloss.hip", "fr_math.h",
+SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_action.hip", "fr_action_object.hip", "fr_goal.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_eval.hip", "fr_objloss.hip", "fr_math.h", "fr_rig.inc",
                                                   "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_action_math.h", "fr_action_object_math.h", "fr_goal_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_eval_math.h", "fr_objloss_math.h", "fr_internal.h", "fr_block.h", "fr_ssim_tile.h")] + \
           [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 

@@ -189,7 +189,8 @@ def test_product_never_imports_oracle():
 def test_product_library_is_not_the_experiment_rig(lib):
     """The library build() produces reads NO environment variable (no getenv import) and holds only kernels a default call can reach:
     the A/B generations (rolling-window walk, 8 x 8 pixel blocks, the 25-leaf two-pass kernel, round 1's compositing and sort
-    forms, the parking projection kernels) exist in -DFR_AB builds only (tools/build_variant.sh -> tools/_build/)."""
+    forms, the parking projection kernels) are retired from the source as well; what is left of the rig (csrc/fr_rig.inc: host
+    switches, loop statistics, ablations) exists in -DFR_AB builds only (tools/build_variant.sh -> tools/_build/)."""
     import subprocess
     import sys
     from fisher_rast import _lib
@@ -209,6 +210,16 @@ def test_product_library_is_not_the_experiment_rig(lib):
     src = open(os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", "fisher_rast.hip")).read()
     outside = re.sub(r"#ifdef FR_AB\b.*?#e(?:ndif|lse)", "", src, flags=re.S)
     assert "getenv" not in outside and "getenv" not in open(os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", "fisher_occ.hip")).read()
+    # the rig's header (always included) reads the environment inside `#ifdef FR_AB` only
+    rig = open(os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", "fr_rig.inc")).read()
+    assert "getenv" in rig and "getenv" not in re.sub(r"#ifdef FR_AB\b.*?#e(?:ndif|lse)", "", rig, flags=re.S)
+    # the kernels carry single-line hooks of the rig, never a preprocessor block of it ...
+    assert not re.search(r"#\s*(?:ifdef|ifndef|if\s+defined|if\s+!\s*defined|elif)\b[^\n]*\bFR_(?:LOOPSTATS|ABLATE|FWD_STATS)\b", src)
+    # ... and the generations that only a rig switch selected are gone from the source, not just from the binary
+    for retired in (r"k_fisher_tile_v3w", r"k_fisher_tile_v3<\s*8", r"k_fisher_tile_v3<\s*16,\s*4,\s*true", r"k_fisher_tile_v2<\s*25", r"k_pack_static<\s*25",
+                    r"k_render_forward\b(?!_walk)", r"k_backward_lin_tile<\s*false", r"k_backward_lin_walk<\s*true", r"k_preprocess_views<\s*-?(?:4|11|RC)\b",
+                    r"legacy_sort"):
+        assert not re.search(retired, src), retired
     for py in ("ops.py", "_lib.py", "distributed.py", "path_eval.py"):
         txt = open(os.path.join(ROOT, "fisher-nerf-customized_amd", "fisher_rast", py)).read()
         for var in ("FR_DEBUG_MODE", "FR_STREAMS", "FR_TILE_CAPACITY", "FR_GROUPS", "FR_GV", "FR_VC"):

@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B of the rig's environment switches on one box: ab_env.sh <rounds> "VAR=val" ...  (the switches exist in -DFR_AB builds only:
+# A/B of the rig's environment switches on one box: ab_env.sh <rounds> "VAR=val" ...  (FR_DEBUG_MODE and the FR_GV / FR_VC / ... knobs, listed in
+# csrc/fr_rig.inc; they exist in -DFR_AB builds only; FR_LOOPSTATS_MODE / FR_ABLATE_MODE belong to tools/loopstats.py / fe_ablate.py and their builds:
 # tools/build_variant.sh rig, then FISHER_RAST_SO=tools/_build/ab_rig.so is set here)
 rounds=$1; shift
 export FISHER_RAST_SO="${FISHER_RAST_SO:-$PWD/tools/_build/ab_rig.so}"

@@ -1,12 +1,13 @@
 """tools/fe_ablate.py (GPU box): what the direct key scatter inside k_preprocess_views_c costs, by leaving parts of it out.
-A -DFR_ABLATE build of the library (tools/_build/, never the package directory) with FR_DEBUG_MODE
+A -DFR_ABLATE build of the library (tools/_build/, never the package directory) with FR_ABLATE_MODE (the rig's own variable;
+FR_DEBUG_MODE, the host switches, is left alone)
     30 = everything, 31 = no key sweep, 32 = the sweep without the key stores, 33 = synthetic list entries (no list loads, no stores),
     34 = no range claims (no global atomics), 35 = phase A only (frustum test + survivor lists), 36 = phases A + B (no records, no list
     entries), 37 = all phases, every record written to the same few cache lines (the arithmetic without its HBM traffic);
 every mode raises the overflow flag so that the kernels behind the scan return at once -- the time of one launch is the front end's.
 `--outh` / `--point`: the out_H launch of 16 keyframes / the per-Gaussian scores of 64 views with modes 0, 28 (no global atomics), 29 (no
 LDS atomics either).
-One child process per mode (FR_DEBUG_MODE is read once per process)."""
+One child process per mode (FR_ABLATE_MODE is read once per process)."""
 import os
 import subprocess
 import sys
@@ -18,7 +19,7 @@ CSRC = os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc")
 
 def build():
     srcs = [os.path.join(CSRC, f) for f in ("fisher_rast.hip", "fisher_occ.hip")]
-    deps = srcs + [os.path.join(CSRC, "fr_math.h")]
+    deps = srcs + [os.path.join(CSRC, "fr_math.h"), os.path.join(CSRC, "fr_rig.inc")]
     if os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in deps):
         return
     os.makedirs(os.path.dirname(SO), exist_ok=True)
@@ -89,5 +90,5 @@ if __name__ == "__main__":
         outh = [a for a in ("--outh", "--point") if a in sys.argv]
         modes = [int(a) for a in sys.argv[1:] if a not in ("--outh", "--point")] or ([0, 28, 29] if outh else [30, 31, 32, 33, 34, 35, 36, 37])
         for m in modes:
-            env = dict(os.environ, FR_DEBUG_MODE=str(m), FISHER_RAST_SO=SO)
+            env = dict(os.environ, FR_ABLATE_MODE=str(m), FISHER_RAST_SO=SO)
             subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", str(m)] + outh, env=env)

@@ -1,7 +1,8 @@
 """tools/loopstats.py (GPU box): loop-trip counters / s_memtime shares of k_fisher_tile_v3 on the bench workload, from a
 -DFR_LOOPSTATS build of the library that is compiled ON DEMAND into tools/_build/ (never into the package directory) and loaded
-through FISHER_RAST_SO.  One child process per mode (FR_DEBUG_MODE is read once per process):
-    python tools/loopstats.py            -> modes 2..7 and 10..12 (fisher_rast.hip: k_fisher_tile_v3, FR_LOOPSTATS)
+through FISHER_RAST_SO.  One child process per mode (FR_LOOPSTATS_MODE, the rig's own variable, is read once per process; FR_DEBUG_MODE,
+the host switches, is left alone):
+    python tools/loopstats.py            -> modes 2..7 and 10..12 (fr_rig.inc: FrLoopStats::walk_result)
     python tools/loopstats.py 4 5        -> only these
 Mode 4 = wave-level walk iterations, 5 = contributing (pixel, splat) pairs, 6 = lane-level walk steps, 2 = candidates, 3 = chunks,
 7 = steps of the busiest lane, 10 / 11 / 12 = s_memtime ticks (/64) of the key stream / chunk set-up / walk."""
@@ -16,7 +17,7 @@ CSRC = os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc")
 
 def build():
     srcs = [os.path.join(CSRC, f) for f in ("fisher_rast.hip", "fisher_occ.hip")]
-    deps = srcs + [os.path.join(CSRC, "fr_math.h")]
+    deps = srcs + [os.path.join(CSRC, "fr_math.h"), os.path.join(CSRC, "fr_rig.inc")]
     if os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in deps):
         return
     os.makedirs(os.path.dirname(SO), exist_ok=True)
@@ -49,5 +50,5 @@ if __name__ == "__main__":
         build()
         modes = [int(a) for a in sys.argv[1:]] or [2, 3, 4, 5, 6, 7, 10, 11, 12]
         for m in modes:
-            env = dict(os.environ, FR_DEBUG_MODE=str(m), FISHER_RAST_SO=SO)
+            env = dict(os.environ, FR_LOOPSTATS_MODE=str(m), FISHER_RAST_SO=SO)
             subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", str(m)], env=env)

@@ -47,7 +47,7 @@ if len(sys.argv) > 3:
     out["contributing_pairs_per_step"] = int(float(sys.argv[2]))
     out["walk_iterations_per_step"] = int(float(sys.argv[3]))
     out["loop_stats_note"] = ("(pixel, splat) pairs that pass every test of forward.cu:338-363 and wave-level walk iterations of one "
-                              "64-view step, counted by a -DFR_LOOPSTATS build (tools/loopstats.py, FR_DEBUG_MODE 5 and 4)")
+                              "64-view step, counted by a -DFR_LOOPSTATS build (tools/loopstats.py, FR_LOOPSTATS_MODE 5 and 4)")
 json.dump(out, open(os.path.join(ROOT, "profiles", "pmc_k_fisher_tile_v4.json"), "w"), indent=1)
 for f in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"{tag}_pmc_*.txt"))):
     shutil.copy(f, os.path.join(ROOT, "profiles", os.path.basename(f)))
