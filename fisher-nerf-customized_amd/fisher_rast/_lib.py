@@ -1,6 +1,6 @@
 """ctypes binding of libfisher_rast.so (C ABI declared in include/fisher_rast.h).
 
-The library is built in-tree by `__graft_entry__.build()` (hipcc --offload-arch=gfx950).  There is no
+The library is built in-tree by `__graft_entry__.build()` (hipcc for gfx950, HIPCC_FLAGS there).  There is no
 CPU fallback: if the shared object is missing, loading raises and every op of the package fails loudly.
 """
 import ctypes
@@ -227,46 +227,140 @@ FR_ACTION_MAX_QUEUE = 128
 FR_ACTION_OBJECT_MAX = 200
 
 
-# every symbol include/fisher_rast.h and include/fisher_occ.h declare
-EXPORTS = (
-    "fr_version", "fr_last_error", "fr_build_id", "fr_init", "fr_fisher_workspace_layout", "fr_fisher_part_list_offset", "fr_workspace_bytes", "fr_workspace_layout", "fr_mark_visible",
-    "fr_forward", "fr_backward", "fr_backward_scratch_bytes", "fr_backward_ws", "fr_forward_pair", "fr_forward_features", "fr_backward_pair", "fr_backward_pair_scratch_bytes", "fr_backward_pair_ws", "fr_fisher_workspace_bytes", "fr_fisher_views",
-    "fr_fisher_pose_workspace_bytes", "fr_fisher_pose_workspace_layout", "fr_fisher_pose_views",
-    "fr_render_views_workspace_bytes", "fr_render_views_workspace_layout", "fr_render_views",
-    "fr_fisher_point_workspace_bytes", "fr_fisher_point_workspace_layout", "fr_fisher_point_views",
-    "fr_popgs_diag_criterion_workspace_bytes", "fr_popgs_diag_criterion",
-    "fr_image_loss_workspace_bytes", "fr_image_loss_forward", "fr_image_loss_backward",
-    "fr_frame_ingest_workspace_bytes", "fr_frame_ingest_select", "fr_frame_ingest_emit",
-    "fr_map_edit_workspace_bytes", "fr_map_edit_plan", "fr_map_edit_apply", "fr_map_edit_split_children", "fr_adam_step",
-    "fr_rendervar_workspace_bytes", "fr_rendervar_forward", "fr_rendervar_backward",
-    "fr_keyframe_valid_pixels_workspace_bytes", "fr_keyframe_overlap_workspace_bytes", "fr_keyframe_valid_pixels", "fr_keyframe_overlap",
-    "fr_densify_stats", "fr_densify_masks", "fr_prune_mask", "fr_knn_workspace_bytes", "fr_knn_dist2", "fr_spatial_order_workspace_bytes", "fr_spatial_order", "fr_profile_enable", "fr_profile_fetch",
-    "fr_occ_workspace_bytes", "fr_occ_update", "fr_occ_freespace", "fr_occ_frontiers", "fr_occ_erode", "fr_occ_cells_of",
-    "fr_occ_ring_candidates", "fr_occ_free_candidates",
-    "fr_plan_workspace_bytes", "fr_plan_round_cap", "fr_plan_grid", "fr_plan_tiers", "fr_plan_field", "fr_plan_paths",
-    "fr_plan_actions", "fr_rollout_actions", "fr_plan_actions_object",
-    "fr_occ_object_cells", "fr_occ_grid_candidates",
-    "fr_cloud_index_bytes", "fr_cloud_index_workspace_bytes", "fr_cloud_query_workspace_bytes", "fr_cloud_index_build", "fr_cloud_query",
-    "fr_dbscan_workspace_bytes", "fr_target_select_workspace_bytes", "fr_dbscan", "fr_target_select",
-    "fr_view_metrics_workspace_bytes", "fr_view_metrics", "fr_view_metrics_summary",
-    "fr_loss_mask_workspace_bytes", "fr_loss_mask", "fr_bg_penalty_workspace_bytes", "fr_bg_penalty_forward", "fr_bg_penalty_backward",
-    "fr_outside_mask_workspace_bytes", "fr_outside_mask",
-)
+def _prototypes():
+    """{name: (restype, argtypes)} of every symbol include/fisher_rast.h and include/fisher_occ.h declare (tests/test_prototypes_cpu.py
+    holds each row against its declaration); argtypes None = declared (void), left unset"""
+    ci, cs, i32, i64, u32, sz = ctypes.c_int, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_size_t
+    f32, f64, vp, fp, P = ctypes.c_float, ctypes.c_double, ctypes.c_void_p, _f32p, ctypes.POINTER
+    rc, gs, fc, occ = P(RasterCfg), P(Gaussians), P(FisherCfg), P(OccCfg)
+    back = [rc, gs, vp, vp, vp, vp, fp, i32] + [fp] * 9                  # fr_backward and fr_backward_ws up to the gradients
+    back_pair = [rc, gs, vp, vp, vp, vp, fp, fp, fp] + [fp] * 10         # the same of the pair forms
+    own_ws = [i64, vp, sz, vp]                                           # the *_ws tail: capacity, workspace, bytes, stream
+    return {
+        "fr_version": (ci, None),
+        "fr_last_error": (cs, None),
+        "fr_build_id": (cs, None),
+        "fr_init": (ci, None),
+        "fr_fisher_workspace_layout": (ci, [i32, i32, i32, i32, i64, i32, P(sz)]),
+        "fr_fisher_part_list_offset": (ci, [i32, i32, i32, i32, i64, i32, P(sz)]),
+        "fr_workspace_bytes": (ci, [i32, i32, i32, i64, P(sz)]),
+        "fr_workspace_layout": (ci, [i32, i32, i32, i64, P(sz)]),
+        "fr_mark_visible": (ci, [i32, fp, fp, fp, vp, vp]),
+        "fr_forward": (ci, [rc, gs, vp, vp, i64, vp, fp, fp, vp, vp, vp]),
+        "fr_backward": (ci, back + [vp]),
+        "fr_backward_scratch_bytes": (sz, [i32] * 4 + [i64]),
+        "fr_backward_ws": (ci, back + own_ws),
+        "fr_forward_pair": (ci, [rc, gs, fp, vp, vp, i64, vp, fp, fp, fp, vp, vp, vp]),
+        "fr_forward_features": (ci, [rc, fp, vp, vp, vp, fp, vp]),
+        "fr_backward_pair": (ci, back_pair + [vp]),
+        "fr_backward_pair_scratch_bytes": (sz, [i32] * 3 + [i64]),
+        "fr_backward_pair_ws": (ci, back_pair + own_ws),
+        "fr_fisher_workspace_bytes": (sz, [i32, i32, i32, i32, i64, i32]),
+        "fr_fisher_views": (ci, [rc, gs, fc, vp, sz, i64, vp, vp]),
+        "fr_fisher_pose_workspace_bytes": (sz, [i32] * 4 + [i64]),
+        "fr_fisher_pose_workspace_layout": (ci, [i32] * 4 + [i64, P(sz)]),
+        "fr_fisher_pose_views": (ci, [rc, gs, fc, fp, vp, sz, i64, vp, vp]),
+        "fr_render_views_workspace_bytes": (sz, [i32] * 4 + [i64]),
+        "fr_render_views_workspace_layout": (ci, [i32] * 4 + [i64, P(sz)]),
+        "fr_render_views": (ci, [rc, gs, fc, fp, fp, fp, fp, vp, sz, i64, vp, vp]),
+        "fr_fisher_point_workspace_bytes": (sz, [i32] * 4 + [i64, i32]),
+        "fr_fisher_point_workspace_layout": (ci, [i32] * 4 + [i64, i32, P(sz)]),
+        "fr_fisher_point_views": (ci, [rc, gs, fc, fp, fp, vp, sz, i64, vp, vp]),
+        "fr_popgs_diag_criterion_workspace_bytes": (sz, [i32, i64]),
+        "fr_popgs_diag_criterion": (ci, [i32, i32, i64, fp, fp, i64, fp, vp, vp, f32, i32, vp, vp, sz, vp]),
+        "fr_image_loss_workspace_bytes": (sz, [i32] * 3),
+        "fr_image_loss_forward": (ci, [P(ImageLossCfg), fp, fp, vp, fp, fp, fp, fp, vp, sz, vp]),
+        "fr_image_loss_backward": (ci, [P(ImageLossCfg), fp, fp, vp, fp, fp, fp, vp]),
+        "fr_frame_ingest_workspace_bytes": (sz, [i32] * 3),
+        "fr_frame_ingest_select": (ci, [P(FrameIngestCfg), fp, fp, vp, vp, vp, sz, vp]),
+        "fr_frame_ingest_emit": (ci, [P(FrameIngestCfg), fp, fp, fp, vp, i32, i64] + [fp] * 6 + [vp]),
+        "fr_map_edit_workspace_bytes": (sz, [i32]),
+        "fr_map_edit_plan": (ci, [i32] + [vp] * 5 + [sz, vp]),
+        "fr_map_edit_apply": (ci, [P(MapEditArray)] + [i32] * 6 + [vp, vp]),
+        "fr_map_edit_split_children": (ci, [i32] * 3 + [fp] * 4 + [vp]),
+        "fr_adam_step": (ci, [P(AdamArray), i32, vp]),
+        "fr_rendervar_workspace_bytes": (sz, [i32]),
+        "fr_rendervar_forward": (ci, [P(RenderVarCfg), vp]),
+        "fr_rendervar_backward": (ci, [P(RenderVarCfg), vp, sz, vp]),
+        "fr_keyframe_valid_pixels_workspace_bytes": (sz, [i32] * 2),
+        "fr_keyframe_overlap_workspace_bytes": (sz, [i32]),
+        "fr_keyframe_valid_pixels": (ci, [i32, i32, fp, vp, vp, vp, vp, sz, vp]),
+        "fr_keyframe_overlap": (ci, [P(KeyframeCfg), fp, vp, vp, fp, vp, vp, vp, fp, vp, vp, sz, vp]),
+        "fr_densify_stats": (ci, [i32, vp, fp, fp, fp, fp, vp, vp]),
+        "fr_densify_masks": (ci, [i32, fp, fp, fp, i32, f32, f32, f32, vp, vp, vp]),
+        "fr_prune_mask": (ci, [i32, fp, fp, i32, f32, f32, vp, vp]),
+        "fr_knn_workspace_bytes": (sz, [i32]),
+        "fr_knn_dist2": (ci, [i32, fp, fp, vp, sz, vp]),
+        "fr_spatial_order_workspace_bytes": (sz, [i32]),
+        "fr_spatial_order": (ci, [i32, fp, vp, vp, sz, vp]),
+        "fr_profile_enable": (ci, [ci]),
+        "fr_profile_fetch": (ci, [P(f32), ci]),
+        "fr_occ_workspace_bytes": (sz, [occ]),
+        "fr_occ_update": (ci, [occ, fp, i32, i32, i32, P(f32 * 4), P(f32 * 16), P(f32), i32, i32, i32, fp, vp, sz, vp]),
+        "fr_occ_freespace": (ci, [occ, fp, fp, i32, vp, vp, sz, vp]),
+        "fr_occ_frontiers": (ci, [occ, fp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, sz, vp]),
+        "fr_occ_erode": (ci, [occ, vp, vp, i32, vp]),
+        "fr_occ_cells_of": (ci, [occ, fp, i32, vp, vp]),
+        "fr_occ_ring_candidates": (ci, [occ, fp, i32, i32, f32, f32, f32, u32, vp, i32, fp, vp, vp]),
+        "fr_occ_free_candidates": (ci, [occ, vp, f32, u32, fp, i32, vp, vp, sz, vp]),
+        "fr_plan_workspace_bytes": (sz, [occ]),
+        "fr_plan_round_cap": (i32, [occ]),
+        "fr_plan_grid": (ci, [occ, fp, fp, i32, f32, i32, i32, vp, vp, vp, sz, vp]),
+        "fr_plan_tiers": (ci, [occ, vp, vp, vp]),
+        "fr_plan_field": (ci, [occ, vp, i32, i32, vp, vp, P(i32 * 2), vp, sz, vp]),
+        "fr_plan_paths": (ci, [occ, vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp]),
+        "fr_plan_actions": (ci, [occ, vp, i32, vp, vp, vp, i32, P(f64), f64, f64, f64, i32, f64] + [vp] * 7),
+        "fr_rollout_actions": (ci, [P(f64), vp, vp, i32, i32, f64, f64, vp, vp, vp]),
+        "fr_plan_actions_object": (ci, [occ, vp, i32, vp, vp, vp, i32, P(f64), f64, f64, f64, f64] + [vp] * 9),
+        "fr_occ_object_cells": (ci, [occ, vp, i32, i32, vp, i32, vp, vp, sz, vp]),
+        "fr_occ_grid_candidates": (ci, [occ, vp, i32, vp, vp, i32, f32, f32, i32, i32, i32, f32, u32, vp, i32, vp, vp, vp]),
+        "fr_cloud_index_bytes": (sz, [i32]),
+        "fr_cloud_index_workspace_bytes": (sz, [i32]),
+        "fr_cloud_query_workspace_bytes": (sz, [i32]),
+        "fr_cloud_index_build": (ci, [i32, fp, vp, sz, vp, sz, vp]),
+        "fr_cloud_query": (ci, [vp, sz, i32, P(CloudQueryCfg), vp, sz, vp]),
+        "fr_dbscan_workspace_bytes": (sz, [i32]),
+        "fr_target_select_workspace_bytes": (sz, [i32]),
+        "fr_dbscan": (ci, [i32, fp, f32, i32, vp, vp, vp, sz, vp]),
+        "fr_target_select": (ci, [i32, fp, fp, f32, f32, f32, f32, i32] + [vp] * 7 + [sz, vp]),
+        "fr_view_metrics_workspace_bytes": (sz, [i32] * 3),
+        "fr_view_metrics": (ci, [P(ViewMetricsCfg)] + [vp] * 8 + [sz, vp]),
+        "fr_view_metrics_summary": (ci, [vp, i32, vp, vp]),
+        "fr_loss_mask_workspace_bytes": (sz, [i32] * 2),
+        "fr_loss_mask": (ci, [P(LossMaskCfg), fp, fp] + [vp] * 4 + [sz, vp]),
+        "fr_bg_penalty_workspace_bytes": (sz, [i32] * 2),
+        "fr_bg_penalty_forward": (ci, [i32, i32, f32, f32, fp, fp, vp, fp, fp, vp, sz, vp]),
+        "fr_bg_penalty_backward": (ci, [i32, i32, f32, f32, fp, fp, vp, fp, fp, fp, fp, vp]),
+        "fr_outside_mask_workspace_bytes": (sz, [i32]),
+        "fr_outside_mask": (ci, [i32, i32, fp, fp, fp, fp, vp, i32, i32, vp, vp, vp, sz, vp]),
+    }
+
+
+PROTOTYPES = _prototypes()
+EXPORTS = tuple(PROTOTYPES)
 
 _lib = None
 
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-SOURCES = [os.path.join(_CSRC, n) for n in ("fisher_rast.hip", "fisher_occ.hip", "fr_popgs.hip", "fr_loss.hip", "fr_ingest.hip", "fr_mapedit.hip", "fr_adam.hip", "fr_rendervar.hip", "fr_keyframe.hip", "fr_plan.hip", "fr_action.hip", "fr_action_object.hip", "fr_goal.hip", "fr_cloud.hip", "fr_cluster.hip", "fr_eval.hip", "fr_objloss.hip", "fr_math.h", "fr_rig.inc",
-                                                  "fr_loss_math.h", "fr_ingest_math.h", "fr_mapedit_math.h", "fr_adam_math.h", "fr_rendervar_math.h", "fr_keyframe_math.h", "fr_plan_math.h", "fr_action_math.h", "fr_action_object_math.h", "fr_goal_math.h", "fr_cloud_math.h", "fr_cluster_math.h", "fr_eval_math.h", "fr_objloss_math.h", "fr_internal.h", "fr_block.h", "fr_ssim_tile.h")] + \
-          [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
 
 
-def source_hash():
-    """sha256 (first 16 hex digits) over the kernel and header sources, or None when they are not beside the package."""
+def _in_csrc(*suffixes):
+    return sorted(os.path.join(_CSRC, n) for n in os.listdir(_CSRC) if n.endswith(suffixes)) if os.path.isdir(_CSRC) else []
+
+
+# the manifest: what is in csrc/ IS the library.  UNITS is what build() compiles, SOURCES what the build id is taken over.
+UNITS = _in_csrc(".hip")
+HEADERS = [os.path.join(_INCLUDE, n) for n in ("fisher_rast.h", "fisher_occ.h")]
+SOURCES = UNITS + _in_csrc(".h", ".inc") + HEADERS
+
+
+def source_hash(files=None):
+    """sha256 (first 16 hex digits) over the kernel and header sources (SOURCES, or `files` in their place), or None when they are
+    not beside the package."""
     import hashlib
     h = hashlib.sha256()
-    for f in SOURCES:
+    for f in (SOURCES if files is None else files):
         if not os.path.exists(f):
             return None
         h.update(open(f, "rb").read())
@@ -292,272 +386,19 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(SO_PATH)
     ab_build = "FISHER_RAST_SO" in os.environ          # an A/B partner may be an older build, without the newest entry points
-    for name in EXPORTS:
-        if not hasattr(lib, name) and not ab_build:
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if not hasattr(lib, name):
+            if ab_build:
+                continue
             raise FisherRastError(f"{SO_PATH} does not export {name}")
-    lib.fr_version.restype = ctypes.c_int
-    lib.fr_last_error.restype = ctypes.c_char_p
-    lib.fr_build_id.restype = ctypes.c_char_p
-    lib.fr_init.restype = ctypes.c_int
-    lib.fr_fisher_workspace_layout.restype = ctypes.c_int
-    lib.fr_fisher_workspace_layout.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
-    if hasattr(lib, "fr_fisher_part_list_offset"):
-        lib.fr_fisher_part_list_offset.restype = ctypes.c_int
-        lib.fr_fisher_part_list_offset.argtypes = lib.fr_fisher_workspace_layout.argtypes
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     # a stale or foreign binary must not pass for the sources beside it (FISHER_RAST_SO builds for A/B runs are exempt)
     want = source_hash()
     got = lib.fr_build_id().decode().split(":")[-1]
-    if "FISHER_RAST_SO" not in os.environ and want is not None and got != want:
+    if not ab_build and want is not None and got != want:
         raise FisherRastError(f"{SO_PATH} was built from other sources (build id {got}, sources {want}): "
                               "run `python -c \"import __graft_entry__ as g; g.build()\"`")
-    lib.fr_workspace_bytes.restype = ctypes.c_int
-    lib.fr_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                       ctypes.POINTER(ctypes.c_size_t)]
-    lib.fr_workspace_layout.restype = ctypes.c_int
-    lib.fr_workspace_layout.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                        ctypes.POINTER(ctypes.c_size_t)]
-    lib.fr_mark_visible.restype = ctypes.c_int
-    lib.fr_mark_visible.argtypes = [ctypes.c_int32, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.fr_forward.restype = ctypes.c_int
-    lib.fr_forward.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians),
-                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                               _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.fr_backward.restype = ctypes.c_int
-    lib.fr_backward.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.c_void_p,
-                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                _f32p, ctypes.c_int32] + [_f32p] * 9 + [ctypes.c_void_p]
-    lib.fr_backward_scratch_bytes.restype = ctypes.c_size_t
-    lib.fr_backward_scratch_bytes.argtypes = [ctypes.c_int32] * 4 + [ctypes.c_int64]
-    lib.fr_backward_ws.restype = ctypes.c_int
-    lib.fr_backward_ws.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.c_void_p,
-                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                   _f32p, ctypes.c_int32] + [_f32p] * 9 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.fr_forward_pair.restype = ctypes.c_int
-    lib.fr_forward_pair.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), _f32p,
-                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                    _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.fr_forward_features.restype = ctypes.c_int
-    lib.fr_forward_features.argtypes = [ctypes.POINTER(RasterCfg), _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        _f32p, ctypes.c_void_p]
-    lib.fr_backward_pair.restype = ctypes.c_int
-    lib.fr_backward_pair.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                     _f32p, _f32p, _f32p] + [_f32p] * 10 + [ctypes.c_void_p]
-    lib.fr_backward_pair_scratch_bytes.restype = ctypes.c_size_t
-    lib.fr_backward_pair_scratch_bytes.argtypes = [ctypes.c_int32] * 3 + [ctypes.c_int64]
-    lib.fr_backward_pair_ws.restype = ctypes.c_int
-    lib.fr_backward_pair_ws.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        _f32p, _f32p, _f32p] + [_f32p] * 10 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.fr_fisher_workspace_bytes.restype = ctypes.c_size_t
-    lib.fr_fisher_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                              ctypes.c_int64, ctypes.c_int32]
-    lib.fr_fisher_views.restype = ctypes.c_int
-    lib.fr_fisher_views.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians),
-                                    ctypes.POINTER(FisherCfg), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64,
-                                    ctypes.c_void_p, ctypes.c_void_p]
-    lib.fr_fisher_pose_workspace_bytes.restype = ctypes.c_size_t
-    lib.fr_fisher_pose_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
-    lib.fr_fisher_pose_workspace_layout.restype = ctypes.c_int
-    lib.fr_fisher_pose_workspace_layout.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                    ctypes.POINTER(ctypes.c_size_t)]
-    lib.fr_fisher_pose_views.restype = ctypes.c_int
-    lib.fr_fisher_pose_views.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.POINTER(FisherCfg), _f32p,
-                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
-    if hasattr(lib, "fr_render_views"):
-        lib.fr_render_views_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_render_views_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
-        lib.fr_render_views_workspace_layout.restype = ctypes.c_int
-        lib.fr_render_views_workspace_layout.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                         ctypes.POINTER(ctypes.c_size_t)]
-        lib.fr_render_views.restype = ctypes.c_int
-        lib.fr_render_views.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.POINTER(FisherCfg),
-                                        _f32p, _f32p, _f32p, _f32p,
-                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
-    if hasattr(lib, "fr_fisher_point_views"):
-        lib.fr_fisher_point_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_fisher_point_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                        ctypes.c_int32]
-        lib.fr_fisher_point_workspace_layout.restype = ctypes.c_int
-        lib.fr_fisher_point_workspace_layout.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                         ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
-        lib.fr_fisher_point_views.restype = ctypes.c_int
-        lib.fr_fisher_point_views.argtypes = [ctypes.POINTER(RasterCfg), ctypes.POINTER(Gaussians), ctypes.POINTER(FisherCfg), _f32p, _f32p,
-                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
-    if hasattr(lib, "fr_popgs_diag_criterion"):
-        lib.fr_popgs_diag_criterion_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_popgs_diag_criterion_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64]
-        lib.fr_popgs_diag_criterion.restype = ctypes.c_int
-        lib.fr_popgs_diag_criterion.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _f32p, _f32p, ctypes.c_int64, _f32p,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    if hasattr(lib, "fr_image_loss_forward"):
-        lib.fr_image_loss_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_image_loss_workspace_bytes.argtypes = [ctypes.c_int32] * 3
-        lib.fr_image_loss_forward.restype = ctypes.c_int
-        lib.fr_image_loss_forward.argtypes = [ctypes.POINTER(ImageLossCfg), _f32p, _f32p, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p,
-                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_image_loss_backward.restype = ctypes.c_int
-        lib.fr_image_loss_backward.argtypes = [ctypes.POINTER(ImageLossCfg), _f32p, _f32p, ctypes.c_void_p, _f32p, _f32p, _f32p, ctypes.c_void_p]
-    if hasattr(lib, "fr_frame_ingest_select"):
-        lib.fr_frame_ingest_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_frame_ingest_workspace_bytes.argtypes = [ctypes.c_int32] * 3
-        lib.fr_frame_ingest_select.restype = ctypes.c_int
-        lib.fr_frame_ingest_select.argtypes = [ctypes.POINTER(FrameIngestCfg), _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_frame_ingest_emit.restype = ctypes.c_int
-        lib.fr_frame_ingest_emit.argtypes = [ctypes.POINTER(FrameIngestCfg), _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_int32,
-                                             ctypes.c_int64] + [_f32p] * 6 + [ctypes.c_void_p]
-    if hasattr(lib, "fr_map_edit_plan"):
-        lib.fr_map_edit_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_map_edit_workspace_bytes.argtypes = [ctypes.c_int32]
-        lib.fr_map_edit_plan.restype = ctypes.c_int
-        lib.fr_map_edit_plan.argtypes = [ctypes.c_int32] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_map_edit_apply.restype = ctypes.c_int
-        lib.fr_map_edit_apply.argtypes = [ctypes.POINTER(MapEditArray)] + [ctypes.c_int32] * 6 + [ctypes.c_void_p, ctypes.c_void_p]
-        lib.fr_map_edit_split_children.restype = ctypes.c_int
-        lib.fr_map_edit_split_children.argtypes = [ctypes.c_int32] * 3 + [_f32p] * 4 + [ctypes.c_void_p]
-    if hasattr(lib, "fr_adam_step"):
-        lib.fr_adam_step.restype = ctypes.c_int
-        lib.fr_adam_step.argtypes = [ctypes.POINTER(AdamArray), ctypes.c_int32, ctypes.c_void_p]
-    if hasattr(lib, "fr_rendervar_forward"):
-        lib.fr_rendervar_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_rendervar_workspace_bytes.argtypes = [ctypes.c_int32]
-        lib.fr_rendervar_forward.restype = ctypes.c_int
-        lib.fr_rendervar_forward.argtypes = [ctypes.POINTER(RenderVarCfg), ctypes.c_void_p]
-        lib.fr_rendervar_backward.restype = ctypes.c_int
-        lib.fr_rendervar_backward.argtypes = [ctypes.POINTER(RenderVarCfg), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    if hasattr(lib, "fr_keyframe_overlap"):
-        lib.fr_keyframe_valid_pixels_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_keyframe_valid_pixels_workspace_bytes.argtypes = [ctypes.c_int32] * 2
-        lib.fr_keyframe_overlap_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_keyframe_overlap_workspace_bytes.argtypes = [ctypes.c_int32]
-        lib.fr_keyframe_valid_pixels.restype = ctypes.c_int
-        lib.fr_keyframe_valid_pixels.argtypes = [ctypes.c_int32, ctypes.c_int32, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_keyframe_overlap.restype = ctypes.c_int
-        lib.fr_keyframe_overlap.argtypes = [ctypes.POINTER(KeyframeCfg), _f32p, ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                            ctypes.c_void_p]
-    lib.fr_densify_stats.restype = ctypes.c_int
-    lib.fr_densify_stats.argtypes = [ctypes.c_int32, ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.fr_densify_masks.restype = ctypes.c_int
-    lib.fr_densify_masks.argtypes = [ctypes.c_int32, _f32p, _f32p, _f32p, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.fr_prune_mask.restype = ctypes.c_int
-    lib.fr_prune_mask.argtypes = [ctypes.c_int32, _f32p, _f32p, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
-    lib.fr_knn_workspace_bytes.restype = ctypes.c_size_t
-    lib.fr_knn_workspace_bytes.argtypes = [ctypes.c_int32]
-    lib.fr_knn_dist2.restype = ctypes.c_int
-    lib.fr_knn_dist2.argtypes = [ctypes.c_int32, _f32p, _f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.fr_spatial_order_workspace_bytes.restype = ctypes.c_size_t
-    lib.fr_spatial_order_workspace_bytes.argtypes = [ctypes.c_int32]
-    lib.fr_spatial_order.restype = ctypes.c_int
-    lib.fr_spatial_order.argtypes = [ctypes.c_int32, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.fr_profile_enable.restype = ctypes.c_int
-    lib.fr_profile_enable.argtypes = [ctypes.c_int]
-    lib.fr_profile_fetch.restype = ctypes.c_int
-    lib.fr_profile_fetch.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_int]
-    occp = ctypes.POINTER(OccCfg)
-    f4, f16 = ctypes.c_float * 4, ctypes.c_float * 16
-    lib.fr_occ_workspace_bytes.restype = ctypes.c_size_t
-    lib.fr_occ_workspace_bytes.argtypes = [occp]
-    lib.fr_occ_update.restype = ctypes.c_int
-    lib.fr_occ_update.argtypes = [occp, _f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(f4), ctypes.POINTER(f16),
-                                  ctypes.POINTER(ctypes.c_float), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f32p,
-                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.fr_occ_freespace.restype = ctypes.c_int
-    lib.fr_occ_freespace.argtypes = [occp, _f32p, _f32p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.fr_occ_frontiers.restype = ctypes.c_int
-    lib.fr_occ_frontiers.argtypes = [occp, _f32p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.fr_occ_erode.restype = ctypes.c_int
-    lib.fr_occ_erode.argtypes = [occp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-    lib.fr_occ_ring_candidates.restype = ctypes.c_int
-    lib.fr_occ_ring_candidates.argtypes = [occp, _f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int32, _f32p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.fr_occ_free_candidates.restype = ctypes.c_int
-    lib.fr_occ_free_candidates.argtypes = [occp, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint32, _f32p, ctypes.c_int32,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.fr_occ_cells_of.restype = ctypes.c_int
-    lib.fr_occ_cells_of.argtypes = [occp, _f32p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-    if hasattr(lib, "fr_plan_field"):
-        lib.fr_plan_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_plan_workspace_bytes.argtypes = [occp]
-        lib.fr_plan_round_cap.restype = ctypes.c_int32
-        lib.fr_plan_round_cap.argtypes = [occp]
-        lib.fr_plan_grid.restype = ctypes.c_int
-        lib.fr_plan_grid.argtypes = [occp, _f32p, _f32p, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_plan_tiers.restype = ctypes.c_int
-        lib.fr_plan_tiers.argtypes = [occp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        lib.fr_plan_field.restype = ctypes.c_int
-        lib.fr_plan_field.argtypes = [occp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.POINTER(ctypes.c_int32 * 2), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_plan_paths.restype = ctypes.c_int
-        lib.fr_plan_paths.argtypes = [occp, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                      ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-    if hasattr(lib, "fr_plan_actions"):
-        vp, i32, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double
-        f64p = ctypes.POINTER(ctypes.c_double)
-        lib.fr_plan_actions.restype = ctypes.c_int
-        lib.fr_plan_actions.argtypes = [occp, vp, i32, vp, vp, vp, i32, f64p, f64, f64, f64, i32, f64, vp, vp, vp, vp, vp, vp, vp]
-        lib.fr_rollout_actions.restype = ctypes.c_int
-        lib.fr_rollout_actions.argtypes = [f64p, vp, vp, i32, i32, f64, f64, vp, vp, vp]
-    if hasattr(lib, "fr_plan_actions_object"):
-        vp, i32, f64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_float
-        lib.fr_plan_actions_object.restype = ctypes.c_int
-        lib.fr_plan_actions_object.argtypes = [occp, vp, i32, vp, vp, vp, i32, ctypes.POINTER(ctypes.c_double), f64, f64, f64, f64] + [vp] * 9
-        lib.fr_occ_object_cells.restype = ctypes.c_int
-        lib.fr_occ_object_cells.argtypes = [occp, vp, i32, i32, vp, i32, vp, vp, ctypes.c_size_t, vp]
-        lib.fr_occ_grid_candidates.restype = ctypes.c_int
-        lib.fr_occ_grid_candidates.argtypes = [occp, vp, i32, vp, vp, i32, f32, f32, i32, i32, i32, f32, ctypes.c_uint32, vp, i32, vp, vp, vp]
-    if hasattr(lib, "fr_cloud_query"):
-        for f in (lib.fr_cloud_index_bytes, lib.fr_cloud_index_workspace_bytes, lib.fr_cloud_query_workspace_bytes):
-            f.restype = ctypes.c_size_t
-            f.argtypes = [ctypes.c_int32]
-        lib.fr_cloud_index_build.restype = ctypes.c_int
-        lib.fr_cloud_index_build.argtypes = [ctypes.c_int32, _f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_cloud_query.restype = ctypes.c_int
-        lib.fr_cloud_query.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.POINTER(CloudQueryCfg), ctypes.c_void_p, ctypes.c_size_t,
-                                       ctypes.c_void_p]
-    if hasattr(lib, "fr_target_select"):
-        for f in (lib.fr_dbscan_workspace_bytes, lib.fr_target_select_workspace_bytes):
-            f.restype = ctypes.c_size_t
-            f.argtypes = [ctypes.c_int32]
-        lib.fr_dbscan.restype = ctypes.c_int
-        lib.fr_dbscan.argtypes = [ctypes.c_int32, _f32p, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_target_select.restype = ctypes.c_int
-        lib.fr_target_select.argtypes = [ctypes.c_int32, _f32p, _f32p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                         ctypes.c_int32] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
-    if hasattr(lib, "fr_view_metrics"):
-        lib.fr_view_metrics_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_view_metrics_workspace_bytes.argtypes = [ctypes.c_int32] * 3
-        lib.fr_view_metrics.restype = ctypes.c_int
-        lib.fr_view_metrics.argtypes = [ctypes.POINTER(ViewMetricsCfg)] + [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_view_metrics_summary.restype = ctypes.c_int
-        lib.fr_view_metrics_summary.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-    if hasattr(lib, "fr_loss_mask"):
-        lib.fr_loss_mask_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_loss_mask_workspace_bytes.argtypes = [ctypes.c_int32] * 2
-        lib.fr_loss_mask.restype = ctypes.c_int
-        lib.fr_loss_mask.argtypes = [ctypes.POINTER(LossMaskCfg), _f32p, _f32p] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_bg_penalty_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_bg_penalty_workspace_bytes.argtypes = [ctypes.c_int32] * 2
-        lib.fr_bg_penalty_forward.restype = ctypes.c_int
-        lib.fr_bg_penalty_forward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _f32p, _f32p, ctypes.c_void_p,
-                                              _f32p, _f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib.fr_bg_penalty_backward.restype = ctypes.c_int
-        lib.fr_bg_penalty_backward.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _f32p, _f32p, ctypes.c_void_p,
-                                               _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p]
-        lib.fr_outside_mask_workspace_bytes.restype = ctypes.c_size_t
-        lib.fr_outside_mask_workspace_bytes.argtypes = [ctypes.c_int32]
-        lib.fr_outside_mask.restype = ctypes.c_int
-        lib.fr_outside_mask.argtypes = [ctypes.c_int32, ctypes.c_int32, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     _lib = lib
     return lib
 

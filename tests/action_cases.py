@@ -17,9 +17,9 @@ margin gets another seed here, in CASES.
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
+import harness_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MARGIN = 1e-9
@@ -266,16 +266,8 @@ def make_case(name):
 
 # ---- the g++ harness ------------------------------------------------------------------------------------------------------------------
 
-def harness_sources():
-    return [os.path.join(ROOT, "tests", "harness", "fr_action_harness.cpp"), os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", "fr_action_math.h")]
-
-
 def build_harness():
-    so = os.path.join(ROOT, "tests", "harness", "libfr_action_harness.so")
-    srcs = harness_sources()
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_action_harness", harness_build.EXACT))
     vp, ci, cf, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
     h.fra_h_max_queue.restype = ci
     h.fra_h_plan.argtypes = [ci, ci, cd, cf, cf, vp, ci, vp, vp, vp, ci, vp, cd, cd, cd, ci, vp, vp, vp, vp, vp, vp]

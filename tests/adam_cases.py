@@ -6,9 +6,9 @@ each correctly rounded in both, so it reproduces the header bit for bit (NaN pay
 for optim.HipAdamBackend: the g++ build of the header (tests/harness/fr_adam_harness.cpp) on CPU tensors; the bookkeeping Python
 above it (FusedAdam) is the product's own."""
 import ctypes
-import os
 
 import numpy as np
+import harness_build
 
 F = np.float32
 MAP_KEYS = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales")
@@ -139,15 +139,7 @@ def k_need(got, want64, terms):
 # ---- the g++ harness over csrc/fr_adam_math.h (tests/harness/fr_adam_harness.cpp) ------------------------------------------------
 
 def build_harness():
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdir = os.path.join(root, "tests", "harness")
-    so = os.path.join(hdir, "libfr_adam_harness.so")
-    srcs = [os.path.join(hdir, "fr_adam_harness.cpp"), os.path.join(root, "fisher-nerf-customized_amd", "csrc", "fr_adam_math.h"),
-            os.path.join(root, "include", "fisher_rast.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_adam_harness"))
     vp = ctypes.c_void_p
     h.fra_step.argtypes = [ctypes.c_longlong] + [vp] * 4 + [ctypes.c_float] * 6 + [ctypes.c_int]
     h.fra_step.restype = None

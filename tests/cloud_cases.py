@@ -8,9 +8,9 @@ reference's torch matmul orders its sums differently; the margins are 50 times t
 seeds until a case qualifies."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+import harness_build
 
 F = np.float32
 FAMILIES = ("uniform", "clusters", "outside", "plane", "point", "surface", "nonfinite")
@@ -208,12 +208,7 @@ GOLDEN_DEPTH = ((48, 64, "object", "-Z", 1), (47, 63, "object", "Z", 2), (47, 63
 # ---- the harness ----------------------------------------------------------------------------------------------------------------------
 
 def build_harness():
-    hdir = os.path.join(ROOT, "tests", "harness")
-    so = os.path.join(hdir, "libfr_cloud_harness.so")
-    srcs = [os.path.join(hdir, "fr_cloud_harness.cpp"), os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", "fr_cloud_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_cloud_harness"))
     vp = ctypes.c_void_p
     h.frc_h_dist2.argtypes = [vp, vp]
     h.frc_h_dist2.restype = ctypes.c_float

@@ -13,9 +13,9 @@ EQUAL.  For selection cases additionally no band score lies within 4 ulp of the 
 threshold IS a score and the strict comparison is exact)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+import harness_build
 
 F = np.float32
 EPS, MIN_SAMPLES = 0.1, 5
@@ -257,12 +257,7 @@ def qualifying_select_case(P=SELECT_P, kind="map"):
 # ---- the g++ harness --------------------------------------------------------------------------------------------------------------------
 
 def build_harness():
-    hdir = os.path.join(ROOT, "tests", "harness")
-    so = os.path.join(hdir, "libfr_cluster_harness.so")
-    srcs = [os.path.join(hdir, "fr_cluster_harness.cpp"), os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", "fr_cluster_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_cluster_harness"))
     vp, f32, i32, u32 = ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint32
     h.frk_h_eps_ok.argtypes, h.frk_h_eps_ok.restype = [f32], i32
     h.frk_h_dist2.argtypes, h.frk_h_dist2.restype = [vp, vp], f32

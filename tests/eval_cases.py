@@ -7,9 +7,9 @@ FAMILIES[(v + rot) % 7] -- so a wrong view stride shows as a wrong number.  A ta
 its float form is bytes / 255 in binary32, so the three target layouts state the same image."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+import harness_build
 
 SHAPES = [(1, 11, 11), (3, 5, 70), (5, 17, 33), (2, 16, 16)]
 FAMILIES = ["noise", "smooth", "step", "identical", "near", "out_of_range", "black_gt"]
@@ -175,13 +175,7 @@ def ulp_diff(a, b):
 
 def build_harness():
     """ctypes handle of the harness, built with the flags loss_cases.build_harness uses"""
-    hdir = os.path.join(ROOT, "tests", "harness")
-    so = os.path.join(hdir, "libfr_eval_harness.so")
-    csrc = os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc")
-    srcs = [os.path.join(hdir, "fr_eval_harness.cpp"), os.path.join(csrc, "fr_eval_math.h"), os.path.join(csrc, "fr_loss_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_eval_harness"))
     vp, ll = ctypes.c_void_p, ctypes.c_longlong
     h.fre_clamp_of.restype = ctypes.c_float
     h.fre_clamp_of.argtypes = [ctypes.c_float]

@@ -18,11 +18,11 @@ out below gets another seed here, in CASES.
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 
 from action_cases import FILL, Policy, compute_next_campos, ulp32, yaw_pose
+import harness_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MARGIN = 1e-9
@@ -418,18 +418,8 @@ def cells_to_world(cells, W, H, cell, center):
 
 # ---- the g++ harness ------------------------------------------------------------------------------------------------------------------
 
-def harness_sources():
-    csrc = os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc")
-    return [os.path.join(ROOT, "tests", "harness", "fr_goal_harness.cpp")] + [os.path.join(csrc, n) for n in ("fr_action_object_math.h", "fr_goal_math.h",
-                                                                                                                "fr_action_math.h")]
-
-
 def build_harness():
-    so = os.path.join(ROOT, "tests", "harness", "libfr_goal_harness.so")
-    srcs = harness_sources()
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_goal_harness", harness_build.EXACT))
     vp, ci, cf, cd, cu = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_uint32
     h.frg_h_object_max.restype = ci
     h.frg_h_plan_object.argtypes = [ci, ci, cd, cf, cf, vp, ci, vp, vp, vp, ci, vp, cd, cd, cd] + [vp] * 9

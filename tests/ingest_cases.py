@@ -5,11 +5,11 @@ header's operand order: every operation is one of + - x / sqrt, each correctly r
 for bit -- all but logf.  `torch_non_presence` / `torch_pointcloud` are the reference's chain (models/SLAM/gaussian.py:320-342,
 75-143: torch.median, max_pool2d, torch.inverse, matmul, boolean indexing) in this helper's own form, on any device and dtype.
 The g++ harness over the header (tests/harness/fr_ingest_harness.cpp) is bound here too."""
-import os
 
 import numpy as np
 
 import cameras
+import harness_build
 
 FAMILIES = ["half", "all", "none", "ties", "prefix-hi", "prefix-lo", "nan", "inf", "last-pixel", "pool-corner"]
 # (H, W, d): one pixel; odd n; a 2 x 2 pool; one workgroup exactly at three poolings; ragged workgroups; pooled 12 x 16; and several
@@ -257,14 +257,7 @@ def points_need(got, c, idx, transform_pts=True):
 
 def build_harness():
     import ctypes
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdir = os.path.join(root, "tests", "harness")
-    so = os.path.join(hdir, "libfr_ingest_harness.so")
-    srcs = [os.path.join(hdir, "fr_ingest_harness.cpp"), os.path.join(root, "fisher-nerf-customized_amd", "csrc", "fr_ingest_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_ingest_harness"))
     vp = ctypes.c_void_p
     h.fri_select.argtypes = [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [vp] * 7
     h.fri_select.restype = None

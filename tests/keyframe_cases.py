@@ -8,11 +8,11 @@ in NumPy as in the header, so it reproduces the g++ harness bit for bit; in bina
 reference's chain (torch.where, unique / isin, torch.inverse, matmul per keyframe, a sort of 0-dim tensors) in this helper's own
 form, on any device.  The g++ harness (tests/harness/fr_keyframe_harness.cpp) is bound here too, also as a backend of the product's
 KeyframeSelection, which has no CPU path of its own."""
-import os
 
 import numpy as np
 
 import cameras
+import harness_build
 
 # qualifying families may be compared with torch and the golden file once `qualifies` holds; the adversarial ones sit on the
 # decisions themselves (equal keys, thresholds) and are compared with the harness / the binary32 restatement only
@@ -305,15 +305,7 @@ def torch_chain(gt_depth, w2c, intrinsics, keyframes, k, curr_mask=None, pixels=
 
 def build_harness():
     import ctypes
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdir = os.path.join(root, "tests", "harness")
-    csrc = os.path.join(root, "fisher-nerf-customized_amd", "csrc")
-    so = os.path.join(hdir, "libfr_keyframe_harness.so")
-    srcs = [os.path.join(hdir, "fr_keyframe_harness.cpp"), os.path.join(csrc, "fr_keyframe_math.h"), os.path.join(csrc, "fr_ingest_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_keyframe_harness"))
     vp = ctypes.c_void_p
     h.frk_valid_pixels.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     h.frk_valid_pixels.restype = None

@@ -8,6 +8,7 @@ cases it equals the reference's binary64 run to 1e-12 (tests/test_image_loss_cpu
 import os
 
 import numpy as np
+import harness_build
 
 SHAPES = [(3, 11, 11), (3, 5, 70), (3, 17, 33), (1, 17, 33)]
 FAMILIES = ["noise", "smooth", "flat", "step", "identical"]
@@ -183,14 +184,7 @@ def loss64(x, y, mask, w_l1, w_ssim, denom, weights_map=False):
 def build_harness():
     """ctypes handle of the harness, built with the flags conftest.py uses for the other one"""
     import ctypes
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdir = os.path.join(root, "tests", "harness")
-    so = os.path.join(hdir, "libfr_loss_harness.so")
-    srcs = [os.path.join(hdir, "fr_loss_harness.cpp"), os.path.join(root, "fisher-nerf-customized_amd", "csrc", "fr_loss_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_loss_harness"))
     h.frl_sign_of.restype = ctypes.c_float
     h.frl_sign_of.argtypes = [ctypes.c_float]
     vp = ctypes.c_void_p

@@ -11,6 +11,7 @@ Adam state and statistics from the recorded arrays on any device, `snapshot` rea
 import os
 
 import numpy as np
+import harness_build
 
 F = np.float32
 MAP_KEYS = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales")
@@ -428,15 +429,7 @@ class NumpyBackend:
 
 def build_harness():
     import ctypes
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdir = os.path.join(root, "tests", "harness")
-    so = os.path.join(hdir, "libfr_mapedit_harness.so")
-    csrc = os.path.join(root, "fisher-nerf-customized_amd", "csrc")
-    srcs = [os.path.join(hdir, "fr_mapedit_harness.cpp"), os.path.join(csrc, "fr_mapedit_math.h"), os.path.join(csrc, "fr_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_mapedit_harness"))
     vp = ctypes.c_void_p
     h.frm_rotations.argtypes = [ctypes.c_int, vp, vp]
     h.frm_rotations.restype = None

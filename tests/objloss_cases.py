@@ -11,9 +11,9 @@ rotation, integer translation, means on multiples of 2^-6, power-of-two focal le
 in any order) and a general camera."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+import harness_build
 
 F = np.float32
 SHAPES = [(1, 1), (1, 7), (5, 7), (16, 16), (37, 53), (64, 65)]          # n odd and even, one pixel, more than one workgroup
@@ -304,13 +304,7 @@ def exp_is_correctly_rounded(logs):
 # ---- the g++ harness over csrc/fr_objloss_math.h (tests/harness/fr_objloss_harness.cpp) --------------------------------------------
 
 def build_harness():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdir = os.path.join(root, "tests", "harness")
-    so = os.path.join(hdir, "libfr_objloss_harness.so")
-    srcs = [os.path.join(hdir, "fr_objloss_harness.cpp"), os.path.join(root, "fisher-nerf-customized_amd", "csrc", "fr_objloss_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_objloss_harness"))
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     h.fro_loss_mask.argtypes = [ci, ci, cf, ci, cf, ci] + [vp] * 5
     h.fro_penalty_forward.argtypes = [ci, ci, cf, cf] + [vp] * 5

@@ -11,9 +11,9 @@ and the map families the tests run on.  Cells are (row, col) = (y, x); a family 
 import ctypes
 import heapq
 import os
-import subprocess
 
 import numpy as np
+import harness_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -412,16 +412,8 @@ FAMILIES = ("empty-room", "door-1", "door-3", "door-9", "serpentine", "two-route
 
 # ---- the g++ harness ----------------------------------------------------------------------------------------------------------------
 
-def harness_sources():
-    return [os.path.join(ROOT, "tests", "harness", "fr_plan_harness.cpp"), os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", "fr_plan_math.h")]
-
-
 def build_harness():
-    so = os.path.join(ROOT, "tests", "harness", "libfr_plan_harness.so")
-    srcs = harness_sources()
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_plan_harness", harness_build.EXACT))
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     h.frp_h_grid.argtypes = [ci, ci, vp, vp, ci, cf, cf, cf, cf, ci, ci, vp, vp]
     h.frp_h_grid.restype = None

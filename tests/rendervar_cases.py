@@ -8,11 +8,11 @@ autograd differentiates it.  `stages` evaluates every stage of the kernels' arit
 that stage's binary32 inputs, with the sum of the magnitudes of its terms; `HarnessBackend` is the CPU stand-in for
 rendervar.HipRenderVarBackend, the g++ build of the header (tests/harness/fr_rendervar_harness.cpp) on CPU tensors."""
 import ctypes
-import os
 
 import numpy as np
 import torch
 import torch.nn.functional as tF
+import harness_build
 
 F = np.float32
 EPS_N = 1e-12
@@ -330,16 +330,7 @@ def torch32_staged(inp, time_idx):
 # ---- the g++ harness over csrc/fr_rendervar_math.h (tests/harness/fr_rendervar_harness.cpp) -----------------------------------------
 
 def build_harness():
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdir = os.path.join(root, "tests", "harness")
-    so = os.path.join(hdir, "libfr_rendervar_harness.so")
-    csrc = os.path.join(root, "fisher-nerf-customized_amd", "csrc")
-    srcs = [os.path.join(hdir, "fr_rendervar_harness.cpp"), os.path.join(csrc, "fr_rendervar_math.h"), os.path.join(csrc, "fr_math.h"),
-            os.path.join(root, "include", "fisher_rast.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_rendervar_harness"))
     vp = ctypes.c_void_p
     h.frv_forward.argtypes = [vp]
     h.frv_forward.restype = None

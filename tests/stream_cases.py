@@ -295,8 +295,9 @@ def stream_run(case, ref, dev, stream=None, blocker_ms=BLOCKER_MS, null_stream=F
     return finish(enqueue(case, ref, dev, stream, blocker_ms, null_stream))
 
 
-def declared_exports():
-    """{name: parameter list} of every function that include/fisher_rast.h and include/fisher_occ.h declare, comments taken out"""
+def declared_exports(with_return=False):
+    """{name: parameter list} of every function that include/fisher_rast.h and include/fisher_occ.h declare, comments taken out;
+    with_return: {name: (return type, parameter list)}"""
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -306,8 +307,8 @@ def declared_exports():
             text = f.read()
         text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
         text = re.sub(r"//[^\n]*", " ", text)
-        for m in re.finditer(r"\b(fr_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", text):
-            found[m.group(1)] = m.group(2)
+        for m in re.finditer(r"([A-Za-z_][\w \t*]*?)\s*\b(fr_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", text):
+            found[m.group(2)] = (" ".join(m.group(1).split()), m.group(3)) if with_return else m.group(3)
     return found
 
 

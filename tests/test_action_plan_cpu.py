@@ -5,7 +5,6 @@ the roll-out against the planner and against path_eval's host roll-out; the stan
 undefined-behaviour sanitizers; the ABI's rejections, which need no device; the Python wrappers' host logic on a stand-in library."""
 import ctypes
 import os
-import subprocess
 import types
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 import torch
 
 import action_cases as ac
+import harness_build
 
 
 @pytest.fixture(scope="module")
@@ -121,21 +121,17 @@ def test_the_families_sit_on_their_decisions(harness):
 
 def test_harness_program_under_sanitizers(tmp_path):
     """the stand-alone program (its own main) over the same header, under -fsanitize=address,undefined"""
-    exe = str(tmp_path / "fr_action_harness_asan")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-DFRA_HARNESS_MAIN", "-o", exe, ac.harness_sources()[0]])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    r = harness_build.sanitized_program("fr_action_harness", "FRA_HARNESS_MAIN", tmp_path)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "checksum" in r.stdout and not r.stderr.strip()
 
 
 def test_sources_exports_and_header(harness):
     from fisher_rast import _lib
-    assert any(s.endswith("fr_action.hip") for s in _lib.SOURCES) and any(s.endswith("fr_action_math.h") for s in _lib.SOURCES)
+    assert os.path.join(_lib._CSRC, "fr_action.hip") in _lib.UNITS and os.path.join(_lib._CSRC, "fr_action_math.h") in _lib.SOURCES
     header = open(os.path.join(ac.ROOT, "include", "fisher_occ.h")).read()
     for name in ("fr_plan_actions", "fr_rollout_actions"):
         assert name in _lib.EXPORTS and name + "(" in header
-    assert '"fr_action.hip"' in open(os.path.join(ac.ROOT, "__graft_entry__.py")).read()
     assert f"#define FR_ACTION_MAX_QUEUE {_lib.FR_ACTION_MAX_QUEUE}" in header and _lib.FR_ACTION_MAX_QUEUE == harness.fra_h_max_queue() >= 64
     src = open(os.path.join(ac.ROOT, "fisher-nerf-customized_amd", "csrc", "fr_action.hip")).read()
     assert "hipMalloc" not in src and "hipMemcpy" not in src and "Synchronize" not in src and "getenv" not in src

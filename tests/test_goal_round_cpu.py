@@ -6,12 +6,12 @@ grid's tables against their NumPy restatements; the stand-alone harness program 
 the ABI's rejections, which need no device."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import goal_cases as gc
+import harness_build
 
 
 @pytest.fixture(scope="module")
@@ -161,10 +161,7 @@ def test_grid_poses_of_the_harness_equal_the_restatement(harness):
 
 def test_harness_program_under_sanitizers(tmp_path):
     """the stand-alone program (its own main) over the same headers, under -fsanitize=address,undefined"""
-    exe = str(tmp_path / "fr_goal_harness_asan")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-DFRG_HARNESS_MAIN", "-o", exe, gc.harness_sources()[0]])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    r = harness_build.sanitized_program("fr_goal_harness", "FRG_HARNESS_MAIN", tmp_path)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "checksum" in r.stdout and not r.stderr.strip()
 
@@ -172,12 +169,10 @@ def test_harness_program_under_sanitizers(tmp_path):
 def test_sources_exports_and_header(harness):
     from fisher_rast import _lib
     for n in ("fr_goal.hip", "fr_action_object.hip", "fr_goal_math.h", "fr_action_object_math.h"):
-        assert any(s.endswith(n) for s in _lib.SOURCES), n
+        assert os.path.join(_lib._CSRC, n) in (_lib.UNITS if n.endswith(".hip") else _lib.SOURCES), n
     header = open(os.path.join(gc.ROOT, "include", "fisher_occ.h")).read()
     for name in ("fr_plan_actions_object", "fr_occ_object_cells", "fr_occ_grid_candidates"):
         assert name in _lib.EXPORTS and name + "(" in header
-    entry = open(os.path.join(gc.ROOT, "__graft_entry__.py")).read()
-    assert '"fr_goal.hip"' in entry and '"fr_action_object.hip"' in entry
     assert f"#define FR_ACTION_OBJECT_MAX {_lib.FR_ACTION_OBJECT_MAX}" in header and _lib.FR_ACTION_OBJECT_MAX == harness.frg_h_object_max() == 200
     assert "#define FR_ACTION_MAX_QUEUE 128" in header                              # the planning queue's cap is not raised
     for unit in ("fr_goal.hip", "fr_action_object.hip"):

@@ -6,11 +6,11 @@ g++ into a harness of this test's own and compared on the CPU with the general c
 The inputs cover both fov clamps, needle-shaped splats and cov2D determinants near zero."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import harness_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc")
@@ -64,13 +64,10 @@ TX, TY = W / (2 * FX), H / (2 * FY)
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no C++ compiler")
     d = tmp_path_factory.mktemp("mean_rows_unit")
     src, so = d / "h.cpp", d / "h.so"
     src.write_text(SRC)
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", f"-I{CSRC}", "-o", str(so), str(src)])
+    harness_build.compile_shared(str(src), str(so), harness_build.EXACT + ("-fno-fast-math", f"-I{CSRC}"))
     return ctypes.CDLL(str(so))
 
 

@@ -7,6 +7,7 @@ family; on a general camera every Gaussian outside a band around the decisions, 
 the reference's own get_loss / get_gaussians_outside_mask gave on the CPU (tests/golden/reference_object_loss.npz).  Then the host
 logic of the flags."""
 import inspect
+import os
 import sys
 import types
 
@@ -365,12 +366,11 @@ def test_abi_is_declared_exported_and_mirrored():
     g.build()
     from fisher_rast import _lib
     lib = _lib.load()
-    header = open(_lib.SOURCES[-2]).read()
+    header = open(next(h for h in _lib.HEADERS if h.endswith("fisher_rast.h"))).read()
     for name in ("fr_loss_mask_workspace_bytes", "fr_loss_mask", "fr_bg_penalty_workspace_bytes", "fr_bg_penalty_forward", "fr_bg_penalty_backward",
                  "fr_outside_mask_workspace_bytes", "fr_outside_mask"):
         assert name in _lib.EXPORTS and hasattr(lib, name) and f" {name}(" in header, name
-    assert any(s.endswith("fr_objloss.hip") for s in _lib.SOURCES) and any(s.endswith("fr_objloss_math.h") for s in _lib.SOURCES)
-    assert "fr_objloss.hip" in open(g.__file__).read()
+    assert os.path.join(_lib._CSRC, "fr_objloss.hip") in _lib.UNITS and os.path.join(_lib._CSRC, "fr_objloss_math.h") in _lib.SOURCES
     assert f"#define FR_LOSS_MASK_STATUS_WORDS {_lib.FR_LOSS_MASK_STATUS_WORDS}" in header
     assert f"#define FR_OUTSIDE_STATUS_WORDS {_lib.FR_OUTSIDE_STATUS_WORDS}" in header
     assert lib.fr_loss_mask_workspace_bytes(0, 5) == 0 and lib.fr_loss_mask_workspace_bytes(5, 7) >= 4 * 256 * 4 + 4

@@ -5,13 +5,13 @@ stand-alone harness program under the address and undefined-behaviour sanitizers
 install on a stand-in class.  There is no reference-run fixture for this stage: the reference's planning needs cv2."""
 import ctypes
 import os
-import subprocess
 import sys
 import types
 
 import numpy as np
 import pytest
 
+import harness_build
 import plan_cases as pc
 
 
@@ -154,10 +154,7 @@ def test_max_len_one_short_gives_minus_one(plan_harness):
 
 def test_harness_program_under_sanitizers(tmp_path):
     """the stand-alone program (its own main) over the same header, under -fsanitize=address,undefined"""
-    exe = str(tmp_path / "fr_plan_harness_asan")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-DFRP_HARNESS_MAIN", "-o", exe, pc.harness_sources()[0]])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    r = harness_build.sanitized_program("fr_plan_harness", "FRP_HARNESS_MAIN", tmp_path)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "checksum" in r.stdout and not r.stderr.strip()
 

@@ -337,7 +337,7 @@ def test_abi_is_declared_exported_and_mirrored(rv_harness):
     assert lib.fr_rendervar_forward.restype is ctypes.c_int and len(lib.fr_rendervar_forward.argtypes) == 2
     assert lib.fr_rendervar_backward.restype is ctypes.c_int and len(lib.fr_rendervar_backward.argtypes) == 4
     assert lib.fr_rendervar_workspace_bytes.restype is ctypes.c_size_t
-    assert any(s.endswith("fr_rendervar.hip") for s in _lib.SOURCES) and any(s.endswith("fr_rendervar_math.h") for s in _lib.SOURCES)
+    assert os.path.join(_lib._CSRC, "fr_rendervar.hip") in _lib.UNITS and os.path.join(_lib._CSRC, "fr_rendervar_math.h") in _lib.SOURCES
     # the struct as a C++ compiler lays it out
     names = [n for n, _ in _lib.RenderVarCfg._fields_]
     out = (ctypes.c_longlong * (len(names) + 1))()

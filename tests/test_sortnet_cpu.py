@@ -7,24 +7,18 @@ The in-lane lists are checked exhaustively by the zero-one principle (a comparat
 zero-one input; it sorts every bitonic input iff it sorts every bitonic zero-one input, a monotone map keeping a sequence bitonic);
 whole runs are checked against std::sort inside the harness and against np.sort here."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import harness_build
+
 KS = list(range(1, 9))
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def net():
-    hdir = os.path.join(ROOT, "tests", "harness")
-    so = os.path.join(hdir, "libfr_sortnet_harness.so")
-    srcs = [os.path.join(hdir, "fr_sortnet_harness.cpp"), os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", "fr_sortnet.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, srcs[0]])
-    h = ctypes.CDLL(so)
+    h = ctypes.CDLL(harness_build.shared("fr_sortnet_harness", ()))
     h.frsn_sort_run.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32]
     for f in (h.frsn_list_len, h.frsn_list_failures):
         f.argtypes = [ctypes.c_int, ctypes.c_int]

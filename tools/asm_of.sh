@@ -1,8 +1,8 @@
 #!/bin/bash
 # tools/asm_of.sh <mangled-name-prefix> [extra hipcc flags]: gfx950 assembly of one kernel of fisher_rast.hip -> /tmp/kernel.s
 name=$1; shift
-cd "$(dirname "$0")/../fisher-nerf-customized_amd/csrc"
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize "$@" -S --cuda-device-only -o /tmp/all.s fisher_rast.hip 2>/dev/null
+cd "$(dirname "$0")/.." || exit 1
+python -c 'import sys, __graft_entry__ as g; g.device_assembly("fisher_rast.hip", "/tmp/all.s", sys.argv[1:])' "$@" || exit 1
 a=$(grep -n "^$name" /tmp/all.s | head -1 | cut -d: -f1)
 b=$(awk -v a=$a 'NR>a && /^.Lfunc_end/ {print NR; exit}' /tmp/all.s)
 sed -n "${a},${b}p" /tmp/all.s > /tmp/kernel.s

@@ -14,17 +14,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SO = os.path.join(ROOT, "tools", "_build", "libfisher_rast_ablate.so")
-CSRC = os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc")
 
 
 def build():
-    srcs = [os.path.join(CSRC, f) for f in ("fisher_rast.hip", "fisher_occ.hip")]
-    deps = srcs + [os.path.join(CSRC, "fr_math.h"), os.path.join(CSRC, "fr_rig.inc")]
-    if os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in deps):
-        return
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                           "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize", "-DFR_ABLATE", "-o", SO] + srcs)
+    sys.path.insert(0, ROOT)
+    import __graft_entry__
+    __graft_entry__.build_library(SO, ["-DFR_ABLATE"], force=False)        # the product's recipe; rebuilt when any source changed
 
 
 def child(mode):

@@ -2,12 +2,11 @@
 gfx950 assembly's metadata; no GPU needed).  Waves per SIMD allowed by registers = min(8, 512 // alloc), alloc = ceil8(vgpr + agpr)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "fisher-nerf-customized_amd", "csrc", sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".hip") else "fisher_rast.hip")
-extra = [a for a in sys.argv[1:] if not a.endswith(".hip")]
+sys.path.insert(0, ROOT)
+import __graft_entry__
+unit = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".hip") else "fisher_rast.hip"
 out = "/tmp/kernel_resources.s"
-subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off",
-                       "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize", *extra, "-S", "--cuda-device-only", "-o", out, src],
-                      stderr=subprocess.DEVNULL)
+__graft_entry__.device_assembly(unit, out, [a for a in sys.argv[1:] if not a.endswith(".hip")])
 s = open(out).read()
 pat = re.compile(r"\.agpr_count:\s+(\d+).*?\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+)"
                  r".*?\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+)", re.S)
