@@ -20,6 +20,11 @@
 //                                           lane can still improve or tie there (pruning is non-strict: the lowest original index
 //                                           among equal distances is part of the result); loop counters, bounds and candidates
 //                                           are wave-uniform
+//                                           <0, 1> is the FOLD of a running evaluation (cfg->seed_d2): best starts at the caller's
+//                                           running squared distance and is written back, pruning is STRICT (no index, so no ties),
+//                                           and a lane that the frame of all targets cannot improve is dead before the first load.
+//                                           "depth" also takes a pixel mask, the near flag rule and writes the samples' points
+//                                           (NaN rows where there is no query: a ready target cloud for fr_cloud_index_build)
 //                          k_cloud_partials / k_cloud_total   the statistics, in caller order and one fixed order of sums
 //                                           (fr_cloud_math.h: frc_sum_block): binary64 partials per 256 queries, no float atomics
 //
@@ -226,6 +231,10 @@ struct FrcQuery
 	float* dist;                      // out_dist, or the workspace's copy when only the statistics want it (null: not written)
 	int32_t* out_idx;
 	uint8_t* out_flag;
+	float* seed_d2;                   // "points": the running squared distances of a fold, read and written by the query's own lane
+	const uint8_t* mask;              // "depth": [H,W] or null
+	float* out_points;                // "depth": [Hs Ws, 3] or null
+	int flag_near;                    // "depth": the flag is d < dist_th instead of d > dist_th
 };
 
 __global__ __launch_bounds__(FRC_THREADS) void k_cloud_qkeys(FrcQuery p)
@@ -237,19 +246,29 @@ __global__ __launch_bounds__(FRC_THREADS) void k_cloud_qkeys(FrcQuery p)
 	p.qkeys[i] = ((uint64_t)code << 32) | (uint32_t)i;
 }
 
-// the query of sample (sx, sy) of the depth image: false where the pixel has no depth or its point is not finite
+// the query of sample (sx, sy) of the depth image: false where the pixel is masked out, has no depth or its point is not finite
 __device__ __forceinline__ bool frc_depth_query(const FrcQuery& p, int sx, int sy, float* q)
 {
 	const int u = sx * p.stride, v = sy * p.stride;
-	const float d = p.depth[(size_t)v * p.W + u];
-	if (!frc_depth_valid(d)) return false;
+	const size_t px = (size_t)v * p.W + u;
+	const float d = p.depth[px];
+	if (!frc_sample_is_query(d, p.mask != nullptr, p.mask ? p.mask[px] : (uint8_t)1)) return false;
 	frc_back_project(u, v, d, p.kinv, p.c2w, p.flip_z, q);
 	return frc_finite3(q[0], q[1], q[2]);
 }
 
-template <int DEPTH>
+__device__ __forceinline__ bool frc_depth_flag(const FrcQuery& p, float d)
+{
+	return p.flag_near ? frc_flag_near(d, p.dist_th) : frc_flag_novel(d, p.dist_th);
+}
+
+// FOLD ("points" with seed_d2): a lane's best starts at its seed, no index is kept, and every test is strict -- a box is opened
+// only when a live lane can IMPROVE there (frc_fold_may_improve), since a tie changes nothing.  A lane whose seed is not above
+// its bound to the frame of all finite targets is dead from the start; a wave of dead lanes writes its outputs and leaves.
+template <int DEPTH, int FOLD>
 __global__ __launch_bounds__(FRC_THREADS) void k_cloud_search(FrcQuery p)
 {
+	static_assert(!(DEPTH && FOLD), "a fold takes its queries from points");
 	const int lane = threadIdx.x & 63;
 	const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (FRC_THREADS / 64) + (threadIdx.x >> 6)));
 	bool inrange, ok;
@@ -267,6 +286,11 @@ __global__ __launch_bounds__(FRC_THREADS) void k_cloud_search(FrcQuery p)
 		{
 			m = sy * p.Ws + sx;
 			ok = frc_depth_query(p, sx, sy, q);
+			if (p.out_points)
+			{
+				float* o = p.out_points + 3 * (size_t)m;
+				o[0] = ok ? q[0] : NAN; o[1] = ok ? q[1] : NAN; o[2] = ok ? q[2] : NAN;
+			}
 		}
 		if (ok) code = frc_morton(q[0], q[1], q[2], p.head->lo, p.head->hi);
 		else q[0] = q[1] = q[2] = 0.f;
@@ -289,7 +313,13 @@ __global__ __launch_bounds__(FRC_THREADS) void k_cloud_search(FrcQuery p)
 	const int nf = __builtin_amdgcn_readfirstlane((int)p.head->nf);
 	float best = INFINITY;
 	int32_t bidx = -1;
-	if (ok && nf > 0)
+	bool live = ok;                   // the lane has a query; FOLD: and the query can still improve
+	if (FOLD)
+	{
+		if (ok) best = p.seed_d2[m];
+		live = ok && nf > 0 && frc_fold_may_improve(frc_box_dist2(q[0], q[1], q[2], p.head->lo, p.head->hi), best);
+	}
+	if (live && nf > 0)
 	{
 		// the lane's own place among the sorted target keys (first key of its code or beyond), and FRC_SEED targets on each side
 		const uint64_t want = (uint64_t)code << 32;
@@ -303,44 +333,63 @@ __global__ __launch_bounds__(FRC_THREADS) void k_cloud_search(FrcQuery p)
 		for (int s = s0; s <= s1; s++)
 		{
 			const float d2 = frc_dist2(q[0], q[1], q[2], p.sorted[3 * (size_t)s], p.sorted[3 * (size_t)s + 1], p.sorted[3 * (size_t)s + 2]);
-			const int32_t idx = (int32_t)(uint32_t)p.tkeys[s];
-			if (frc_better(d2, idx, best, bidx)) { best = d2; bidx = idx; }
+			if (FOLD) best = frc_fold(best, d2);
+			else
+			{
+				const int32_t idx = (int32_t)(uint32_t)p.tkeys[s];
+				if (frc_better(d2, idx, best, bidx)) { best = d2; bidx = idx; }
+			}
 		}
 	}
-	const int nb = (nf + FRC_BOX - 1) / FRC_BOX, nsb = (nf + FRC_SUB - 1) / FRC_SUB, nsp = (nb + FRC_SUPER - 1) / FRC_SUPER;
+	const int nb = (nf + FRC_BOX - 1) / FRC_BOX, nsb = (nf + FRC_SUB - 1) / FRC_SUB;
+	const int nsp = (!FOLD || frc_any(live)) ? (nb + FRC_SUPER - 1) / FRC_SUPER : 0;          // (a fold's wave of dead lanes scans nothing)
 	for (int sp = 0; sp < nsp; sp++)
 	{
 		const float* px = p.supers + 6 * (size_t)sp;
 		const float d0 = frc_box_dist2(q[0], q[1], q[2], px, px + 3);
-		if (!frc_any(ok && !(d0 > best))) continue;           // skipped only when no lane can improve OR TIE there
+		// skipped only when no lane can improve OR TIE there; a fold: when no live lane can improve
+		if (!frc_any(live && (FOLD ? frc_fold_may_improve(d0, best) : !(d0 > best)))) continue;
 		const int b1 = min(nb, (sp + 1) * FRC_SUPER);
 		for (int b = sp * FRC_SUPER; b < b1; b++)
 		{
 			const float* bx = p.boxes + 6 * (size_t)b;
 			const float d1 = frc_box_dist2(q[0], q[1], q[2], bx, bx + 3);
-			if (!frc_any(ok && !(d1 > best))) continue;
+			if (!frc_any(live && (FOLD ? frc_fold_may_improve(d1, best) : !(d1 > best)))) continue;
 			const int sb1 = min(nsb, (b + 1) * (FRC_BOX / FRC_SUB));
 			for (int sb = b * (FRC_BOX / FRC_SUB); sb < sb1; sb++)
 			{
 				const float* sx = p.sboxes + 6 * (size_t)sb;
 				const float d2b = frc_box_dist2(q[0], q[1], q[2], sx, sx + 3);
-				if (!frc_any(ok && !(d2b > best))) continue;
+				if (!frc_any(live && (FOLD ? frc_fold_may_improve(d2b, best) : !(d2b > best)))) continue;
 				const int end = min(nf, (sb + 1) * FRC_SUB);
 				for (int s = sb * FRC_SUB; s < end; s++)
 				{
 					const float d2 = frc_dist2(q[0], q[1], q[2], p.sorted[3 * (size_t)s], p.sorted[3 * (size_t)s + 1], p.sorted[3 * (size_t)s + 2]);
-					const int32_t idx = (int32_t)(uint32_t)p.tkeys[s];
-					if (frc_better(d2, idx, best, bidx)) { best = d2; bidx = idx; }
+					if (FOLD) best = frc_fold(best, d2);
+					else
+					{
+						const int32_t idx = (int32_t)(uint32_t)p.tkeys[s];
+						if (frc_better(d2, idx, best, bidx)) { best = d2; bidx = idx; }
+					}
 				}
 			}
 		}
 	}
 	if (!inrange) return;
+	if (FOLD)
+	{
+		// the query's own lane is the only one that touches its seed: no atomics; a query that is not finite leaves it alone
+		if (ok) p.seed_d2[m] = best;
+		const float d = ok ? frc_distance(best) : INFINITY;
+		if (p.dist) p.dist[m] = d;
+		if (p.out_flag) p.out_flag[m] = (uint8_t)(ok && frc_flag_near(d, p.dist_th));
+		return;
+	}
 	const bool found = ok && bidx >= 0;
 	const float d = found ? frc_distance(best) : INFINITY;
 	if (p.dist) p.dist[m] = d;
 	if (p.out_idx) p.out_idx[m] = found ? bidx : -1;
-	if (p.out_flag) p.out_flag[m] = (uint8_t)(ok && (DEPTH ? frc_flag_novel(d, p.dist_th) : frc_flag_near(d, p.dist_th)));
+	if (p.out_flag) p.out_flag[m] = (uint8_t)(ok && (DEPTH ? frc_depth_flag(p, d) : frc_flag_near(d, p.dist_th)));
 }
 
 struct FrcPartial { double sum; unsigned long long valid, flagged, skipped; };
@@ -366,7 +415,7 @@ __global__ __launch_bounds__(FRC_THREADS) void k_cloud_partials(FrcQuery p, int 
 			else ok = frc_finite3(p.queries[3 * (size_t)m], p.queries[3 * (size_t)m + 1], p.queries[3 * (size_t)m + 2]);
 		}
 		const float d = ok ? p.dist[m] : 0.0f;
-		const bool flag = ok && (DEPTH ? frc_flag_novel(d, p.dist_th) : frc_flag_near(d, p.dist_th));
+		const bool flag = ok && (DEPTH ? frc_depth_flag(p, d) : frc_flag_near(d, p.dist_th));
 		double v = ok ? (double)d : 0.0;
 #pragma unroll
 		for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
@@ -501,6 +550,9 @@ extern "C" int fr_cloud_query(const void* index, size_t index_bytes, int32_t N, 
 		p.H = cfg->H; p.W = cfg->W; p.stride = cfg->stride; p.flip_z = cfg->flip_z != 0;
 		p.Hs = (cfg->H + cfg->stride - 1) / cfg->stride; p.Ws = (cfg->W + cfg->stride - 1) / cfg->stride;
 		M = (int64_t)p.Hs * p.Ws;
+		if (cfg->seed_d2) return fr_fail(FR_EINVAL, "fr_cloud_query: seed_d2 goes with FR_CLOUD_SOURCE_POINTS only");
+		if (!fr_aligned(cfg->out_points, 4)) return fr_fail(FR_EINVAL, "fr_cloud_query: misaligned out_points (4 bytes)");
+		p.mask = cfg->mask; p.out_points = cfg->out_points; p.flag_near = cfg->flag_near != 0;
 	}
 	else
 	{
@@ -508,6 +560,10 @@ extern "C" int fr_cloud_query(const void* index, size_t index_bytes, int32_t N, 
 		if (M < 0 || M > FR_CLOUD_MAX_POINTS) return fr_fail(FR_EINVAL, "fr_cloud_query: M outside [0, FR_CLOUD_MAX_POINTS]");
 		if (M > 0 && !cfg->queries) return fr_fail(FR_EINVAL, "fr_cloud_query: null queries");
 		if (!fr_aligned(cfg->queries, 4)) return fr_fail(FR_EINVAL, "fr_cloud_query: misaligned queries");
+		if (cfg->mask || cfg->out_points) return fr_fail(FR_EINVAL, "fr_cloud_query: mask and out_points go with FR_CLOUD_SOURCE_DEPTH only");
+		if (cfg->seed_d2 && cfg->out_idx) return fr_fail(FR_EINVAL, "fr_cloud_query: out_idx must be null with seed_d2 (the union it would index is gone)");
+		if (!fr_aligned(cfg->seed_d2, 4)) return fr_fail(FR_EINVAL, "fr_cloud_query: misaligned seed_d2 (4 bytes)");
+		p.seed_d2 = cfg->seed_d2;
 	}
 	if (!fr_aligned(index, 8) || !fr_aligned(workspace, 8) || !fr_aligned(cfg->out_dist, 4) || !fr_aligned(cfg->out_idx, 4) ||
 	    !fr_aligned(cfg->out_stats, 8))
@@ -530,12 +586,12 @@ extern "C" int fr_cloud_query(const void* index, size_t index_bytes, int32_t N, 
 	p.dist = cfg->out_dist ? cfg->out_dist : (cfg->out_stats ? (float*)(ws + Q.dist) : nullptr);
 	p.out_idx = cfg->out_idx; p.out_flag = cfg->out_flag;
 	int rc;
-	if (M > 0 && (p.dist || p.out_idx || p.out_flag))
+	if (M > 0 && (p.dist || p.out_idx || p.out_flag || p.seed_d2 || p.out_points))
 	{
 		if (depth)
 		{
 			const int waves = ((p.Ws + 7) / 8) * ((p.Hs + 7) / 8);
-			hipLaunchKernelGGL(k_cloud_search<1>, dim3((waves + 3) / 4), dim3(FRC_THREADS), 0, s, p);
+			hipLaunchKernelGGL((k_cloud_search<1, 0>), dim3((waves + 3) / 4), dim3(FRC_THREADS), 0, s, p);
 		}
 		else
 		{
@@ -543,7 +599,8 @@ extern "C" int fr_cloud_query(const void* index, size_t index_bytes, int32_t N, 
 			hipLaunchKernelGGL(k_cloud_qkeys, dim3(nblk), dim3(FRC_THREADS), 0, s, p);
 			if ((rc = fr_check_launch("k_cloud_qkeys"))) return rc;
 			if ((rc = fr_sort_keys64(p.qkeys, (uint32_t)M, stream))) return rc;
-			hipLaunchKernelGGL(k_cloud_search<0>, dim3(nblk), dim3(FRC_THREADS), 0, s, p);
+			if (p.seed_d2) hipLaunchKernelGGL((k_cloud_search<0, 1>), dim3(nblk), dim3(FRC_THREADS), 0, s, p);
+			else hipLaunchKernelGGL((k_cloud_search<0, 0>), dim3(nblk), dim3(FRC_THREADS), 0, s, p);
 		}
 		if ((rc = fr_check_launch("k_cloud_search"))) return rc;
 	}

@@ -55,6 +55,13 @@ FRC_HD bool frc_better(float d2, int32_t idx, float best_d2, int32_t best_idx)
 
 FRC_HD float frc_distance(float d2) { return sqrtf(d2); }
 
+// The seeded ("fold") search: a running squared distance against a candidate.  min over a union of target sets = min of the minima,
+// exactly: both are values of frc_dist2 (never -0, never NaN for finite operands), and the smaller of two floats is one of them.
+// Equal values keep the seed's bits; a candidate replaces the seed only when it is strictly smaller, so no index is kept and the
+// box tests of a fold may prune strictly (frc_fold_may_improve).
+FRC_HD float frc_fold(float seed_d2, float d2) { return d2 < seed_d2 ? d2 : seed_d2; }
+FRC_HD bool frc_fold_may_improve(float bound_d2, float best_d2) { return bound_d2 < best_d2; }
+
 FRC_HD uint32_t frc_spread10(uint32_t x)
 {
 	x = (x | (x << 16)) & 0x030000FFu;
@@ -83,6 +90,10 @@ FRC_HD uint32_t frc_morton(float x, float y, float z, const float* lo, const flo
 
 // test_utils.py:531: a pixel has a depth when it is finite and positive
 FRC_HD bool frc_depth_valid(float d) { return frc_finite(d) && d > 0.0f; }
+
+// tester_gaussians_navigation.py:515, (object_mask_bw > 0) & (depth > 0): with a mask a pixel is a query only where its mask byte
+// is not 0 and it has a depth; a masked-out pixel is a pixel without a depth in every respect
+FRC_HD bool frc_sample_is_query(float d, int has_mask, uint8_t mask_byte) { return (!has_mask || mask_byte != 0) && frc_depth_valid(d); }
 
 // test_utils.py:544-550: the pixel (u, v) at depth d through kinv [9] into the camera frame, the camera z negated for a camera that
 // looks along -Z, then through c2w [12] (the top three rows of a row-major 4 x 4) into the world

@@ -193,7 +193,8 @@ class CloudQueryCfg(ctypes.Structure):
     """fr_cloud_query_cfg (include/fisher_rast.h)"""
     _fields_ = [("source", ctypes.c_int32), ("M", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("stride", ctypes.c_int32),
                 ("flip_z", ctypes.c_int32), ("dist_th", ctypes.c_float)] + \
-               [(n, ctypes.c_void_p) for n in ("queries", "depth", "kinv", "c2w", "out_dist", "out_idx", "out_flag", "out_stats")]
+               [(n, ctypes.c_void_p) for n in ("queries", "depth", "kinv", "c2w", "out_dist", "out_idx", "out_flag", "out_stats")] + \
+               [("seed_d2", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("flag_near", ctypes.c_int32), ("out_points", ctypes.c_void_p)]
 
 
 FR_CLUSTER_MAX_POINTS = 1 << 26

@@ -760,6 +760,20 @@ typedef struct {
 	uint8_t* out_flag;                /* [M] bytes or null */
 	void* out_stats;                  /* FR_CLOUD_STATS_WORDS 8-byte words or null; the same call gives the same bytes: per-256-query binary64
 	                                     partials in caller order, added in one fixed order (frc_sum_block), integer counts, no float atomics */
+	/* Optional, for a running evaluation that folds one frame after another into the search; all zero or null is the call above, bit for bit. */
+	float* seed_d2;                   /* "points": [M] in and out, or null.  A FOLD: query m starts from best = seed_d2[m], a SQUARED distance
+	                                     (d2 above), and the smaller of the seed and the minimum over the finite targets is written back;
+	                                     out_dist[m] = sqrtf of it, out_flag and the statistics are taken from it -- what a search against the
+	                                     union of everything folded so far would give, exactly (a minimum over a union is the minimum of the
+	                                     minima).  A query with a non-finite coordinate leaves its seed untouched and is counted as skipped.
+	                                     Seeds are +inf or values an earlier fold wrote; they are NOT inspected.  out_idx must be null (the
+	                                     union is gone); FR_EINVAL otherwise, in "depth" mode, or when not 4-byte aligned */
+	const uint8_t* mask;              /* "depth": device [H,W] bytes or null.  A pixel is a query only where its byte is not 0 AND its depth is
+	                                     valid; a masked-out pixel is a pixel without a depth in every respect.  FR_EINVAL in "points" mode */
+	int32_t flag_near;                /* "depth": non-zero makes out_flag and `flagged` d < dist_th (strict) instead of d > dist_th */
+	float* out_points;                /* "depth": [Hs Ws, 3] or null: the point of every sample in sample order, three NaNs where the sample is
+	                                     no query -- fr_cloud_index_build sorts such rows last and ignores them, so this is a target cloud
+	                                     as it stands.  4-byte aligned; FR_EINVAL when not, or in "points" mode */
 } fr_cloud_query_cfg;
 
 /* Host-only queries, non-decreasing in their argument (0 for an argument outside the limits). */
@@ -775,7 +789,8 @@ int fr_cloud_index_build(int32_t N, const float* points, void* index, size_t ind
 /* Any subset of the outputs of cfg against an index built over N points.  M = 0 writes the statistics only (zeros).
  * FR_EINVAL for a null index, cfg or workspace, a null source pointer, an unknown source, non-positive H / W / stride, sizes outside the
  * limits, a misaligned pointer (index, workspace, out_stats 8 bytes; floats and out_idx 4), a short index or workspace
- * (fr_cloud_query_workspace_bytes(M), in depth mode of Hs Ws). */
+ * (fr_cloud_query_workspace_bytes(M), in depth mode of Hs Ws; the optional fields need no more), an optional field with the wrong
+ * source or misaligned (see the struct). */
 int fr_cloud_query(const void* index, size_t index_bytes, int32_t N, const fr_cloud_query_cfg* cfg, void* workspace,
                    size_t workspace_bytes, fr_stream_t stream);
 
