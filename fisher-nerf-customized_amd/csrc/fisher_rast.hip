@@ -7564,6 +7564,8 @@ extern "C" int fr_fisher_views(const fr_raster_cfg* cfg, const fr_gaussians* g, 
                                void* workspace, size_t workspace_bytes, int64_t max_rendered,
                                int32_t* status, fr_stream_t stream)
 {
+	// an extension makes this another call, which renders nothing: the POp-GS block stage (fr_popgs_block.hip)
+	if (cfg && cfg->ext) return fr_popgs_block_stage(cfg, g, fc, workspace, workspace_bytes, status, stream);
 	int rc = fr_validate(cfg, g, "fr_fisher_views");
 	if (rc) return rc;
 	if ((rc = fr_check_views("fr_fisher_views", "bad fisher cfg", FR_CHK_CFG, cfg, fc, max_rendered, status))) return rc;

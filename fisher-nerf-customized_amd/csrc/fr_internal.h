@@ -9,6 +9,9 @@ __attribute__((visibility("hidden"))) int fr_fail(int code, const char* msg);
 __attribute__((visibility("hidden"))) int fr_check_launch(const char* what);
 // ascending sort of n 64-bit device keys in place on `stream` (fisher_rast.hip: the bitonic network of the Morton sort); n = 0 is fine
 __attribute__((visibility("hidden"))) int fr_sort_keys64(uint64_t* keys, uint32_t n, fr_stream_t stream);
+// fr_fisher_views with cfg->ext set (non-null): the POp-GS block stage over probe rows (fr_popgs_block.hip; contract in fisher_rast.h)
+__attribute__((visibility("hidden"))) int fr_popgs_block_stage(const fr_raster_cfg* cfg, const fr_gaussians* g, const fr_fisher_cfg* fc, void* workspace,
+                                                               size_t workspace_bytes, int32_t* status, fr_stream_t stream);
 
 // ---- argument checks and workspace layout of the entry points (host) ----------------------------------------------------------------
 // workspace sections begin on 256 bytes

@@ -16,6 +16,31 @@ FR_POPGS_TOPT, FR_POPGS_DOPT = 0, 1
 _f32p = ctypes.c_void_p  # device pointers travel as raw addresses
 
 
+FR_EXT_POPGS_BLOCK = 1
+FR_POPGS_BLOCK_VISIBLE, FR_POPGS_BLOCK_SCORE, FR_POPGS_BLOCK_PRIOR = 0, 1, 2
+FR_POPGS_BLOCK_MAX_WG = 256
+
+
+class RasterExt(ctypes.Structure):
+    """fr_raster_ext (include/fisher_rast.h): with RasterCfg.ext set, fr_fisher_views is the POp-GS block stage"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("kind", "mode", "K", "use_opacity", "use_rot", "use_scale", "criterion", "n")] + \
+               [("lam", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("vis_in", "out_vis", "out_vis_count", "prior_blocks", "prior_idx", "out_scores", "out_matched")]
+
+
+def popgs_block_workspace_bytes(P, poses):
+    """FR_POPGS_BLOCK_WS_BYTES (include/fisher_rast.h): the workspace of the block stage for `poses` poses of a map of P Gaussians"""
+    P, poses = int(P), int(poses)
+    a = lambda x: (x + 255) & ~255
+    wgs = (P + 255) // 256
+    return a(poses * P) + a(poses * P * 4) + 2 * a(poses * wgs * 4) + a(poses * 4) + a(poses * FR_POPGS_BLOCK_MAX_WG * 32)
+
+
+def popgs_block_dim(use_opacity, use_rot, use_scale):
+    """d of the d x d blocks: mean 3, opacity 1, rot 4, scale 3"""
+    return 3 + (1 if use_opacity else 0) + (4 if use_rot else 0) + (3 if use_scale else 0)
+
+
 class RasterCfg(ctypes.Structure):
     _fields_ = [
         ("P", ctypes.c_int32),
@@ -31,6 +56,7 @@ class RasterCfg(ctypes.Structure):
         ("viewmatrix", _f32p),
         ("projmatrix", _f32p),
         ("campos", _f32p),
+        ("ext", ctypes.POINTER(RasterExt)),      # null (the default): every entry point as before the field existed
     ]
 
 

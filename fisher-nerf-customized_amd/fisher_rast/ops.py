@@ -6,7 +6,8 @@ Four groups of entry points:
     rasterize_points.h:18-66); `diff_gaussian_rasterization/_C.py` re-exports them under the reference names.
   * `FisherScorer` -- the batched multi-view scorer behind GaussianSLAM.compute_Hessian / compute_H_train /
     pose_eval (models/SLAM/gaussian.py:1338-1375, 1503-1570); its `render_views` renders a batch of poses in one call
-    (RGB, depth / silhouette, median depth, final transmittance: fr_render_views).
+    (RGB, depth / silhouette, median depth, final transmittance: fr_render_views); its `visible` / `popgs_block_prior` /
+    `popgs_block_scores` are the POp-GS block stage (fr_raster_cfg.ext: fr_fisher_views renders nothing).
   * `knn_dist2` -- simple_knn._C.distCUDA2.
   * `popgs_diag_criterion` -- the POp-GS T-opt / D-opt score of a batch of views from their probe rows, and the priors of the
     path evaluation updated in the same pass (tester_gaussians_navigation.py:2147-2178).
@@ -741,6 +742,97 @@ class FisherScorer:
         if per_view:
             res["point_scores"] = point
         return res
+
+    # -- POp-GS block stage (fr_raster_cfg.ext: fr_fisher_views renders nothing, include/fisher_rast.h) -------------------------
+    def _block_stage(self, ext, w2cs, K, rows=None):
+        """One call of the block stage on the current stream (no sync): `ext` filled by the caller, poses w2cs [V,4,4] (each repeated
+        per probe here, as the C side reads pose p from view p K), rows [V,K,P,11] or None.  Returns the status word [4] (device)."""
+        d = self.dev
+        if self.P == 0:
+            raise FisherRastError("the POp-GS block stage needs a map of at least one Gaussian")
+        w2cs = _prep(w2cs.reshape(-1, 4, 4), d)
+        V, K = int(w2cs.shape[0]), int(K)
+        views = w2cs.repeat_interleave(K, dim=0).contiguous() if K > 1 else w2cs
+        if rows is not None and (rows.numel() != V * K * self.P * 11 or rows.dtype != torch.float32 or not rows.is_contiguous() or rows.device != d):
+            raise ValueError("rows must be a contiguous fp32 device tensor [V, K, P, 11]")
+        ext.kind, ext.K = _lib.FR_EXT_POPGS_BLOCK, K
+        cfg = RasterCfg.from_buffer_copy(self.cfg)
+        cfg.ext = ctypes.pointer(ext)
+        fc = FisherCfg()
+        fc.n_views, fc.columns = V * K, 11
+        fc.w2c = ctypes.c_void_p(views.data_ptr())
+        fc.out_H = None if rows is None else ctypes.c_void_p(rows.data_ptr())
+        fc.out_H_view_stride = 11 * self.P
+        ws = self._workspace(_lib.popgs_block_workspace_bytes(self.P, V), "block")
+        status = torch.empty((4,), dtype=torch.int32, device=d)
+        with torch.cuda.device(d):
+            _lib.check(self.lib.fr_fisher_views(ctypes.byref(cfg), ctypes.byref(self.g), ctypes.byref(fc), ws.data_ptr(), ws.numel(), 0,
+                                                status.data_ptr(), _stream(d)), "fr_fisher_views (POp-GS block stage)")
+        return status
+
+    @staticmethod
+    def _block_flags(ext, use_rot, use_scale, use_opacity):
+        ext.use_rot, ext.use_scale, ext.use_opacity = int(bool(use_rot)), int(bool(use_scale)), int(bool(use_opacity))
+        return _lib.popgs_block_dim(use_opacity, use_rot, use_scale)
+
+    def visible(self, w2cs):
+        """(mask bool [V,P], counts int32 [V]) on the device: Gaussian i has radius > 0 at pose v -- the single-view rasteriser's
+        `radii > 0`, bit for bit, without rendering.  No sync."""
+        d = self.dev
+        V = int(w2cs.reshape(-1, 4, 4).shape[0])
+        mask = torch.empty((V, self.P), dtype=torch.uint8, device=d)
+        counts = torch.empty((V,), dtype=torch.int32, device=d)
+        if V == 0 or self.P == 0:
+            return mask.view(torch.bool), counts.zero_()
+        ext = _lib.RasterExt()
+        ext.mode, ext.out_vis, ext.out_vis_count = _lib.FR_POPGS_BLOCK_VISIBLE, mask.data_ptr(), counts.data_ptr()
+        self._block_stage(ext, w2cs, 1)
+        return mask.view(torch.bool), counts
+
+    def popgs_block_prior(self, rows, w2cs, K, use_rot=True, use_scale=True, use_opacity=True):
+        """compute_H_train_blocks from the keyframes' probe rows [V,K,P,11] and poses w2cs [V,4,4], the reference's truncation kept:
+        (Hm [n,d,d] fp32, idx [n] int32), n = the smallest visible count.  One host read (n)."""
+        d = self.dev
+        ext = _lib.RasterExt()
+        dim = self._block_flags(ext, use_rot, use_scale, use_opacity)
+        Hm = torch.empty((self.P, dim, dim), dtype=torch.float32, device=d)
+        idx = torch.empty((self.P,), dtype=torch.int32, device=d)
+        ext.mode, ext.n, ext.prior_blocks, ext.prior_idx = _lib.FR_POPGS_BLOCK_PRIOR, self.P, Hm.data_ptr(), idx.data_ptr()
+        status = self._block_stage(ext, w2cs, K, rows)
+        n = int(status[0].item())
+        return Hm[:n], idx[:n]
+
+    def popgs_block_scores(self, rows, w2cs, K, Hm, idx, lam=1e-6, criterion="topt", use_rot=True, use_scale=True, use_opacity=True, vis=None):
+        """Block T-opt / D-opt scores of V poses from their probe rows [V,K,P,11] against the prior (Hm [n,d,d], idx [n]):
+        (scores float64 [V], matched int32 [V]) on the device, no sync; a pose that sees none of the prior's Gaussians scores -inf.
+        `vis` (bool / uint8 [V,P]) replaces the visibility the call would compute from w2cs.  The status word of the call
+        ({pairs, 0, non-positive pivots, prior rows with an index outside the map}) is left in `self.block_status`."""
+        d = self.dev
+        if criterion not in ("topt", "dopt"):
+            raise ValueError("criterion must be 'topt' or 'dopt'")
+        V = int(w2cs.reshape(-1, 4, 4).shape[0])
+        scores = torch.empty((V,), dtype=torch.float64, device=d)
+        matched = torch.empty((V,), dtype=torch.int32, device=d)
+        ext = _lib.RasterExt()
+        dim = self._block_flags(ext, use_rot, use_scale, use_opacity)
+        n = int(idx.shape[0])
+        if tuple(Hm.shape) != (n, dim, dim):
+            raise ValueError(f"Hm is {tuple(Hm.shape)}, expected {(n, dim, dim)}")
+        if n == 0 or V == 0:
+            self.block_status = torch.zeros((4,), dtype=torch.int32, device=d)
+            return scores.fill_(float("-inf")), matched.zero_()
+        Hm = _prep(Hm, d)
+        idx = idx.to(device=d, dtype=torch.int32).contiguous()
+        if vis is not None:
+            if tuple(vis.shape) != (V, self.P) or vis.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("vis must be bool or uint8 [V, P]")
+            vis = vis.to(d).contiguous().view(torch.uint8)
+            ext.vis_in = vis.data_ptr()
+        ext.mode, ext.n, ext.lam = _lib.FR_POPGS_BLOCK_SCORE, n, float(lam)
+        ext.criterion = _lib.FR_POPGS_TOPT if criterion == "topt" else _lib.FR_POPGS_DOPT
+        ext.prior_blocks, ext.prior_idx, ext.out_scores, ext.out_matched = Hm.data_ptr(), idx.data_ptr(), scores.data_ptr(), matched.data_ptr()
+        self.block_status = self._block_stage(ext, w2cs, K, rows)
+        return scores, matched
 
 
 def spatial_order_of(means3D: torch.Tensor) -> torch.Tensor:

@@ -11,6 +11,10 @@
       no per-probe backward pass.  What a probe returns is the reference's quantity -- the power-2 gradient row of every
       Gaussian under z_k -- so diag / block estimates agree with the reference's route to the scorer's 1e-4 bar
       (tests/test_gpu_fisher_parity.py checks both against the oracle and against the drop-in autograd rasteriser).
+  Block criteria, fused (`fused=True` of compute_H_train_blocks / pose_eval_popgs_blocks): the probe rows stay on the device and
+      the POp-GS block stage of fr_fisher_views (fr_raster_cfg.ext, include/fisher_rast.h) builds the prior and scores every pose of
+      a chunk in one pass, factorising in binary64 -- no extra render for `radius > 0`, no einsum, no isin, no batched LAPACK; the host
+      reads the prior's n, the scores, and the scorer's status word per probe launch.  Off by default: the default route is the binary32 LAPACK chain, whose last digits differ.
   Only the accelerated estimators live here.  `install()` grafts them onto the reference class and leaves everything else
   of that class in place.
 """
@@ -29,6 +33,52 @@ def _criterion(name):
     if name not in ("topt", "dopt"):
         raise ValueError("criterion must be 'topt' or 'dopt'")
     return name
+
+
+def _keyframe_w2cs(slam):
+    if len(slam.keyframe_list) == 0:
+        raise RuntimeError("No keyframes available for POP-GS prior (blocks).")
+    return torch.stack([slam._as_w2c(kf['est_w2c']) for kf in slam.keyframe_list])
+
+
+def visible_masks(slam, w2cs):
+    """(mask bool [V,N], counts int32 [V]) on the device for V world->camera poses: `radius > 0` of the rasteriser, bit for bit, without
+    rendering (the VISIBLE mode of the POp-GS block stage).  `_visible_indices` stays as it is."""
+    return slam._scorer().visible(slam._as_w2c(w2cs).reshape(-1, 4, 4))
+
+
+def _probe_draws(zs, v0, v1, K):
+    """the draws of poses [v0, v1) as the sequence `_draw_probes` takes, or None: `zs` is a [V,K,3,H,W] tensor, a callable
+    (v0, v1) -> [v1 - v0, K, 3, H, W], or None (random draws)"""
+    if zs is None:
+        return None
+    z = zs(v0, v1) if callable(zs) else zs[v0:v1]
+    return list(z.reshape((v1 - v0) * K, *z.shape[-3:]))
+
+
+def _fused_block_prior(slam, K, zs, flags):
+    """compute_H_train_blocks on the device: the keyframes' probes in one launch, one call of the block stage (PRIOR).  `zs`: K
+    draws shared by every keyframe, as `estimate_block_JtJ(..., zs=zs)` per keyframe gives them.  The stage needs every keyframe's
+    rows at once, so this is not chunked: F keyframes hold F K N 44 bytes of rows (0.53 GB at 4 keyframes, K = 6, 500k Gaussians)
+    plus the [N, d, d] output at its capacity (0.24 GB there)."""
+    w2cs = _keyframe_w2cs(slam)
+    F = int(w2cs.shape[0])
+    rows, _ = slam._pose_probe_rows(w2cs, K, None if zs is None else list(zs) * F)
+    Hm, idx = slam._scorer().popgs_block_prior(rows, w2cs, K, **flags)
+    return Hm, idx.long()
+
+
+def _fused_block_scores(slam, w2cs, K, Hm, idx, lam, crit, flags, zs=None, chunk_bytes=4 << 30):
+    """block scores [V] (float64, device) of V poses: chunks sized like `_diag_batch`, per chunk one probe launch and one call of the
+    block stage (SCORE).  No host read here beyond the scorer's status word per probe launch."""
+    N, V = int(slam.params['means3D'].shape[0]), int(w2cs.shape[0])
+    per = max(1, int(chunk_bytes // (K * N * 44)))
+    scorer, out = slam._scorer(), []
+    for v0 in range(0, V, per):
+        v1 = min(V, v0 + per)
+        rows, _ = slam._pose_probe_rows(w2cs[v0:v1], K, _probe_draws(zs, v0, v1, K))
+        out.append(scorer.popgs_block_scores(rows, w2cs[v0:v1], K, Hm, idx, lam=lam, criterion=crit, **flags)[0])
+    return torch.cat(out) if out else torch.zeros((0,), dtype=torch.float64, device=w2cs.device)
 
 
 class ObjectFisherOps(FisherOps):
@@ -136,9 +186,12 @@ class ObjectFisherOps(FisherOps):
         G = rows[0][:, vis_idx][:, :, self._block_columns(use_rot, use_scale, use_opacity)]      # [K, Nv, d]
         return torch.einsum('kvi,kvj->vij', G, G) / float(K), vis_idx
 
-    def compute_H_train_blocks(self, K: int = 2, **flags):
+    def compute_H_train_blocks(self, K: int = 2, fused: bool = False, **flags):
         """Sum over the keyframes.  The reference does not align the visible sets of different keyframes: it truncates both
-        operands to the smaller count and keeps the first keyframe's index list (1577-1584); kept, so that scores match."""
+        operands to the smaller count and keeps the first keyframe's index list (1577-1584); kept, so that scores match.
+        `fused=True`: the same on the device in one pass (`_fused_block_prior`); the host reads n and the probe launch's status word."""
+        if fused:
+            return _fused_block_prior(self, int(K), flags.pop("zs", None), flags)
         if len(self.keyframe_list) == 0:
             raise RuntimeError("No keyframes available for POP-GS prior (blocks).")
         per_kf = [self.estimate_block_JtJ(kf['est_w2c'], K=K, **flags) for kf in self.keyframe_list]
@@ -167,9 +220,18 @@ class ObjectFisherOps(FisherOps):
         return cls._block_scores(Hm_blocks, J_blocks, lam, "dopt")
 
     def pose_eval_popgs_blocks(self, poses, random_gaussian_params=None, criterion: str = "topt", K: int = 6, lam: float = 1e-6,
-                               use_rot=True, use_scale=True, use_opacity=True):
+                               use_rot=True, use_scale=True, use_opacity=True, fused=False, zs=None):
+        """(scores cpu fp32 [V], stack(c2w)).  `fused=True`: the prior and every pose's score on the device (the POp-GS block stage of
+        fr_fisher_views, binary64 factorisations); the scores are read once at the end, beside the prior's n and the scorer's status
+        word per probe launch (3 to 6 device-to-host copies a call, measured, against two per pose); `zs` ([V,K,3,H,W] or a callable (v0, v1) -> that slice)
+        replaces the random draws of the poses' probes there."""
         crit = _criterion(criterion)
         flags = dict(use_rot=use_rot, use_scale=use_scale, use_opacity=use_opacity)
+        if fused:
+            Hm, train_idx = _fused_block_prior(self, int(K), None, flags)
+            c2w_all = self._stack_poses(poses)
+            scores = _fused_block_scores(self, torch.linalg.inv(c2w_all), int(K), Hm, train_idx, lam, crit, flags, zs)
+            return scores.float().cpu(), c2w_all
         Hm, train_idx = self.compute_H_train_blocks(K=K, **flags)
         scores, c2ws = [], []
         for c2w in poses:

@@ -86,6 +86,7 @@ typedef void* fr_stream_t; /* hipStream_t */
 /* Camera / raster settings: GaussianRasterizationSettings, RAST/diff_gaussian_rasterization/__init__.py:140-151.
  * bg / viewmatrix / projmatrix / campos stay DEVICE pointers, as in the reference (they are CUDA tensors there);
  * viewmatrix and projmatrix are the 16 floats of the transposed tensors, i.e. column-major matrices. */
+struct fr_raster_ext;
 typedef struct fr_raster_cfg {
 	int32_t P;
 	int32_t image_height;
@@ -101,6 +102,9 @@ typedef struct fr_raster_cfg {
 	const float* viewmatrix;
 	const float* projmatrix;
 	const float* campos;
+	const struct fr_raster_ext* ext; /* null: every entry point is what it was before this field existed, bit for bit.  Only
+	                                    fr_fisher_views reads it (the POp-GS block stage, below its declaration); every other
+	                                    entry point ignores the field */
 } fr_raster_cfg;
 
 /* Gaussian inputs; a null pointer stands for the reference's empty tensor. */
@@ -396,6 +400,75 @@ size_t fr_popgs_diag_criterion_workspace_bytes(int32_t V, int64_t E);
 int fr_popgs_diag_criterion(int32_t V, int32_t K, int64_t E, const float* rows, const float* prior_in, int64_t prior_in_view_stride,
                             float* prior_out, const uint8_t* accumulate, const int32_t* vis_count, float lam, int32_t criterion,
                             double* scores, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+
+/* ---- POp-GS block criteria over probe rows: an extension of fr_raster_cfg, no export of its own -------------------------
+ * The reference scores a pose from the block estimator per pose: one more render for `radius > 0`, an einsum to [Nv,d,d], two isin,
+ * batched LAPACK on binary32 blocks of condition ~ |J| / lam, one float read back (models/SLAM/gaussian_object.py:2111-2176, 1572-1585,
+ * 1660-1732).  With cfg->ext set, fr_fisher_views IS A DIFFERENT CALL THAT RENDERS NOTHING: the block stage over probe rows the caller
+ * already has (what fr_fisher_views wrote into out_H per view under dL_dpix_image).  It branches before any other validation.
+ *
+ * What the stage reads from the ordinary arguments:
+ *   cfg        P (at least 1), image size, tanfovx / tanfovy, scale_modifier, viewmatrix, projmatrix (the last six only where a
+ *              visibility is computed), ext
+ *   g          means3D, scales, rotations where a visibility is computed (else g may be null); a non-null cov3D_precomp: FR_EINVAL
+ *   cfg_f      n_views = poses * K; w2c [n_views,16] -- pose p is read from view p K (the caller repeats it per probe); columns = 11;
+ *              out_H = the rows [n_views, P, 11], an INPUT here; out_H_view_stride = 11 P.  Every other field zero / null, else FR_EINVAL
+ *   workspace  FR_POPGS_BLOCK_WS_BYTES(P, poses) bytes, 8-byte aligned (smaller: FR_ENOSPACE)
+ *   max_rendered  ignored
+ *   status     device int32[4] = {PRIOR: n; SCORE: pairs matched over all poses; VISIBLE: 0,
+ *                                 0,
+ *                                 SCORE: factorisations that met a non-positive pivot (A1 of a pair; A0 too under D-opt),
+ *                                 SCORE: prior rows skipped for an index outside [0, P)}
+ * d = 3 + use_opacity + 4 use_rot + 3 use_scale; a block's columns are the row's columns [0,1,2 | 3 | 7..10 | 4..6] (mean, opacity,
+ * rot, scale: the reference's order), those present.
+ *
+ * FR_POPGS_BLOCK_VISIBLE  out_vis[p,i] = 1 where Gaussian i has radius > 0 in pose p, else 0; out_vis_count[p] = their number (what
+ *     out_vis_count of a rendering call reports).  Camera-frame mean ((w0 x + w1 y) + w2 z) + w3 per row of the pose, unfused, then the
+ *     single-view rasteriser's own projection: the mask is its `radii > 0`, bit for bit.  The rows may be null.
+ * FR_POPGS_BLOCK_SCORE    visibility from vis_in where given (no geometry is read), else computed as above (and written to out_vis /
+ *     out_vis_count where given).  For pose p and prior row r with i = prior_idx[r] visible in p, all in binary64:
+ *         G_k = the d selected columns of row (p K + k, i);  J = (sum_k G_k G_k^T) / K, k ascending
+ *         A0 = lower triangle of prior_blocks[r] + lam I;  A1 = A0 + J;  both factorised as an unpivoted L D L^T with pivots pi
+ *         T-opt term: - trace(A1^-1), from the factor;  D-opt term: sum log|pi(A1)| - sum log|pi(A0)|  (exactly 0.0 when every G_k is
+ *         zero: the two factorisations are then the same operations).  A non-positive pivot is counted, the value still formed from |pi|.
+ *     out_scores[p] = the sum over r in a fixed order: per thread (r ascending in steps of the grid), the workgroup's 256 threads, one
+ *     partial per workgroup, a pose's partials in index order; the workgroups per pose depend on n alone.  No atomics: the same call
+ *     gives the same bits, and a pose's score does not depend on its batch.  out_matched[p] = the pairs; a pose with none scores -inf.
+ *     prior_idx need not be sorted; an index outside [0, P) skips the row (never dereferenced) and is counted.
+ * FR_POPGS_BLOCK_PRIOR    compute_H_train_blocks, the reference's truncation kept (gaussian_object.py:1577-1584): views are keyframes x K.
+ *     Each keyframe's visible Gaussians are listed ascending; n = the smallest count; prior_idx[r] = the first keyframe's r-th visible
+ *     index; prior_blocks[r] = sum over the keyframes, in order, of that keyframe's block at ITS r-th visible Gaussian (by position, not
+ *     by index), a block = binary32 (sum_k g_a g_b) / K as fma(g_a, g_b, b) from 0 with k ascending -- the chain of the reference's einsum --,
+ *     all d x d entries written.  ext->n is the capacity of
+ *     the two outputs: rows r < min(n, ext->n) are written; status[0] = n is the call's one host read.
+ * No device allocation, no host synchronisation.  poses at most 65535. */
+enum { FR_EXT_POPGS_BLOCK = 1 };
+enum { FR_POPGS_BLOCK_VISIBLE = 0, FR_POPGS_BLOCK_SCORE = 1, FR_POPGS_BLOCK_PRIOR = 2 };
+#define FR_POPGS_BLOCK_MAX_WG 256      /* workgroups (partials) per pose of the SCORE pass: min(this, ceil(n / 256)) */
+#define FR_POPGS_BLOCK_ALIGN(x) ((((size_t)(x)) + 255) & ~(size_t)255)
+#define FR_POPGS_BLOCK_WGS(P) ((((size_t)(P)) + 255) / 256)
+/* sections, each on 256 bytes: visibility u8[poses,P], visible lists i32[poses,P], counts and offsets u32[poses, ceil(P/256)] each,
+ * list lengths u32[poses], partials 32 B x [poses, FR_POPGS_BLOCK_MAX_WG] */
+#define FR_POPGS_BLOCK_WS_BYTES(P, poses) \
+	(FR_POPGS_BLOCK_ALIGN((size_t)(poses) * (size_t)(P)) + FR_POPGS_BLOCK_ALIGN((size_t)(poses) * (size_t)(P) * 4) + \
+	 2 * FR_POPGS_BLOCK_ALIGN((size_t)(poses) * FR_POPGS_BLOCK_WGS(P) * 4) + FR_POPGS_BLOCK_ALIGN((size_t)(poses) * 4) + \
+	 FR_POPGS_BLOCK_ALIGN((size_t)(poses) * FR_POPGS_BLOCK_MAX_WG * 32))
+typedef struct fr_raster_ext {
+	int32_t kind;                 /* FR_EXT_POPGS_BLOCK; anything else: FR_EINVAL */
+	int32_t mode;                 /* FR_POPGS_BLOCK_VISIBLE / _SCORE / _PRIOR */
+	int32_t K;                    /* probes per pose */
+	int32_t use_opacity, use_rot, use_scale;   /* 0 or 1 each */
+	int32_t criterion;            /* SCORE: FR_POPGS_TOPT / FR_POPGS_DOPT */
+	int32_t n;                    /* SCORE: prior rows; PRIOR: capacity of prior_blocks / prior_idx in rows */
+	double lam;                   /* SCORE */
+	const uint8_t* vis_in;        /* SCORE: device [poses,P] bytes or null */
+	uint8_t* out_vis;             /* device [poses,P] bytes or null (VISIBLE: this or out_vis_count) */
+	int32_t* out_vis_count;       /* device [poses] or null */
+	float* prior_blocks;          /* device [n,d,d] binary32: SCORE reads it, PRIOR writes it */
+	int32_t* prior_idx;           /* device [n]: SCORE reads it, PRIOR writes it */
+	double* out_scores;           /* SCORE: device [poses] binary64 */
+	int32_t* out_matched;         /* SCORE: device [poses] */
+} fr_raster_ext;
 
 /* ---- densification / pruning statistics of the training step ---------------------------
  * One pass over the Gaussians each, in place of the torch-op chains of models/SLAM/gaussian.py:289-291 and
